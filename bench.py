@@ -17,14 +17,17 @@ at the true coefficients) and, for N>1, the algorithm's one round of communicati
 a single all-reduce (RCCL over xGMI) of the [Sig_inv | Sig_inv.theta | theta] message (p^2+2p doubles).
 value = total rows of all ranks / max-over-ranks time.
 
-The same JSON line carries `roofline` (Gram kernel vs the fp64 MFMA peak, HIP-event timed on the launch stream),
-`allreduce` (the collective, timed inside the steps and on its own), `cpu_baseline` (the numpy oracle of the hot
-path on the host cores, bounded sample; N=1 only) and `extra` (the HBM-bound logit pass, optionally the whole fit).
+The same JSON line carries `roofline` (Gram kernel vs the fp64 MFMA peak, HIP-event timed on the launch stream, from the
+timed steps themselves) and `allreduce` (the collective, timed inside the steps).
 
-Order of an N = 1 run: generate the shard -> W + K steps (`value`) -> the same launch until the GPU has been busy for
---sustain-seconds (`sustained_block`) -> the CPU baseline in freshly spawned interpreters -> the K steps once more
-(`second_block`).  N > 1 starts with a PREFLIGHT per rank (devices, free HBM, communicator and one 8-byte all-reduce under
-60 s watchdogs: a one-line reason and a non-zero exit, never a hang); `--preflight` runs only that.
+A plain run is: generate the shard -> W warm-up steps (extended until two launches agree, --warmup-cap-seconds) -> K timed
+steps (`value`, `ms_per_step`) -> --dump-outputs DIR, if given, writes the last step's Gram matrix -> the line.
+--full adds what takes runs of its own, after the K steps: for N = 1 the same launch until the GPU has been busy for
+--sustain-seconds (`sustained_block`), the CPU baseline in freshly spawned interpreters (`cpu_baseline`: the numpy oracle of
+the hot path on the host cores, bounded sample) and the K steps once more (`second_block`); for N > 1 the strong-scaling
+leg and the all-reduce on its own; then `extra` (the HBM-bound logit pass, the end-to-end fit legs).  N > 1 starts with a
+PREFLIGHT per rank (devices, free HBM, communicator and one 8-byte all-reduce under 60 s watchdogs: a one-line reason and a
+non-zero exit, never a hang); `--preflight` runs only that.
 """
 import argparse
 import hashlib
@@ -42,6 +45,7 @@ if ROOT not in sys.path:
 FP64_MFMA_PEAK_TF = 78.6    # 256 CU x 4 SIMD x 32 flop/clk x 2.4 GHz (= fp32 vector 157.3 / 2)
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8.0 TB/s spec
 STRONG_MIN_ROWS = 65536     # rows per launch below which the library leaves the cyclic p = 500 Gram kernel (gram.hip)
+DUMP_CAP_BYTES = 60 << 20   # --dump-outputs writes at most this much (under 64 MB with the .npy headers)
 
 
 def parse(argv=None):
@@ -54,7 +58,7 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=20260101)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--e2e", action="store_true", help="(default since round 6; kept so that older command lines still parse)")
+    ap.add_argument("--e2e", action="store_true", help="(part of --full; kept so that older command lines still parse)")
     ap.add_argument("--no-e2e", action="store_true",
                     help="leave out the end-to-end fit legs (`extra.end_to_end_fit`): every gram_cyclic_kernel launch of the command then\n"
                          "has the benchmark's size, which is what bench/profile_round.sh wants for rocprofv3's per-kernel averages")
@@ -71,13 +75,20 @@ def parse(argv=None):
                     help="only the N-rank preflight (device count, free HBM for the shard, RCCL communicator + one 8-byte all-reduce, each\n"
                          "under a 60 s watchdog): exit code 0 and one line per rank, or non-zero with the reason -- never hangs")
     ap.add_argument("--sustain-seconds", type=float, default=12.0,
-                    help="after the K timed steps keep launching the same Gram pass until the GPU has been busy this long (N = 1): the\n"
+                    help="--full: after the K timed steps keep launching the same Gram pass until the GPU has been busy this long (N = 1): the\n"
                          "driver's utilisation sampler sees the run, and the line carries the sustained ms_per_step")
     ap.add_argument("--watchdog-seconds", type=float, default=900.0,
                     help="a rank that is still running after this long prints every thread's Python stack and leaves with exit code 1\n"
-                         "(a hang becomes a reason; the default run takes ~2.5 min at N = 1 with the CPU baseline, ~1 min at N = 8); 0: off")
+                         "(a hang becomes a reason; a --full run takes ~2.5 min at N = 1 with the CPU baseline, ~1 min at N = 8); 0: off")
     ap.add_argument("--cpu-rows-per-partition", type=int, default=0, help="0 = sized by oracle/cpu_baseline.py")
     ap.add_argument("--cpu-gram-rows", type=int, default=400_000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the legs that take runs of their own: the sustained block, the CPU baseline and\n"
+                         "the second block (N = 1), the strong-scaling leg and the isolated all-reduce (N > 1), the logit pass and the\n"
+                         "end-to-end fit legs (--no-cpu-baseline / --no-extra / --no-e2e / --sustain-seconds 0 leave single legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: the p x p Gram matrix after the step's all-reduce) as\n"
+                         "DIR/H.npy (float64; a fixed seeded sample of its entries beyond %d MB)" % (DUMP_CAP_BYTES >> 20))
     return ap.parse_args(argv)
 
 
@@ -162,6 +173,20 @@ def traffic_from_profile(p, R):
                              "MI355X_MICROARCH.md; Gram sources %s)" % have)
     except Exception as e:
         return None, "unavailable: %r" % (e,)
+
+
+def dump_outputs(outdir, arrays):
+    """outdir/<name>.npy for every float64 array of `arrays`.  Beyond DUMP_CAP_BYTES in all, each array keeps the same share of its
+    entries, a fixed seeded sample (flattened, in index order): two builds given the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(a.size * 8 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if total > DUMP_CAP_BYTES:
+            idx = np.random.default_rng(0).choice(a.size, a.size * DUMP_CAP_BYTES // total, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def _watchdog(seconds, what, rank):
@@ -351,6 +376,8 @@ def worker(args):
         return {"min": min(vals), "max": max(vals), "mean": sum(vals) / len(vals), "per_rank": vals}
 
     elapsed, kern_ms, comm_ms, step_ms = timed_steps(X, w, args.steps, args.warmup, settle_cap_s=args.warmup_cap_seconds)
+    if args.dump_outputs and rank == 0:          # before any later leg writes H again
+        dump_outputs(args.dump_outputs, {"H": H.cpu().numpy()})
     last_ms = step_ms[-1]
     median_ms = sorted(step_ms)[len(step_ms) // 2]
     first_ranks = per_rank(step_ms[0])
@@ -366,15 +393,15 @@ def worker(args):
               % ((kern_ranks["max"] / kern_ranks["min"] - 1) * 100, slow, kern_ranks["max"], clock_ranks["per_rank"][slow], kern_ranks["min"]),
               file=sys.stderr, flush=True)
 
-    # ---- N = 1: the same launches again until the GPU has been busy for --sustain-seconds (the driver's utilisation sampler sees the
-    # run; the rate a long job holds), THEN the CPU baseline (fresh spawned interpreters, the GPU idle), then the K steps a second time
+    # ---- --full, N = 1: the same launches again until the GPU has been busy for --sustain-seconds (the driver's utilisation sampler sees
+    # the run; the rate a long job holds), THEN the CPU baseline (fresh spawned interpreters, the GPU idle), then the K steps a second time
     sustained = second_block = None
-    if world == 1 and args.sustain_seconds > 0:
+    if args.full and world == 1 and args.sustain_seconds > 0:
         nsus = int(max(0.0, args.sustain_seconds - elapsed) / max(1e-6, kern_ms * 1e-3))
         if nsus > 0:
             s_el, s_kern, _, _ = timed_steps(X, w, nsus, 0)
             sustained = {"steps": nsus, "seconds": s_el, "ms_per_step": s_el / nsus * 1e3, "kernel_ms": s_kern, "value": R * nsus / s_el}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # a REPORTED reference point: its failure (a worker, the pool's barrier, a missing gcc / liboracle_synth, host memory)
         # must not cost the primary GPU line
         try:
@@ -390,16 +417,17 @@ def worker(args):
         second_block = {"steps": args.steps, "ms_per_step": b_el / args.steps * 1e3, "kernel_ms": b_kern, "value": R * args.steps / b_el,
                         "note": "the same K steps once more after the CPU baseline (GPU cold again): the line's `value` is the FIRST block"}
 
-    # ---- strong scaling leg (N > 1): the SAME total rows as one GPU's shard, split evenly over the ranks
+    # ---- --full, strong scaling leg (N > 1): the SAME total rows as one GPU's shard, split evenly over the ranks
     strong = None
-    if dist is not None and args.scaling in ("strong", "both") and R // world < STRONG_MIN_ROWS:
+    want_strong = args.full and dist is not None and args.scaling in ("strong", "both")
+    if want_strong and R // world < STRONG_MIN_ROWS:
         # fewer rows per rank than the p = 500 Gram kernel of the weak-scaling line takes: another kernel would run, and the leg would
         # compare kernels, not GPUs -- say so instead of changing kernels silently
         strong = {"scaling": "strong", "skipped": "rows_per_gpu / N = %d is under the %d rows per launch the metric's kernel needs "
                                                   "(gram_cyclic_kernel); run with a larger --rows-per-gpu" % (R // world, STRONG_MIN_ROWS)}
         if rank == 0:
             print("[bench] strong-scaling leg skipped: " + strong["skipped"], file=sys.stderr, flush=True)
-    elif dist is not None and args.scaling in ("strong", "both"):
+    elif want_strong:
         Rs = R // world
         s_el, s_kern, s_comm, _ = timed_steps(X[:Rs], w[:Rs], args.steps, args.warmup)
         s_name, _ = engine.gram_last_kernel()
@@ -409,9 +437,13 @@ def worker(args):
                   "note": "every rank takes the first total_rows / N rows of its own resident shard (same distribution, "
                           "same seeded stream); speed-up vs N=1 = value / the N=1 run's value"}
 
-    # ---- the collective on its own (all ranks): 20 back-to-back all-reduces of the message
+    # ---- the collective (all ranks): its time inside the steps; with --full also on its own, 20 back-to-back all-reduces of the message
     allreduce = None
     if dist is not None:
+        nbytes = msg.numel() * 8
+        allreduce = {"backend": "rccl" if backend == "nccl" else backend, "ranks": world, "payload_bytes": nbytes,
+                     "ms_in_step": comm_ms, "ms_isolated": None, "busbw_GBps_isolated": None}
+    if dist is not None and args.full:
         reps = 20
         for _ in range(3):
             dist.all_reduce(msg)
@@ -422,10 +454,8 @@ def worker(args):
         barrier()
         iso = torch.tensor([(time.perf_counter() - t1) / reps * 1e3], dtype=torch.float64, device="cuda")
         dist.all_reduce(iso, op=dist.ReduceOp.MAX)
-        nbytes = msg.numel() * 8
-        allreduce = {"backend": "rccl" if backend == "nccl" else backend, "ranks": world, "payload_bytes": nbytes,
-                     "ms_in_step": comm_ms, "ms_isolated": float(iso.item()),
-                     "busbw_GBps_isolated": 2.0 * (world - 1) / world * nbytes / (float(iso.item()) * 1e-3) / 1e9}
+        allreduce.update({"ms_isolated": float(iso.item()),
+                          "busbw_GBps_isolated": 2.0 * (world - 1) / world * nbytes / (float(iso.item()) * 1e-3) / 1e9})
 
     out = None
     if rank == 0:
@@ -473,9 +503,10 @@ def worker(args):
             "strong_scaling": strong,
         }
 
-    # ---- extras: the HBM-bound logit pass (rank 0, N = 1), the end-to-end fit legs (every rank takes part when N > 1; --no-e2e leaves them out)
+    # ---- --full extras: the HBM-bound logit pass (rank 0, N = 1), the end-to-end fit legs (every rank takes part when N > 1; --no-e2e
+    # leaves them out)
     extra = {"gen_seconds": t_gen}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         e0, e1 = mk(), mk()
         engine.logit_pass(X, y, beta_true)
         torch.cuda.synchronize()
@@ -488,7 +519,7 @@ def worker(args):
         extra["logit_pass"] = {"ms": ms, "rows_per_s": R / (ms * 1e-3),
                                "hbm_GBps": R * 8 * (p + 2) / (ms * 1e-3) / 1e9,
                                "hbm_frac_of_8TBps": R * 8 * (p + 2) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-    if not args.no_e2e and not args.no_extra:
+    if args.full and not args.no_e2e and not args.no_extra:
         # The whole path on every rank's shard (the C3 geometry of logistic_dlsa.py:170: partitions of 1e6 rows): per-partition
         # exact-MLE fits + Hessians -> local block sum -> ONE all-reduce of p^2 + 2p + 1 doubles -> WLS solve + LARS on every
         # rank (redundant: cheaper than a broadcast).  Wall time = max over ranks, barrier-bracketed.  A rank whose fit raises does

@@ -8,6 +8,6 @@ bench/profile_round.sh $TAG > $OUT/profile_round.log 2>&1
 python3 bench/pmc_evidence.py $TAG narrow_p100 > $OUT/pmc_evidence.log 2>&1
 cp profiles/${TAG}_pmc_narrow_p100.json $OUT/ 2>/dev/null
 python3 bench/bench_configs.py > $OUT/configs.jsonl 2> $OUT/configs.err
-DLSA_BENCH_BACKEND=gloo python3 bench.py --gpus 8 --rows-per-gpu 2000000 > $OUT/bench_gloo8_dryrun.json 2> $OUT/bench_gloo8_dryrun.err
-python3 bench.py --gpus 1 --rows-per-gpu 2000000 --no-cpu-baseline > $OUT/bench_rows2e6_n1.json 2> $OUT/bench_rows2e6_n1.err
+DLSA_BENCH_BACKEND=gloo python3 bench.py --gpus 8 --rows-per-gpu 2000000 --full > $OUT/bench_gloo8_dryrun.json 2> $OUT/bench_gloo8_dryrun.err
+python3 bench.py --gpus 1 --rows-per-gpu 2000000 --no-cpu-baseline --full > $OUT/bench_rows2e6_n1.json 2> $OUT/bench_rows2e6_n1.err
 tail -3 $OUT/profile_round.log; tail -2 $OUT/pmc_evidence.log; wc -l $OUT/configs.jsonl; tail -c 300 $OUT/bench_gloo8_dryrun.err

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 ./bench/probe_mfma4x4 > $OUT/probe_mfma4x4.txt 2>&1
 # 0. the driver's command, unprofiled, in the SAME call (same box, same minute) as the profiled run below: the round's committed
 #    default line (profiles/<tag>_bench_default.json) and the reference point of the 3 % guard in tests/test_bench_cpu.py
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 # 1. per-kernel time of the same command under rocprofv3 (--no-e2e: without the fit legs every gram_cyclic_kernel launch has the
 #    benchmark's size, so rocprofv3's own per-kernel average IS the metric kernel's; --no-cpu-baseline: host work only)
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --rows-per-gpu $ROWS --no-cpu-baseline --no-e2e > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
@@ -62,8 +62,8 @@ if un and pr:
                         "unprofiled_ms_per_step": un["ms_per_step"], "profiled_kernel_ms_hip_events": pr["roofline"]["kernel_ms"],
                         "profiled_clock_GHz": pr["roofline"]["shader_clock_GHz"], "rocprof_csv_avg_ms": csv_avg[0] if csv_avg else None,
                         "rocprof_over_unprofiled": (csv_avg[0] / un["roofline"]["kernel_ms"]) if csv_avg else None,
-                        "note": "one gpurun call: python3 bench.py --gpus 1 --steps 20 --warmup 5, then the same command with "
-                                "--no-cpu-baseline --no-e2e under rocprofv3 --kernel-trace --stats"}
+                        "note": "one GPU job: python3 bench.py --gpus 1 --steps 20 --warmup 5 --full, then the same command without "
+                                "--full, with --no-cpu-baseline --no-e2e, under rocprofv3 --kernel-trace --stats"}
     print(json.dumps(out["same_call"], indent=1))
 json.dump(out, open("$OUT/pmc_summary.json", "w"), indent=1, sort_keys=True)
 print(json.dumps(out["kernel_ms"], indent=1))

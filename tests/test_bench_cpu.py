@@ -156,7 +156,7 @@ def test_launcher_exports_the_per_rank_thread_count(monkeypatch):
 
 
 def test_bench_arguments_round6():
-    """the end-to-end fit legs are part of the default line (--no-e2e leaves them out; --e2e still parses), and the warm-up is
+    """the end-to-end fit legs are part of the --full line (--no-e2e leaves them out; --e2e still parses), and the warm-up is
     extended until two launches agree, for at most --warmup-cap-seconds"""
     bench = _load_bench()
     a = bench.parse([])
@@ -165,6 +165,31 @@ def test_bench_arguments_round6():
     src = open(os.path.join(ROOT, "bench.py")).read()
     for key in ("first_over_median", "warmup_extra_steps", "first_step_ms_over_ranks", '"k1"', '"lock_step"', "passes_per_partition"):
         assert key in src, key
+
+
+def test_bench_arguments_full_and_dump():
+    """A plain run is the headline figure alone: the other legs need --full; --dump-outputs takes a directory."""
+    bench = _load_bench()
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float64_and_samples_beyond_the_cap(monkeypatch, tmp_path):
+    bench = _load_bench()
+    H = np.arange(30.0).reshape(5, 6)
+    bench.dump_outputs(str(tmp_path / "all"), {"H": H})
+    assert np.array_equal(np.load(str(tmp_path / "all" / "H.npy")), H)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 8 * 20)
+    big = {"H": H, "v": np.arange(10, dtype=np.float32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in big}
+    assert sum(g.nbytes for g in got.values()) <= 8 * 20 and all(g.dtype == np.float64 for g in got.values())
+    assert set(got["H"]) <= set(H.ravel()) and list(got["H"]) == sorted(got["H"]) and got["H"].size == 30 * 20 // 40
+    for k in big:                                    # the sample is fixed: the same entries every time
+        assert np.array_equal(got[k], np.load(str(tmp_path / "b" / (k + ".npy"))))
 
 
 def test_bench_arguments_round4():

@@ -195,7 +195,7 @@ def test_bench_gpus_2_launches_two_ranks_itself():
     """`python bench.py --gpus 2` with no torch.distributed environment must start the two ranks itself (gloo here:
     two RCCL ranks cannot share the test box's single GPU) and report n_gpus = 2 with the reduce timed."""
     out = _run_bench({"DLSA_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--rows-per-gpu", "2000000", "--steps", "3",
-                     "--warmup", "1")
+                     "--warmup", "1", "--full")
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1
     assert out["rccl_ranks"] == 0 and out["allreduce"]["backend"] == "gloo" and out["allreduce"]["ranks"] == 2
     assert out["allreduce"]["payload_bytes"] == (500 * 500 + 2 * 500) * 8
@@ -206,7 +206,7 @@ def test_bench_gpus_2_launches_two_ranks_itself():
 
 
 def test_bench_single_gpu_line_keeps_its_contract():
-    out = _run_bench({}, "--rows-per-gpu", "2000000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    out = _run_bench({}, "--rows-per-gpu", "2000000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in out
@@ -214,7 +214,7 @@ def test_bench_single_gpu_line_keeps_its_contract():
     r = out["roofline"]
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
     assert r["traffic"] is None or r["traffic"] > r["algorithmic_bytes_per_launch"] * 0.5
-    # round 6: the slow-start guards and the fit legs are part of the default line
+    # round 6: the slow-start guards are part of every line, the fit legs of the --full line
     assert out["warmup_extra_steps"] >= 1 and out["first_step_ms"] > 0 and out["median_step_ms"] > 0
     assert abs(out["first_over_median"] - out["first_step_ms"] / out["median_step_ms"]) < 1e-12 and out["first_over_median"] < 1.5
     e2e = out["extra"]["end_to_end_fit"]
@@ -222,6 +222,25 @@ def test_bench_single_gpu_line_keeps_its_contract():
     assert e2e["k1"]["status_ok"] and e2e["k1"]["partitions_per_rank"] == 1 and e2e["k1"]["passes_per_partition"]["max"] >= 1
     ls = e2e["lock_step"]
     assert ls["status_ok"] and ls["fit_path"] == 2 and ls["partitions"] == 1000 and 0 < ls["fit_s"] < 1.0
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_step(eng, tmp_path):
+    """Without --full the line is the headline figure alone (no CPU baseline, sustained or second block, fit legs); --dump-outputs
+    writes the Gram matrix of the last timed step, which is X' diag(w) X of the seeded shard."""
+    R, seed = 200000, 20260101
+    out = _run_bench({}, "--rows-per-gpu", str(R), "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert out["n_gpus"] == 1 and out["steps"] == 4 and out["config"]["rows_per_gpu"] == R
+    assert abs(out["value"] - R * 4 / (out["ms_per_step"] * 4e-3)) / out["value"] < 1e-6
+    assert out["cpu_baseline"] is None and out["sustained_block"] is None and out["second_block"] is None
+    assert set(out["extra"]) == {"gen_seconds"}
+    H = np.load(str(tmp_path / "H.npy"))
+    assert H.dtype == np.float64 and H.shape == (500, 500)
+    X, y = eng.synth(seed, 0, R, 500, kind=eng.SYNTH_GAUSSIAN, labels=True)
+    beta = torch.zeros(500, dtype=torch.float64, device="cuda")
+    beta[:200] = 1.0
+    w, _, _ = eng.logit_pass(X, y, beta, want_g=False, want_loglik=False)
+    ref = (X.T @ (w[:, None] * X)).cpu().numpy()
+    assert rel_inf(H, ref) < 1e-12
 
 
 def test_bench_refuses_world_size_mismatch():
