@@ -1,0 +1,59 @@
+"""Timing of the Cox map step (csrc/cox.hip): one Newton iteration (dlsa_cox_pass_f64 + the Cholesky solve) and the scan pass
+alone, at 1e7 x 100 and 2e6 x 500, on rows stored in time order and on shuffled rows.  Prints one JSON line per case with the
+algorithmic bandwidth of the row passes against the traffic model:
+  eta pass + scan pass: 2 reads of the rows (8 p bytes each) + the Gram's read of the rows (8 p) + A written and read
+  (8 p per event row).  Run under rocprofv3 --kernel-trace --stats for the per-kernel split."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dlsa_amd import engine  # noqa: E402
+
+
+def case(n, p, shuffled, reps):
+    X, _ = engine.synth(321, 0, n, p, labels=False)
+    beta = torch.zeros(p, dtype=torch.float64, device="cuda")
+    beta[: int(0.4 * p)] = 1.0
+    g = torch.Generator(device="cuda").manual_seed(9)
+    t = torch.empty(n, dtype=torch.float64, device="cuda").exponential_(generator=g) / torch.exp(X @ beta)
+    ev = (torch.rand(n, dtype=torch.float64, device="cuda", generator=g) > 0.3).to(torch.float64)
+    order = torch.sort(-t, stable=True).indices
+    if not shuffled:                 # store the rows in time order: `order` becomes the identity
+        X = X[order].contiguous(); t = t[order].contiguous(); ev = ev[order].contiguous()
+        order = torch.arange(n, device="cuda", dtype=torch.int64)
+    b = beta * 0.5
+    for _ in range(2):
+        engine.cox_pass(X, t, ev, order, b)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        H, gr, ll, _ = engine.cox_pass(X, t, ev, order, b)
+        engine.spd_solve(H, gr)
+    e1.record()
+    torch.cuda.synchronize()
+    it_ms = e0.elapsed_time(e1) / reps
+    events = float(ev.sum().item())
+    traffic = 8.0 * p * (3 * n + 2 * events)
+    return {"n": n, "p": p, "order": "shuffled" if shuffled else "sorted", "newton_iter_ms": round(it_ms, 3),
+            "events": int(events), "model_bytes": traffic, "algorithmic_TBps_iter": round(traffic / (it_ms * 1e-3) / 1e12, 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--small", action="store_true", help="1e6 x 100 only (a quick check)")
+    a = ap.parse_args()
+    shapes = [(1_000_000, 100)] if a.small else [(10_000_000, 100), (2_000_000, 500)]
+    for n, p in shapes:
+        for sh in (False, True):
+            print(json.dumps(case(n, p, sh, a.reps)), flush=True)
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

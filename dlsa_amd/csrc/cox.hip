@@ -1,0 +1,717 @@
+// Cox proportional-hazards map step (Breslow ties): one partition's log partial likelihood, score and observed information
+// at a fixed beta, and the per-partition Newton fit on top of it.  The local objective of a partition is its own partial
+// likelihood with risk sets taken inside the partition (a Cox model stratified by partition with a common beta); the blocks
+// it returns (coef, Sig_inv = observed information at coef, Sig_inv coef) feed the unchanged one-round combine.
+//
+// Algebra (one partition, rows in DESCENDING time through the caller's permutation `order`; eta_j = x_j' beta; tie groups
+// are runs of equal time; group i has d_i events and ends at position e_i):
+//   S0_i = sum_{pos <= e_i} exp(eta),  S1_i = sum_{pos <= e_i} exp(eta) x,  a_i = S1_i / S0_i         (forward prefix)
+//   loglik = sum_events eta - sum_i d_i log S0_i,   U = X' delta - A' d
+//   H = X' diag(w) X - A' diag(d) A,  w_j = exp(eta_j) c_j,  c_j = sum_{i : e_i >= pos(j)} d_i / S0_i  (suffix over groups)
+// so H is two weighted Grams on the existing MFMA kernels (X in its own row layout, and the D event rows of A) and no
+// p x p work per event.
+//
+// Passes (every partial combines in a fixed order: no float atomics, no waits between workgroups inside a launch):
+//   1 cox_eta_kernel      one wave per segment of L consecutive positions: eta (written per position), the segment's
+//                         max eta M and sums of exp(eta - M) [1, x], and the tie-group bookkeeping of the segment;
+//   2 cox_segscan_kernel  exclusive prefix over segments, one workgroup per column (a block total is rescaled by its
+//                         max when combined), plus the open tie group entering every segment and the index of its
+//                         first event row of A;
+//   3 cox_scan_kernel     the segment re-walked from its prefix: A rows (a chunk of them per launch), the segment's
+//                         partials of loglik and U, and d_i / S0_i at every group end;
+//   4 cox_finish_kernel + cox_w_kernel: the suffix sum of d_i / S0_i (over segments, then inside each segment by wave
+//                         scans) and w; the column sums of the loglik and U partials;
+//   5 the two Grams: dlsa_gram_f64(A, -d) per chunk and dlsa_gram_f64(X, w) accumulated into H.
+// Scaled sums: a prefix (M, v) stands for v exp(M) with M the max eta it covers, a suffix (Q, v) for v exp(-Q) with Q the
+// smallest group max it covers, so every exponential has a non-positive argument (no overflow at any eta range) and a
+// ratio never sees an underflowed denominator.
+#include "common.h"
+#include <math.h>
+#include <algorithm>
+#include <vector>
+
+typedef double dlsa_cox_d2v __attribute__((ext_vector_type(2)));
+
+namespace dlsa {
+
+#include "logistic.h"      // exp_neg
+#include "rowdot.h"        // merged_reduce, row_of_lane, lane_of_row, read_lane_f64
+
+int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
+                  int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t gram_workspace_bytes_impl(int64_t n, int p, int elem_bytes);
+int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
+                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
+                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);
+int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s);
+int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
+int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
+
+constexpr int COX_THREADS = 256;
+constexpr int COX_WAVES = COX_THREADS / 64;
+constexpr int COX_RB = 4;                      // rows per batch of a wave (one merged butterfly for their dot products)
+constexpr int64_t COX_MAX_SEGS = 4096;
+constexpr size_t COX_A_BYTES = 256ull << 20;   // bound of the A chunk
+
+static __device__ __forceinline__ double2 cox_ld2(const double* ptr, bool vec, int col, int p) {
+    double2 r;
+    const int c0 = col < p ? col : 0;
+    if (vec) {
+        const dlsa_cox_d2v t = __builtin_nontemporal_load(reinterpret_cast<const dlsa_cox_d2v*>(ptr + c0));
+        r.x = t.x; r.y = t.y;
+    } else {
+        r.x = __builtin_nontemporal_load(ptr + c0);
+        r.y = __builtin_nontemporal_load(ptr + (col + 1 < p ? col + 1 : 0));
+    }
+    if (col >= p) r.x = 0.0;
+    if (col + 1 >= p) r.y = 0.0;
+    return r;
+}
+
+// (M, v) = v exp(M): combination of two prefix sums
+static __device__ __forceinline__ void pre_comb(double& M, double& v, double Mb, double vb) {
+    if (Mb == -INFINITY) return;
+    if (M == -INFINITY) { M = Mb; v = vb; return; }
+    const double Mn = fmax(M, Mb);
+    v = v * exp_neg(Mn - M) + vb * exp_neg(Mn - Mb);
+    M = Mn;
+}
+// (Q, v) = v exp(-Q): combination of two suffix sums (v = 0 is empty)
+static __device__ __forceinline__ void suf_comb(double& Q, double& v, double Qb, double vb) {
+    if (vb == 0.0) return;
+    if (v == 0.0) { Q = Qb; v = vb; return; }
+    const double Qn = fmin(Q, Qb);
+    v = v * exp_neg(Q - Qn) + vb * exp_neg(Qb - Qn);
+    Q = Qn;
+}
+
+struct CoxArgs {
+    const double* X; int64_t ldx;
+    const double* time; const double* event; const int64_t* order;
+    int64_t n; int p; int64_t L; int nseg; int ld;      // ld: columns of the column-major segment arrays = nseg
+    const double* beta;
+    double* eta;          // [n] per position
+    double* hzv; double* hzq;        // [n] d / S0 at event-group ends as (Q, v), v = 0 elsewhere
+    double* segM; double* segV;      // [nseg], [(p + 1) x nseg]: segment totals (col 0 = S0, 1 + c = S1_c)
+    double* preM; double* preV;      // exclusive prefixes, same layout
+    int* tie;                        // [4 x nseg]: has_end, head events (up to the first end), tail events (after the last end), event ends
+    int64_t* gidx;                   // [nseg + 1]: first A-row index of each segment; gidx[nseg] = D
+    int* carry;                      // [nseg]: events of the tie group open at the segment's start
+    double* segLL; double* segU;     // [nseg], [p x nseg]
+    double* segHq; double* segHv;    // [nseg] segment totals of d / S0 as (Q, v)
+    double* sufHq; double* sufHv;    // [nseg] their exclusive suffix over the later segments
+    double* A; int64_t lda; double* dA; int64_t g0; int64_t ca; int chunk; int nchunks;
+    double* wv; int64_t vlo; int64_t vstep; int64_t vrows;      // Gram weights of the view rows [vlo + r vstep, r < vrows]
+    double* w_out;                   // [n] per position, nullable
+};
+
+// ---- pass 1 ----------------------------------------------------------------------------------------------------------
+template <int RB, int I>
+__device__ __forceinline__ void bcast_rows(double v, double (&out)[RB]) {
+    if constexpr (I < RB) {
+        out[I] = read_lane_f64<lane_of_row<RB>(I)>(v);
+        bcast_rows<RB, I + 1>(v, out);
+    }
+}
+
+template <int NC, bool VEC>
+__global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
+    constexpr int RB = NC >= 8 ? 1 : COX_RB;        // (wide rows: one row per step keeps the row registers from spilling)
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * COX_WAVES + (threadIdx.x >> 6);
+    if (s >= a.nseg) return;
+    double2 b[NC], s1[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 128 + 2 * lane;
+        b[c].x = col < a.p ? a.beta[col] : 0.0;
+        b[c].y = col + 1 < a.p ? a.beta[col + 1] : 0.0;
+        s1[c].x = 0.0; s1[c].y = 0.0;
+    }
+    double M = -INFINITY, s0 = 0.0;
+    int has_end = 0, head = 0, tail = 0, nend = 0;
+    const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
+    const int myrow = row_of_lane<RB>(lane);
+    for (int64_t q0 = p0; q0 < p1; q0 += RB) {
+        double2 x[RB][NC];
+        double dot[RB];
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const int64_t q = min(q0 + i, p1 - 1);
+            const double* rowp = a.X + a.order[q] * a.ldx;
+            double t = 0.0;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                x[i][c] = cox_ld2(rowp, VEC, c * 128 + 2 * lane, a.p);
+                t = fma(x[i][c].x, b[c].x, fma(x[i][c].y, b[c].y, t));
+            }
+            dot[i] = t;
+        }
+        const double eta = merged_reduce<RB>(dot, lane);
+        if ((lane & rep_mask<RB>()) == 0 && q0 + myrow < p1) a.eta[q0 + myrow] = eta;
+        double e_r[RB];
+        bcast_rows<RB, 0>(eta, e_r);
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const int64_t q = q0 + i;
+            if (q >= p1) break;
+            const double et = e_r[i];
+            if (et > M) {                                       // wave-uniform: rescale the running sums to the new max
+                const double r = M == -INFINITY ? 0.0 : exp_neg(et - M);
+                s0 *= r;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) { s1[c].x *= r; s1[c].y *= r; }
+                M = et;
+            }
+            const double e = exp_neg(M - et);
+            s0 += e;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) { s1[c].x = fma(e, x[i][c].x, s1[c].x); s1[c].y = fma(e, x[i][c].y, s1[c].y); }
+            const int64_t r = a.order[q];
+            const int ev = a.event[r] != 0.0;
+            const bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
+            tail += ev;
+            if (end) {
+                if (!has_end) head = tail;
+                nend += tail > 0;
+                has_end = 1;
+                tail = 0;
+            }
+        }
+    }
+    if (lane == 0) {
+        a.segM[s] = M;
+        a.segV[s] = s0;
+        a.tie[s] = has_end; a.tie[a.ld + s] = head; a.tie[2 * a.ld + s] = tail; a.tie[3 * a.ld + s] = nend;
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 128 + 2 * lane;
+        if (col < a.p) a.segV[(int64_t)(1 + col) * a.ld + s] = s1[c].x;
+        if (col + 1 < a.p) a.segV[(int64_t)(2 + col) * a.ld + s] = s1[c].y;
+    }
+}
+
+// ---- block-wide exclusive scan over the nseg segments, 256 threads each owning a contiguous range --------------------
+// Op: void comb(State& acc, const State& next) (associative, applied left to right); load(s) / store(s, excl).
+template <class State, class Load, class Comb, class Store>
+__device__ void seg_scan(int nseg, State ident, Load load, Comb comb, Store store, State* sh, bool reverse) {
+    const int t = threadIdx.x;
+    const int per = (nseg + COX_THREADS - 1) / COX_THREADS;
+    const int lo = min(nseg, t * per), hi = min(nseg, lo + per);
+    // forward: segments in index order; reverse: walked from the end (suffix scans)
+    auto seg = [&](int i) { return reverse ? nseg - 1 - i : i; };
+    State acc = ident;
+    for (int i = lo; i < hi; ++i) comb(acc, load(seg(i)));
+    sh[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        State run = ident;
+        for (int k = 0; k < COX_THREADS; ++k) { const State v = sh[k]; sh[k] = run; comb(run, v); }
+    }
+    __syncthreads();
+    State run = sh[t];
+    for (int i = lo; i < hi; ++i) { const State v = load(seg(i)); store(seg(i), run); comb(run, v); }
+    __syncthreads();
+}
+
+struct PreS { double M, v; };
+struct TieS { int f, c; };
+
+// ---- pass 2: blocks 0 .. p: prefix of column (S0, S1_c); block p + 1: tie groups and A-row indices ---------------------
+__global__ __launch_bounds__(COX_THREADS) void cox_segscan_kernel(CoxArgs a) {
+    __shared__ PreS shp[COX_THREADS];
+    __shared__ TieS sht[COX_THREADS];
+    __shared__ int64_t shg[COX_THREADS];
+    const int c = blockIdx.x;
+    if (c <= a.p) {
+        const double* V = a.segV + (int64_t)c * a.ld;
+        double* P = a.preV + (int64_t)c * a.ld;
+        seg_scan<PreS>(a.nseg, PreS{-INFINITY, 0.0},
+                       [&](int s) { return PreS{a.segM[s], V[s]}; },
+                       [](PreS& x, const PreS& y) { pre_comb(x.M, x.v, y.M, y.v); },
+                       [&](int s, const PreS& e) { P[s] = e.v; if (c == 0) a.preM[s] = e.M; }, shp, false);
+        return;
+    }
+    // the open tie group entering segment s: (f, c) = (segment has an end, events after its last end / all its events)
+    seg_scan<TieS>(a.nseg, TieS{0, 0},
+                   [&](int s) { return TieS{a.tie[s], a.tie[2 * a.ld + s]}; },
+                   [](TieS& x, const TieS& y) { x.c = y.f ? y.c : x.c + y.c; x.f |= y.f; },
+                   [&](int s, const TieS& e) { a.carry[s] = e.c; }, sht, false);
+    // event groups that END in segment s: its event ends, the first one counted with the events carried in
+    auto count = [&](int s) -> int64_t {
+        if (!a.tie[s]) return 0;
+        const int head = a.tie[a.ld + s], nend = a.tie[3 * a.ld + s];
+        return nend - (head > 0) + (head + a.carry[s] > 0);
+    };
+    seg_scan<int64_t>(a.nseg, (int64_t)0, count, [](int64_t& x, const int64_t& y) { x += y; },
+                      [&](int s, const int64_t& e) { a.gidx[s] = e; }, shg, false);
+    if (threadIdx.x == 0) {
+        int64_t tot = 0;
+        for (int s = 0; s < a.nseg; ++s) tot += count(s);      // (one thread: nseg <= 4096 values already in L2)
+        a.gidx[a.nseg] = tot;
+    }
+}
+
+// ---- pass 3 ------------------------------------------------------------------------------------------------------------
+template <int NC, bool VEC>
+__global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
+    constexpr int RB = NC >= 8 ? 1 : COX_RB;
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * COX_WAVES + (threadIdx.x >> 6);
+    if (s >= a.nseg) return;
+    const int64_t gs = a.gidx[s], ge = a.gidx[s + 1];
+    const int owner = (int)min<int64_t>(gs / a.ca, a.nchunks - 1);       // the chunk that also writes the segment's partials
+    const bool own = owner == a.chunk;
+    if (!own && (ge <= a.g0 || gs >= a.g0 + a.ca)) return;               // no A row of this chunk ends here
+    double M = a.preM[s], s0 = a.preV[s];
+    double2 s1[NC], u[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 128 + 2 * lane;
+        s1[c].x = col < a.p ? a.preV[(int64_t)(1 + col) * a.ld + s] : 0.0;
+        s1[c].y = col + 1 < a.p ? a.preV[(int64_t)(2 + col) * a.ld + s] : 0.0;
+        u[c].x = 0.0; u[c].y = 0.0;
+    }
+    int open = a.carry[s];
+    int64_t g = gs;
+    double ll = 0.0, hq = 0.0, hv = 0.0;
+    const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
+    for (int64_t q0 = p0; q0 < p1; q0 += RB) {
+        double2 x[RB][NC];
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const int64_t q = min(q0 + i, p1 - 1);
+            const double* rowp = a.X + a.order[q] * a.ldx;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) x[i][c] = cox_ld2(rowp, VEC, c * 128 + 2 * lane, a.p);
+        }
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const int64_t q = q0 + i;
+            if (q >= p1) break;
+            const double et = a.eta[q];
+            if (et > M) {
+                const double r = M == -INFINITY ? 0.0 : exp_neg(et - M);
+                s0 *= r;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) { s1[c].x *= r; s1[c].y *= r; }
+                M = et;
+            }
+            const double e = exp_neg(M - et);
+            s0 += e;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) { s1[c].x = fma(e, x[i][c].x, s1[c].x); s1[c].y = fma(e, x[i][c].y, s1[c].y); }
+            const int64_t r = a.order[q];
+            const bool ev = a.event[r] != 0.0;
+            const bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
+            if (ev) {
+                ++open;
+                if (own) {
+                    ll += et;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { u[c].x += x[i][c].x; u[c].y += x[i][c].y; }
+                }
+            }
+            double hzv = 0.0;
+            if (end && open > 0) {
+                const double d = (double)open;
+                const double inv = 1.0 / s0;
+                if (own) {
+                    ll -= d * (M + log(s0));
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { u[c].x = fma(-d * inv, s1[c].x, u[c].x); u[c].y = fma(-d * inv, s1[c].y, u[c].y); }
+                    hzv = d * inv;
+                    suf_comb(hq, hv, M, hzv);      // (walked forward: the segment's total needs no order among its terms but a fixed one)
+                }
+                if (g >= a.g0 && g < a.g0 + a.ca) {
+                    double* Ar = a.A + (g - a.g0) * a.lda;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        const int col = c * 128 + 2 * lane;
+                        if (col < a.p) Ar[col] = s1[c].x * inv;
+                        if (col + 1 < a.p) Ar[col + 1] = s1[c].y * inv;
+                    }
+                    if (lane == 0) a.dA[g - a.g0] = -d;
+                }
+                ++g;
+            }
+            if (end) open = 0;
+            if (own && lane == 0) { a.hzv[q] = hzv; a.hzq[q] = M; }
+        }
+    }
+    if (!own) return;
+    if (lane == 0) { a.segLL[s] = ll; a.segHq[s] = hq; a.segHv[s] = hv; }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 128 + 2 * lane;
+        if (col < a.p) a.segU[(int64_t)col * a.ld + s] = u[c].x;
+        if (col + 1 < a.p) a.segU[(int64_t)(col + 1) * a.ld + s] = u[c].y;
+    }
+}
+
+// ---- pass 4: suffix of d / S0 over segments (block 0) and the column sums of loglik / U (blocks 1 ..) ------------------
+__global__ __launch_bounds__(COX_THREADS) void cox_finish_kernel(CoxArgs a, double* g, double* loglik) {
+    __shared__ PreS shp[COX_THREADS];
+    __shared__ double red[COX_THREADS];
+    if (blockIdx.x == 0) {
+        seg_scan<PreS>(a.nseg, PreS{0.0, 0.0},
+                       [&](int s) { return PreS{a.segHq[s], a.segHv[s]}; },
+                       [](PreS& x, const PreS& y) { suf_comb(x.M, x.v, y.M, y.v); },
+                       [&](int s, const PreS& e) { a.sufHq[s] = e.M; a.sufHv[s] = e.v; }, shp, true);
+        return;
+    }
+    // column c = blockIdx.x - 1 (c == p: loglik): thread t sums segments t, t + 256, ... in order, then a fixed tree
+    const int c = blockIdx.x - 1;
+    const double* src = c < a.p ? a.segU + (int64_t)c * a.ld : a.segLL;
+    double acc = 0.0;
+    for (int s = threadIdx.x; s < a.nseg; s += COX_THREADS) acc += src[s];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int h = COX_THREADS / 2; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (c < a.p) { if (g) g[c] = red[0]; }
+        else if (loglik) *loglik = red[0];
+    }
+}
+
+// ---- pass 5: w per position from the suffix of d / S0: one wave per segment, 64 positions per step, walked backwards ---
+__global__ __launch_bounds__(COX_THREADS) void cox_w_kernel(CoxArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * COX_WAVES + (threadIdx.x >> 6);
+    if (s >= a.nseg) return;
+    double cq = a.sufHq[s], cv = a.sufHv[s];          // everything after the segment
+    const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
+    for (int64_t top = p1; top > p0; top -= 64) {
+        const int64_t q = top - 64 + lane;
+        const bool valid = q >= p0;
+        double hq = valid ? a.hzq[q] : 0.0, hv = valid ? a.hzv[q] : 0.0;
+        // inclusive suffix inside the 64 positions (lane l combines lanes >= l)
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const double oq = __shfl_down(hq, k, 64), ov = __shfl_down(hv, k, 64);
+            if (lane + k < 64) suf_comb(hq, hv, oq, ov);
+        }
+        double tq = hq, tv = hv;
+        suf_comb(tq, tv, cq, cv);
+        if (valid) {
+            const double et = a.eta[q];
+            const double w = tv == 0.0 ? 0.0 : tv * exp_neg(tq - et);
+            if (a.w_out) a.w_out[q] = w;
+            const int64_t rel = a.order[q] - a.vlo;
+            if (rel >= 0 && rel % a.vstep == 0 && rel / a.vstep < a.vrows) a.wv[rel / a.vstep] = w;
+        }
+        cq = __shfl(tq, 0, 64); cv = __shfl(tv, 0, 64);
+    }
+}
+
+// ---- layout of the partition's rows: lo, hi and whether they are exactly lo + j step (strided / contiguous) -------------
+__global__ __launch_bounds__(1024) void cox_layout_kernel(const int64_t* __restrict__ order, int64_t n, int64_t* out) {
+    __shared__ int64_t smn[16], smx[16];
+    __shared__ int bad_sh;
+    int64_t mn = INT64_MAX, mx = -1;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) { mn = min(mn, order[i]); mx = max(mx, order[i]); }
+    for (int m = 32; m >= 1; m >>= 1) { mn = min(mn, (int64_t)__shfl_xor(mn, m, 64)); mx = max(mx, (int64_t)__shfl_xor(mx, m, 64)); }
+    if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
+    if (threadIdx.x == 0) bad_sh = 0;
+    __syncthreads();
+    mn = smn[0]; mx = smx[0];
+    for (int k = 1; k < (int)blockDim.x / 64; ++k) { mn = min(mn, smn[k]); mx = max(mx, smx[k]); }
+    const int64_t step = n > 1 ? (mx - mn) / (n - 1) : 1;
+    // n distinct indices in [mn, mx] that are all mn + j step with mx - mn = (n - 1) step: exactly the progression
+    bool bad = n > 1 && (step < 1 || (mx - mn) != step * (n - 1));
+    for (int64_t i = threadIdx.x; i < n && !bad; i += blockDim.x) bad = (order[i] - mn) % step != 0;
+    if (bad) atomicOr(&bad_sh, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) { out[0] = mn; out[1] = mx; out[2] = bad_sh ? 0 : step; }
+}
+
+__global__ void cox_fill_kernel(double* __restrict__ v, int64_t n, double val) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = val;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+struct CoxLayout {
+    int64_t L, nseg, ca, lda;
+    size_t off_eta, off_hzv, off_hzq, off_segM, off_segV, off_preM, off_preV, off_tie, off_gidx, off_carry, off_segLL, off_segU,
+        off_segH, off_suf, off_A, off_dA, off_wv, off_misc, off_gram, total;
+};
+
+static CoxLayout cox_layout(int64_t max_rows, int p) {
+    CoxLayout l{};
+    const int64_t n = std::max<int64_t>(max_rows, 1);
+    l.L = std::max<int64_t>(64, (n + COX_MAX_SEGS - 1) / COX_MAX_SEGS);
+    l.L = (l.L + COX_RB - 1) / COX_RB * COX_RB;
+    l.nseg = (n + l.L - 1) / l.L;
+    l.lda = (p + 1) / 2 * 2;
+    l.ca = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(COX_A_BYTES / (8 * (size_t)l.lda))));
+    const int64_t S = COX_MAX_SEGS;     // segment arrays sized for the largest count any n gives (the query stays monotone)
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
+    l.off_eta = take(8 * (size_t)n);
+    l.off_hzv = take(8 * (size_t)n);
+    l.off_hzq = take(8 * (size_t)n);
+    l.off_wv = take(8 * (size_t)n);
+    l.off_segM = take(8 * S);
+    l.off_segV = take(8 * S * (size_t)(p + 1));
+    l.off_preM = take(8 * S);
+    l.off_preV = take(8 * S * (size_t)(p + 1));
+    l.off_tie = take(4 * 4 * S);
+    l.off_gidx = take(8 * (S + 1));
+    l.off_carry = take(4 * S);
+    l.off_segLL = take(8 * S);
+    l.off_segU = take(8 * S * (size_t)p);
+    l.off_segH = take(8 * 2 * S);
+    l.off_suf = take(8 * 2 * S);
+    l.off_A = take(8 * (size_t)l.ca * l.lda);
+    l.off_dA = take(8 * (size_t)l.ca);
+    l.off_misc = take(256);
+    l.off_gram = take(gram_workspace_bytes_impl(std::max<int64_t>(n, l.ca), p, 8));
+    l.total = o;
+    return l;
+}
+
+static bool cox_vec_ok(const double* X, int64_t ldx, int p) {
+    return (p % 2 == 0) && (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0);
+}
+
+template <int NC>
+static void launch_rows(bool scan, bool vec, const CoxArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES));
+    if (scan) {
+        if (vec) hipLaunchKernelGGL((cox_scan_kernel<NC, true>), grid, dim3(COX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((cox_scan_kernel<NC, false>), grid, dim3(COX_THREADS), 0, s, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((cox_eta_kernel<NC, true>), grid, dim3(COX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((cox_eta_kernel<NC, false>), grid, dim3(COX_THREADS), 0, s, a);
+    }
+}
+static int launch_row_pass(bool scan, const CoxArgs& a, hipStream_t s) {
+    const bool vec = cox_vec_ok(a.X, a.ldx, a.p);
+    const int nc = (a.p + 127) / 128;
+    if (nc <= 1) launch_rows<1>(scan, vec, a, s);
+    else if (nc <= 2) launch_rows<2>(scan, vec, a, s);
+    else if (nc <= 4) launch_rows<4>(scan, vec, a, s);
+    else if (nc <= 8) launch_rows<8>(scan, vec, a, s);
+    else launch_rows<16>(scan, vec, a, s);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+// Row layout of a partition (once per partition: `order` does not change between iterations): the X-term Gram runs on
+// the view rows vlo + r vstep; a partition that is no such progression is covered by views of n rows one after another.
+struct CoxRows { int64_t lo, hi, step; };
+static int cox_rows(const int64_t* order, int64_t n, int64_t* misc_dev, CoxRows* out, hipStream_t s) {
+    hipLaunchKernelGGL(cox_layout_kernel, dim3(1), dim3(1024), 0, s, order, n, misc_dev);
+    DLSA_HIP_CHECK(hipGetLastError());
+    int64_t h[3];
+    DLSA_HIP_CHECK(hipMemcpyAsync(h, misc_dev, sizeof(h), hipMemcpyDeviceToHost, s));
+    DLSA_HIP_CHECK(hipStreamSynchronize(s));
+    out->lo = h[0]; out->hi = h[1]; out->step = h[2];
+    return DLSA_OK;
+}
+
+// One partition at a fixed beta: H (and g, loglik, w_out) as described at the top.  *D_out: number of event groups.
+static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
+                         int p, const CoxRows& rows, const double* beta, double* H, int64_t ldh, double* g, double* loglik,
+                         double* w_out, char* ws, const CoxLayout& l, int64_t* D_out, hipStream_t s) {
+    CoxArgs a{};
+    a.X = X; a.ldx = ldx; a.time = time; a.event = event; a.order = order; a.n = n; a.p = p; a.beta = beta;
+    a.L = l.L; a.nseg = (int)((n + l.L - 1) / l.L); a.ld = a.nseg;
+    a.eta = (double*)(ws + l.off_eta); a.hzv = (double*)(ws + l.off_hzv); a.hzq = (double*)(ws + l.off_hzq);
+    a.segM = (double*)(ws + l.off_segM); a.segV = (double*)(ws + l.off_segV);
+    a.preM = (double*)(ws + l.off_preM); a.preV = (double*)(ws + l.off_preV);
+    a.tie = (int*)(ws + l.off_tie); a.gidx = (int64_t*)(ws + l.off_gidx); a.carry = (int*)(ws + l.off_carry);
+    a.segLL = (double*)(ws + l.off_segLL); a.segU = (double*)(ws + l.off_segU);
+    a.segHq = (double*)(ws + l.off_segH); a.segHv = a.segHq + COX_MAX_SEGS;
+    a.sufHq = (double*)(ws + l.off_suf); a.sufHv = a.sufHq + COX_MAX_SEGS;
+    a.A = (double*)(ws + l.off_A); a.lda = l.lda; a.dA = (double*)(ws + l.off_dA); a.ca = l.ca;
+    a.wv = (double*)(ws + l.off_wv); a.w_out = w_out;
+    void* gws = ws + l.off_gram;
+    const size_t gws_bytes = l.total - l.off_gram;
+    int rc;
+
+    rc = launch_row_pass(false, a, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cox_segscan_kernel, dim3(p + 2), dim3(COX_THREADS), 0, s, a);
+    DLSA_HIP_CHECK(hipGetLastError());
+    int64_t D = 0;
+    DLSA_HIP_CHECK(hipMemcpyAsync(&D, a.gidx + a.nseg, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    DLSA_HIP_CHECK(hipStreamSynchronize(s));
+    *D_out = D;
+    a.nchunks = (int)std::max<int64_t>(1, (D + l.ca - 1) / l.ca);
+    bool first = true;
+    for (int k = 0; k < a.nchunks; ++k) {
+        a.chunk = k; a.g0 = (int64_t)k * l.ca;
+        rc = launch_row_pass(true, a, s);
+        if (rc) return rc;
+        const int64_t rowsA = std::min<int64_t>(l.ca, D - a.g0);
+        if (rowsA > 0) {
+            rc = gram_impl_f64(a.A, a.lda, a.dA, rowsA, p, H, ldh, first ? 0 : 1, gws, gws_bytes, s);
+            if (rc) return rc;
+            first = false;
+        }
+    }
+    hipLaunchKernelGGL(cox_finish_kernel, dim3(p + 2), dim3(COX_THREADS), 0, s, a, g, loglik);
+    DLSA_HIP_CHECK(hipGetLastError());
+    // w and the X-term Gram over views of the partition's rows
+    const int64_t span = rows.step > 0 ? n : rows.hi - rows.lo + 1;
+    const int64_t vstep = rows.step > 0 ? rows.step : 1;
+    for (int64_t v0 = 0; v0 < span; v0 += n) {
+        a.vlo = rows.lo + v0 * vstep; a.vstep = vstep; a.vrows = std::min<int64_t>(n, span - v0);
+        if (rows.step == 0) {
+            hipLaunchKernelGGL(cox_fill_kernel, dim3((unsigned)((a.vrows + 255) / 256)), dim3(256), 0, s, a.wv, a.vrows, 0.0);
+            DLSA_HIP_CHECK(hipGetLastError());
+        }
+        if (v0 > 0) a.w_out = nullptr;
+        hipLaunchKernelGGL(cox_w_kernel, dim3((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES)), dim3(COX_THREADS), 0, s, a);
+        DLSA_HIP_CHECK(hipGetLastError());
+        rc = gram_impl_f64(X + a.vlo * ldx, ldx * vstep, a.wv, a.vrows, p, H, ldh, first ? 0 : 1, gws, gws_bytes, s);
+        if (rc) return rc;
+        first = false;
+    }
+    return DLSA_OK;
+}
+
+static int cox_check_ws(void* ws, size_t ws_bytes, const CoxLayout& l) {
+    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
+        set_error("cox: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    return DLSA_OK;
+}
+
+}  // namespace dlsa
+
+extern "C" {
+
+size_t dlsa_cox_workspace_bytes(int64_t max_rows, int p) {
+    if (p <= 0 || p > 2048 || max_rows < 0) return 0;
+    // Newton state after the pass scratch: beta, prev, delta, g (p each), stats, the Cholesky factor (p x p)
+    return dlsa::align_up(dlsa::cox_layout(max_rows, p).total, 256) + dlsa::align_up(8 * (size_t)(4 * p + 8), 256) +
+           dlsa::align_up(8 * (size_t)p * p, 256);
+}
+
+int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n, int p,
+                      const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes,
+                      void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && time && event && order && beta && H, "cox_pass: null argument");
+    DLSA_REQUIRE(n >= 1 && p > 0 && p <= 2048 && ldx >= p && ldh >= p, "cox_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
+                 (long long)n, p, (long long)ldx, (long long)ldh);
+    const CoxLayout l = cox_layout(n, p);
+    int rc = cox_check_ws(ws, ws_bytes, l);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    CoxRows rows;
+    rc = cox_rows(order, n, (int64_t*)((char*)ws + l.off_misc), &rows, s);
+    if (rc) return rc;
+    int64_t D = 0;
+    return cox_pass_impl(X, ldx, time, event, order, n, p, rows, beta, H, ldh, g, loglik, w_out, (char*)ws, l, &D, s);
+}
+
+int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
+                     const int64_t* part_offsets_host, int K, int p, double tol, int max_iter, double* coef, double* Sig_inv,
+                     double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws, size_t ws_bytes,
+                     void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && time && event && order && part_offsets_host && coef && Sig_inv && Sig_invMcoef, "cox_fit: null argument");
+    DLSA_REQUIRE(K > 0 && p > 0 && p <= 2048 && ldx >= p, "cox_fit: bad shape K=%d p=%d ldx=%lld", K, p, (long long)ldx);
+    DLSA_REQUIRE(max_iter > 0 && tol > 0, "cox_fit: bad tol/max_iter");
+    int64_t max_rows = 0;
+    for (int k = 0; k < K; ++k) {
+        DLSA_REQUIRE(part_offsets_host[k] >= 0 && part_offsets_host[k + 1] >= part_offsets_host[k], "cox_fit: part_offsets must be non-decreasing from 0");
+        max_rows = std::max(max_rows, part_offsets_host[k + 1] - part_offsets_host[k]);
+    }
+    const CoxLayout l = cox_layout(max_rows, p);
+    const size_t need = dlsa_cox_workspace_bytes(max_rows, p);
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
+        set_error("cox_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* wsc = (char*)ws;
+    double* st = (double*)(wsc + align_up(l.total, 256));
+    double* stats = st;                 // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] loglik
+    double* beta = st + 8;
+    double* prev = beta + p;
+    double* delta = prev + p;
+    double* g = delta + p;
+    double* Lf = (double*)(wsc + align_up(l.total, 256) + align_up(8 * (size_t)(4 * p + 8), 256));
+    int overall = DLSA_OK;
+    for (int k = 0; k < K; ++k) {
+        const int64_t nk = part_offsets_host[k + 1] - part_offsets_host[k];
+        const int64_t* ok = order + part_offsets_host[k];
+        double* Hk = Sig_inv + (size_t)k * p * p;
+        double* ck = coef + (size_t)k * p;
+        double* sk = Sig_invMcoef + (size_t)k * p;
+        int st_k = DLSA_PART_EMPTY, iters = 0;
+        double ll = 0.0;
+        if (nk > 0) {
+            CoxRows rows;
+            int rc = cox_rows(ok, nk, (int64_t*)(wsc + l.off_misc), &rows, s);
+            if (rc) return rc;
+            DLSA_HIP_CHECK(hipMemsetAsync(beta, 0, (size_t)p * sizeof(double), s));
+            double ll_prev = -INFINITY;
+            bool have_prev = false, done = false;
+            int halvings = 0;
+            st_k = DLSA_PART_NOT_CONVERGED;
+            for (int it = 0; it < max_iter + 1 && !done; ++it) {
+                int64_t D = 0;
+                rc = cox_pass_impl(X, ldx, time, event, ok, nk, p, rows, beta, Hk, p, g, stats + 3, nullptr, wsc, l, &D, s);
+                if (rc) return rc;
+                if (D == 0) { st_k = DLSA_PART_EMPTY; break; }
+                rc = launch_chol_solve(Hk, p, 0, g, 0, beta, 0, p, 1, Lf, delta, 0, stats, 0, s, 0);
+                if (rc) return rc;
+                double h[4];
+                DLSA_HIP_CHECK(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, s));
+                DLSA_HIP_CHECK(hipStreamSynchronize(s));
+                ll = h[3];
+                if (!isfinite(ll)) { st_k = DLSA_PART_NAN; break; }
+                // the previous step overshot (the partial likelihood dropped): halve it
+                if (have_prev && ll < ll_prev - 1e-12 * fabs(ll_prev) && halvings < 30) {
+                    ++halvings;
+                    rc = launch_axpby(beta, prev, -1.0, p, delta, s);     // delta = beta - prev
+                    if (rc) return rc;
+                    rc = launch_axpby(prev, delta, 0.5, p, beta, s);      // beta = prev + delta / 2
+                    if (rc) return rc;
+                    continue;
+                }
+                halvings = 0;
+                if (h[2] == 1.0) { st_k = DLSA_PART_NOT_SPD; break; }
+                if (h[2] == 2.0) { st_k = DLSA_PART_NAN; break; }
+                iters = it + 1;
+                if (h[0] <= tol * std::max(1.0, h[1])) { st_k = DLSA_PART_OK; done = true; break; }     // H, g, loglik are at beta
+                if (it == max_iter) break;          // (the extra pass evaluated H at the last iterate)
+                rc = launch_advance(prev, beta, delta, p, s);
+                if (rc) return rc;
+                ll_prev = ll;
+                have_prev = true;
+            }
+        }
+        if (st_k == DLSA_PART_EMPTY) {
+            ll = 0.0;
+            DLSA_HIP_CHECK(hipMemsetAsync(Hk, 0, (size_t)p * p * sizeof(double), s));
+            DLSA_HIP_CHECK(hipMemsetAsync(ck, 0, (size_t)p * sizeof(double), s));
+            DLSA_HIP_CHECK(hipMemsetAsync(sk, 0, (size_t)p * sizeof(double), s));
+        } else {
+            DLSA_HIP_CHECK(hipMemcpyAsync(ck, beta, (size_t)p * sizeof(double), hipMemcpyDeviceToDevice, s));
+            const int rc = launch_matvec(Hk, p, beta, p, sk, s);
+            if (rc) return rc;
+        }
+        if (n_iter_host) n_iter_host[k] = iters;
+        if (status_host) status_host[k] = st_k;
+        if (loglik_host) loglik_host[k] = ll;
+        if (st_k == DLSA_PART_NOT_CONVERGED && overall == DLSA_OK) overall = DLSA_ERR_NOT_CONVERGED;
+        if (st_k == DLSA_PART_NOT_SPD && overall == DLSA_OK) overall = DLSA_ERR_NOT_SPD;
+        if (st_k == DLSA_PART_NAN && overall == DLSA_OK) overall = DLSA_ERR_NAN;
+    }
+    DLSA_HIP_CHECK(hipStreamSynchronize(s));
+    return overall;
+}
+
+}  // extern "C"

@@ -672,6 +672,60 @@ def irls_fit(X, y, part_offsets, tol=1e-13, max_iter=100):
             "status": list(status), "loglik": list(ll), "rc": rc}
 
 
+def _cox_args(X, time, event, order):
+    _require_gpu(X, time, event, order)
+    _f64(X, "X"); _f64(time, "time"); _f64(event, "event"); _f64(order, "order", torch.int64)
+    n = X.shape[0]
+    if time.numel() != n or event.numel() != n:
+        raise ValueError("cox: time and event must have n = %d elements" % n)
+    return X.shape[1]
+
+
+def cox_pass(X, time, event, order, beta, want_w=False):
+    """One Cox partition at a fixed beta (dlsa_cox_pass_f64): `order` [m] int64 holds the partition's absolute row indices
+    in DESCENDING time.  Returns (H [p,p] observed information, g [p] score, loglik [1] log partial likelihood,
+    w [m] or None -- the Breslow weights of the rows order[i])."""
+    lib = _lib.load()
+    p = _cox_args(X, time, event, order)
+    _f64(beta, "beta")
+    m = order.numel()
+    if m < 1 or beta.numel() != p:
+        raise ValueError("cox_pass: need at least one row and beta with p = %d entries" % p)
+    dev = X.device
+    H = torch.empty((p, p), dtype=torch.float64, device=dev)
+    g = torch.empty((p,), dtype=torch.float64, device=dev)
+    ll = torch.empty((1,), dtype=torch.float64, device=dev)
+    w = torch.empty((m,), dtype=torch.float64, device=dev) if want_w else None
+    ws = _workspace(lib.dlsa_cox_workspace_bytes(m, p), dev)
+    check(lib.dlsa_cox_pass_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), m, p, _ptr(beta), _ptr(H), p,
+                                _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, w
+
+
+def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100):
+    """Per-partition Cox fit (dlsa_cox_fit_f64): partition k = rows order[off[k]:off[k+1]] (each segment in descending
+    time).  Same result dict as irls_fit; `loglik` holds the log partial likelihood at coef."""
+    lib = _lib.load()
+    p = _cox_args(X, time, event, order)
+    offs = [int(v) for v in part_offsets]
+    K = len(offs) - 1
+    if K < 1 or offs[0] != 0 or offs[-1] > order.numel() or any(offs[k + 1] < offs[k] for k in range(K)):
+        raise ValueError("cox_fit: part_offsets must be K+1 non-decreasing ints from 0 within the order")
+    dev = X.device
+    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
+    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
+    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
+    ws = _workspace(lib.dlsa_cox_workspace_bytes(max(offs[k + 1] - offs[k] for k in range(K)), p), dev)
+    c_offs = (ctypes.c_int64 * (K + 1))(*offs)
+    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
+    rc = lib.dlsa_cox_fit_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), c_offs, K, p, tol, max_iter,
+                              _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
+    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
+        check(rc)
+    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
+            "loglik": list(ll), "rc": rc}
+
+
 def sum_blocks(coef, smc, sig, mask=None):
     """[sum Sig_inv | sum Sig_invMcoef | sum coef]: the rank's all-reduce message (dlsa.py:30-34)."""
     lib = _lib.load()

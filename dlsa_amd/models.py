@@ -481,3 +481,104 @@ def linear_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_fa
     if out.isna().values.any():
         warnings.warn("NAs appear in the final output")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Cox proportional-hazards map step (Breslow ties): the third model family the DLSA method names.  The local objective of
+# partition k is its own partial likelihood with risk sets inside the partition (a Cox model stratified by partition with a
+# common beta); the block is coef = the partition's MLE, Sig_inv = the observed information there, Sig_invMcoef = Sig_inv coef,
+# so dlsa_mapred / dlsa apply unchanged.  No intercept (the partial likelihood does not identify one).
+# ---------------------------------------------------------------------------------------------
+def simulate_cox(sample_size, p, partition_num, seed=20260101, censor_rate=0.3, tie_levels=None):
+    """Seeded survival rows: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), hazard exp(x beta*) with beta* as
+    in simulate_logistic (first int(0.4p) coefficients 1), event times T = E / exp(x beta*) with E ~ Exp(1), censoring times
+    C ~ Exp(rate) with the rate that censors about `censor_rate` of the rows; time = min(T, C), event = T <= C.  tie_levels
+    rounds the times onto that many quantile levels (heavy ties).  partition_id = i % partition_num.
+    Returns the frame partition_id, time, event, x0 .. x{p-1}."""
+    n, p = int(sample_size), int(p)
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    X = X.cpu().numpy()
+    beta = np.zeros(p)
+    beta[:int(0.4 * p)] = 1.0
+    rng = np.random.default_rng(seed)
+    T = rng.exponential(1.0, n) / np.exp(X @ beta)
+    if censor_rate > 0:
+        # E[P(C < T)] = rate / (rate + h) for a hazard h; one scalar rate from the median hazard is close enough for a simulator
+        h = float(np.median(np.exp(X @ beta))) if n else 1.0
+        rate = h * censor_rate / max(1e-12, 1.0 - censor_rate)
+        C = rng.exponential(1.0 / rate, n)
+    else:
+        C = np.full(n, np.inf)
+    time = np.minimum(T, C)
+    event = (T <= C).astype(np.float64)
+    if tie_levels:
+        q = np.quantile(time, np.linspace(0, 1, int(tie_levels) + 1)[1:])
+        time = q[np.minimum(np.searchsorted(q, time), len(q) - 1)]
+    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    data = np.concatenate((pid[:, None], time[:, None], event[:, None], X), 1)
+    return pd.DataFrame(data, columns=["partition_id", "time", "event"] + ["x" + str(i) for i in range(p)])
+
+
+def cox_order(time, part_id):
+    """The row permutation the Cox kernels read: one stable device sort keyed on (partition, -time).  Returns (order int64,
+    rows per partition).  part_id: int64 tensor of partition indices 0 .. K-1."""
+    # stable sort by -time first, then a stable sort by partition keeps the time order inside every partition
+    o1 = torch.sort(-time, stable=True).indices
+    o2 = torch.sort(part_id[o1], stable=True).indices
+    return o1[o2].contiguous()
+
+
+def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, names=None, tol=1e-13, max_iter=100):
+    """Cox map step for the partitions of one device-resident shard: X [n, p] fp64 row-major, time [n], event [n] (nonzero =
+    event) on the GPU.  Partitions as fit_logistic_partitions: `part_offsets` (K+1 ints, contiguous row ranges) or
+    `partition_num` (partition_id = i % K).  The rows are read through a permutation (one stable device sort keyed on
+    (partition, -time)); nothing is copied.  Returns MappedBlocks with `loglik` = log partial likelihood per partition."""
+    if not X.is_cuda:
+        raise RuntimeError("fit_cox_partitions runs on the GPU only (no CPU fallback)")
+    if X.dtype != torch.float64:
+        raise TypeError("fit_cox_partitions: X must be float64, got %s" % X.dtype)
+    X = engine.row_major(X)
+    n, p = X.shape
+    time = time.to(torch.float64).contiguous()
+    event = event.to(torch.float64).contiguous()
+    if part_offsets is None:
+        K = int(partition_num) if partition_num else 1
+        pid = torch.arange(n, device=X.device, dtype=torch.int64) % K
+    else:
+        offs = [int(v) for v in part_offsets]
+        K = len(offs) - 1
+        if offs[0] != 0 or offs[-1] != n:
+            raise ValueError("fit_cox_partitions: part_offsets must run from 0 to n = %d" % n)
+        pid = torch.repeat_interleave(torch.arange(K, device=X.device, dtype=torch.int64),
+                                      torch.tensor([offs[k + 1] - offs[k] for k in range(K)], device=X.device))
+    order = cox_order(time, pid)
+    counts = torch.bincount(pid, minlength=K).cpu().tolist()
+    offs = [0]
+    for c in counts:
+        offs.append(offs[-1] + int(c))
+    if names is None:
+        names = ["x" + str(i) for i in range(p)]
+    r = engine.cox_fit(X, time, event, order, offs, tol=tol, max_iter=max_iter)
+    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
+
+
+def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_baseline=[], data_info=[]):
+    """Frame-level sibling of logistic_model / linear_model for survival data: one partition (a pandas frame) with a time
+    and an event column.  Returns the p x (3+p) frame `par_id, coef, Sig_invMcoef, <features>`; a chunk that lacks an
+    expected dummy level returns the all-zero block with a warning, as logistic_model does."""
+    features_df = sample_df.drop(columns=[event_name])
+    Xd, names = _device_design(features_df, time_name, False, dummy_info, dummy_factors_baseline, data_info)
+    if Xd is None:
+        return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+    td = torch.from_numpy(np.ascontiguousarray(sample_df[time_name].to_numpy(dtype=np.float64))).cuda()
+    ed = torch.from_numpy(np.ascontiguousarray(sample_df[event_name].to_numpy(dtype=np.float64))).cuda()
+    mb = fit_cox_partitions(Xd, td, ed, names=names)
+    st = mb.status[0]
+    if st == 1:
+        warnings.warn("cox_model: Newton iterations did not converge (max_iter reached: monotone likelihood?)")
+    elif st == 2:
+        warnings.warn("cox_model: information matrix not positive definite (collinear design)")
+    out = mb.block_frame(0)
+    if out.isna().values.any():
+        warnings.warn("NAs appear in the final output")
+    return out

@@ -252,6 +252,24 @@ int dlsa_irls_fit_ex_f64(const double* X, int64_t ldx, const double* y, const in
                          double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                          double* loglik_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Cox proportional-hazards map step (Breslow ties; the third model family of the DLSA method) ---------------------
+ * One partition's objective is its own partial likelihood with risk sets inside the partition.  `order` (device, int64)
+ * holds the partition's n absolute row indices of X / time / event in DESCENDING time; rows tied in time are detected by
+ * comparing time at neighbouring positions.  event: 1.0 = event, 0.0 = censored.  No sorted copy of the rows is made.
+ * dlsa_cox_pass_f64 at a fixed beta: H = observed information X'diag(w)X - A'diag(d)A (p x p, ldh >= p, both triangles),
+ * g = score (p, nullable), loglik = log partial likelihood (1, nullable), w_out (n, nullable: w of the row order[i]).
+ * dlsa_cox_fit_f64: partition k = order[part_offsets[k] .. part_offsets[k+1]); Newton from beta = 0, step halving while
+ * the likelihood drops, stop as dlsa_irls_fit_f64.  Outputs as dlsa_irls_fit_f64 (Sig_inv = H at coef); a partition
+ * without rows or events is DLSA_PART_EMPTY with the all-zero block.  Workspace: dlsa_cox_workspace_bytes(max rows, p). */
+size_t dlsa_cox_workspace_bytes(int64_t max_rows, int p);
+int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n, int p,
+                      const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                      void* ws, size_t ws_bytes, void* stream);
+int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
+                     const int64_t* part_offsets_host, int K, int p, double tol, int max_iter,
+                     double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                     double* loglik_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a9: local sum of partition blocks before the one-round all-reduce (dlsa.py:30-34) -
  * out = [ sum_k Sig_inv (p*p) | sum_k Sig_invMcoef (p) | sum_k coef (p) ] contiguous,
  * the message a rank contributes to the RCCL all-reduce.  Blocks whose status is not OK may
