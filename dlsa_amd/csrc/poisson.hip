@@ -1,0 +1,555 @@
+// Poisson regression map step (log link, optional offsets / exposure): one partition's log-likelihood, score and Fisher
+// information at a fixed beta, and the per-partition Newton fit on top of it.  The block a partition returns (coef,
+// Sig_inv = the information at coef, Sig_inv coef) feeds the unchanged one-round combine.
+//
+// Algebra (one partition; the design is [1 | X] with the implicit intercept, X otherwise; o = offset, 0 when absent):
+//   eta = [1 | x]' beta + o,  mu = exp(eta),
+//   loglik = sum y eta - mu - lgamma(y + 1),  g = X'(y - mu),  H = X' diag(mu) X.
+//
+// Launches per evaluation (every partial combines in a fixed order: no float atomics, no waits between workgroups):
+//   1 poisson_kernel        one read of the rows in the logit pass's layout (rowdot.h: RB rows per wave, one merged butterfly
+//                           for their dot products, non-temporal 16-byte loads): mu (-> w), per-block partials of g,
+//                           sum (y - mu), sum (y eta - mu) and, with the intercept and H wanted, of X'mu and sum mu (the
+//                           Hessian's border, so no extra pass);
+//   2 logit_finish_launch   the fixed-order column sums of those partials (the finish step of logit.hip, shared);
+//   3 the Gram              dlsa_gram_f64's dispatch on (X, mu) into the p x p block (gram_icpt_impl with the border).
+// The constant sum lgamma(y + 1) is a small reduction of its own, once per partition (poisson_const_kernel), which also
+// counts the rows with a negative or non-finite count or offset and sums y and e^o for the intercept's start value.
+#include "common.h"
+#include <math.h>
+#include <algorithm>
+
+typedef double dlsa_pois_d2v __attribute__((ext_vector_type(2)));
+
+namespace dlsa {
+
+#include "rowdot.h"       // merged_reduce, row_of_lane, rep_mask, rank1_update
+
+int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
+                  int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t gram_workspace_bytes_impl(int64_t n, int p, int elem_bytes);
+int gram_icpt_impl(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
+                   void* ws, size_t ws_bytes, hipStream_t s, const double* border);
+void logit_finish_launch(const double* gpart, const double* llpart, int nblocks, int pitch, int p, double* g,
+                         double* loglik, hipStream_t stream, const double* s0part, double* s0);
+int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
+                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
+                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);
+int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s);
+int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
+int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
+
+constexpr int POIS_THREADS = 256;
+constexpr int POIS_WAVES = POIS_THREADS / 64;
+constexpr int POIS_MAX_BLOCKS = 2048;
+constexpr int POIS_CONST_BLOCKS = 512;
+
+// exp(a) over the whole signed range in ~20 instructions (CDNA has no fp64 exp): k = rint(a log2 e), r = a - k ln2 with a
+// two-part ln2 (|r| <= 0.347), the degree-13 Taylor polynomial of exp_neg (logistic.h), ldexp.  <= 2 ulp over the normal
+// range.  a below -746 gives 0 (exp(-745.13) is the smallest subnormal), a above 709.78 gives +inf (2^k overflows), NaN
+// stays NaN (the clamps are comparisons, not fmin / fmax).
+__device__ __forceinline__ double exp_full(double a) {
+    a = a < -746.0 ? -746.0 : (a > 710.0 ? 710.0 : a);
+    const double kf = rint(a * 1.4426950408889634);
+    double r = fma(kf, -6.93147180369123816490e-01, a);
+    r = fma(kf, -1.90821492927058770002e-10, r);
+    double q = 1.6059043836821613e-10;                      // 1/13!
+    q = fma(q, r, 2.08767569878681e-09);
+    q = fma(q, r, 2.505210838544172e-08);
+    q = fma(q, r, 2.755731922398589e-07);
+    q = fma(q, r, 2.7557319223985893e-06);
+    q = fma(q, r, 2.48015873015873e-05);
+    q = fma(q, r, 1.984126984126984e-04);
+    q = fma(q, r, 1.388888888888889e-03);
+    q = fma(q, r, 8.333333333333333e-03);
+    q = fma(q, r, 4.1666666666666664e-02);
+    q = fma(q, r, 1.6666666666666666e-01);
+    q = fma(q, r, 0.5);
+    q = fma(q, r, 1.0);
+    q = fma(q, r, 1.0);
+    return ldexp(q, (int)kf);
+}
+
+struct PoissonArgs {
+    const double* X;
+    const double* y;
+    const double* off;     // nullable (OFF = false)
+    const double* beta;    // the p coefficients of X's columns
+    const double* beta0;   // the intercept's coefficient (nullable: no intercept)
+    double* w_out;         // mu per row (nullable)
+    double* gpart;         // [nblocks][NC*128]
+    double* llpart;        // [nblocks]: sum y eta - mu
+    double* s0part;        // [nblocks]: sum y - mu (the intercept's entry of g)
+    double* hpart;         // BORDER: [nblocks][NC*128] X'mu
+    double* swpart;        // BORDER: [nblocks] sum mu
+    int64_t ldx;
+    int64_t n;
+    int p;
+};
+
+static __device__ __forceinline__ double2 pois_ld2(const double* ptr) {
+    const dlsa_pois_d2v t = __builtin_nontemporal_load(reinterpret_cast<const dlsa_pois_d2v*>(ptr));
+    double2 r; r.x = t.x; r.y = t.y; return r;
+}
+
+// The logit pass's skeleton (logit.hip logit_kernel) with the Poisson terms: branch-free clamped loads, the lane's own row's
+// count and offset travel with the batch, a second register set prefetches the next batch at NC = 1.
+template <int NC, int RB, bool VEC, bool OFF, bool BORDER>
+__global__ __launch_bounds__(POIS_THREADS) void poisson_kernel(PoissonArgs a) {
+    __shared__ double red[NC * 128 + 2];
+    __shared__ double redh[BORDER ? NC * 128 + 1 : 1];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const double b0 = a.beta0 ? *a.beta0 : 0.0;
+    double s0 = 0.0, sw = 0.0, ll = 0.0;
+    double2 b[NC], g[NC], h[BORDER ? NC : 1];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 128 + 2 * lane;
+        b[c].x = col < a.p ? a.beta[col] : 0.0;
+        b[c].y = col + 1 < a.p ? a.beta[col + 1] : 0.0;
+        g[c].x = 0.0; g[c].y = 0.0;
+        if constexpr (BORDER) { h[c].x = 0.0; h[c].y = 0.0; }
+    }
+    const int myrow = row_of_lane<RB>(lane);
+    const bool rep = (lane & rep_mask<RB>()) == 0;
+    const int64_t nbatch = (a.n + RB - 1) / RB;
+    const int64_t stride = (int64_t)gridDim.x * POIS_WAVES;
+
+    auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], double& yv, double& ov) {
+        const int64_t row0 = bt * RB;
+        const int64_t ry = min(row0 + myrow, a.n - 1);
+        const double ytmp = a.y[ry];
+        const double otmp = OFF ? a.off[ry] : 0.0;
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const int64_t r = min(row0 + i, a.n - 1);
+            const double* rowp = a.X + r * a.ldx;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int col = c * 128 + 2 * lane;
+                const int c0 = col < a.p ? col : 0;                   // clamped columns meet beta = 0
+                if (VEC) {                                            // VEC implies p even: a pair never straddles p
+                    x[i][c] = pois_ld2(rowp + c0);
+                } else {
+                    x[i][c].x = __builtin_nontemporal_load(rowp + c0);
+                    x[i][c].y = __builtin_nontemporal_load(rowp + (col + 1 < a.p ? col + 1 : 0));
+                }
+            }
+        }
+        yv = ytmp;
+        ov = otmp;
+    };
+    auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const double yraw, const double oraw) {
+        const int64_t row0 = bt * RB;
+        double dot[RB];
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) s = fma(x[i][c].x, b[c].x, fma(x[i][c].y, b[c].y, s));
+            dot[i] = s;
+        }
+        const int64_t r = row0 + myrow;
+        const bool valid = r < a.n;
+        const double yv = valid ? yraw : 0.0;
+        const double eta = merged_reduce<RB>(dot, lane) + b0 + (OFF ? oraw : 0.0);
+        const double mu = exp_full(eta);
+        const double resid = valid ? (yv - mu) : 0.0;
+        if (valid && rep) {
+            if (a.w_out) a.w_out[r] = mu;
+            ll += yv * eta - mu;
+            s0 += resid;
+        }
+        rank1_update<RB, NC, 0>(resid, x, g);
+        if constexpr (BORDER) {                 // X'mu and sum mu of the same rows (a clamped row past n weighs nothing)
+            const double wv = valid ? mu : 0.0;
+            if (rep) sw += wv;
+            rank1_update<RB, NC, 0>(wv, x, h);
+        }
+    };
+
+    int64_t bt = (int64_t)blockIdx.x * POIS_WAVES + wave;
+    if constexpr (NC == 1) {
+        double2 xa[RB][NC], xb[RB][NC];
+        double ya = 0.0, yb = 0.0, oa = 0.0, ob = 0.0;
+        if (a.n > 0) {
+            load_batch(bt, xa, ya, oa);
+            for (; bt < nbatch; bt += 2 * stride) {
+                const int64_t b1 = bt + stride, b2 = bt + 2 * stride;
+                load_batch(b1, xb, yb, ob);
+                process(bt, xa, ya, oa);
+                load_batch(b2, xa, ya, oa);
+                if (b1 < nbatch) process(b1, xb, yb, ob);
+            }
+        }
+    } else {
+        for (; bt < nbatch; bt += stride) {
+            double2 x[RB][NC];
+            double yv, ov;
+            load_batch(bt, x, yv, ov);
+            process(bt, x, yv, ov);
+        }
+    }
+
+    // block reduction: waves add into LDS one after another (fixed order)
+    ll = wave_allreduce_sum(ll);
+    s0 = wave_allreduce_sum(s0);
+    if constexpr (BORDER) sw = wave_allreduce_sum(sw);
+    for (int wv = 0; wv < POIS_WAVES; ++wv) {
+        if (wave == wv) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                double* dst = red + c * 128 + 2 * lane;
+                if (wv == 0) { dst[0] = g[c].x; dst[1] = g[c].y; }
+                else { dst[0] += g[c].x; dst[1] += g[c].y; }
+                if constexpr (BORDER) {
+                    double* dh = redh + c * 128 + 2 * lane;
+                    if (wv == 0) { dh[0] = h[c].x; dh[1] = h[c].y; }
+                    else { dh[0] += h[c].x; dh[1] += h[c].y; }
+                }
+            }
+            if (lane == 0) {
+                if (wv == 0) { red[NC * 128] = ll; red[NC * 128 + 1] = s0; }
+                else { red[NC * 128] += ll; red[NC * 128 + 1] += s0; }
+                if constexpr (BORDER) { if (wv == 0) redh[NC * 128] = sw; else redh[NC * 128] += sw; }
+            }
+        }
+        __syncthreads();
+    }
+    double* gp = a.gpart + (int64_t)blockIdx.x * (NC * 128);
+    for (int col = tid; col < NC * 128; col += POIS_THREADS) gp[col] = red[col];
+    if (tid == 0) { a.llpart[blockIdx.x] = red[NC * 128]; a.s0part[blockIdx.x] = red[NC * 128 + 1]; }
+    if constexpr (BORDER) {
+        double* hp = a.hpart + (int64_t)blockIdx.x * (NC * 128);
+        for (int col = tid; col < NC * 128; col += POIS_THREADS) hp[col] = redh[col];
+        if (tid == 0) a.swpart[blockIdx.x] = redh[NC * 128];
+    }
+}
+
+// ---- once per partition: [sum lgamma(y + 1), sum y, sum e^o, rows with y < 0 or a non-finite y / o] --------------------
+__global__ __launch_bounds__(256) void poisson_const_kernel(const double* __restrict__ y, const double* __restrict__ off,
+                                                            int64_t n, double* __restrict__ part) {
+    __shared__ double red[4][4];
+    double lg = 0.0, sy = 0.0, se = 0.0, bad = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double yv = y[i], ov = off ? off[i] : 0.0;
+        if (yv >= 0.0 && isfinite(yv) && isfinite(ov)) {      // (NaN fails yv >= 0)
+            lg += lgamma(yv + 1.0);
+            sy += yv;
+            se += exp_full(ov);
+        } else {
+            bad += 1.0;
+        }
+    }
+    lg = wave_allreduce_sum(lg); sy = wave_allreduce_sum(sy); se = wave_allreduce_sum(se); bad = wave_allreduce_sum(bad);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wave][0] = lg; red[wave][1] = sy; red[wave][2] = se; red[wave][3] = bad; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double t = red[0][threadIdx.x];
+        for (int k = 1; k < 4; ++k) t += red[k][threadIdx.x];
+        part[(int64_t)blockIdx.x * 4 + threadIdx.x] = t;
+    }
+}
+
+// one wave per quantity, the block partials in a fixed order
+__global__ __launch_bounds__(256) void poisson_const_finish_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
+    const int j = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double s = 0.0;
+    for (int b = lane; b < nblocks; b += 64) s += part[(int64_t)b * 4 + j];
+    s = wave_allreduce_sum(s);
+    if (lane == 0) out[j] = s;
+}
+
+// the pass entry's full log-likelihood: the kernel's sum of y eta - mu minus the constant (NaN when a row is not a valid count)
+__global__ void poisson_ll_fix_kernel(double* __restrict__ ll, const double* __restrict__ cst) {
+    if (threadIdx.x == 0) ll[0] = cst[3] > 0.0 ? NAN : ll[0] - cst[0];
+}
+
+// out[j] = v[first + j * step]
+__global__ void poisson_gather_kernel(const double* __restrict__ v, int64_t first, int64_t step, int64_t n, double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = v[first + j * step];
+}
+
+// Newton start: beta = 0, the intercept (entry 0) at b0
+__global__ void poisson_start_kernel(double* __restrict__ beta, int pe, int intercept, double b0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < pe) beta[i] = (intercept && i == 0) ? b0 : 0.0;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+static int pois_nc(int p) {
+    const int chunks = (p + 127) / 128;
+    int nc = 1;
+    while (nc < chunks) nc *= 2;
+    return nc;
+}
+
+static int pois_rb(int nc) { return nc <= 2 ? 8 : nc == 4 ? 4 : nc == 8 ? 2 : 1; }
+
+static int pois_blocks(int64_t n, int rb) {
+    const int64_t nbatch = (n + rb - 1) / rb;
+    int64_t blocks = (nbatch + POIS_WAVES * 4 - 1) / (POIS_WAVES * 4);   // >= 4 batches per wave
+    return (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), POIS_MAX_BLOCKS);
+}
+
+struct PoisLayout {
+    size_t off_gpart, off_llpart, off_s0part, off_hpart, off_swpart, off_border, off_cpart, off_cst, off_w, off_y, off_o, off_gram,
+        total;
+};
+
+// pass scratch; row_step > 1: room for the gathered counts and offsets of a strided partition
+static PoisLayout pois_layout(int64_t max_rows, int p, int64_t row_step) {
+    PoisLayout l{};
+    const int64_t n = std::max<int64_t>(max_rows, 1);
+    const size_t gp = (size_t)POIS_MAX_BLOCKS * pois_nc(p) * 128 * sizeof(double);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
+    l.off_gpart = take(gp);
+    l.off_llpart = take(8 * (size_t)POIS_MAX_BLOCKS);
+    l.off_s0part = take(8 * (size_t)POIS_MAX_BLOCKS);
+    l.off_hpart = take(gp);
+    l.off_swpart = take(8 * (size_t)POIS_MAX_BLOCKS);
+    l.off_border = take(8 * (size_t)(p + 1));
+    l.off_cpart = take(8 * 4 * (size_t)POIS_CONST_BLOCKS);
+    l.off_cst = take(8 * 4);
+    l.off_w = take(8 * (size_t)n);
+    l.off_y = take(row_step > 1 ? 8 * (size_t)n : 0);
+    l.off_o = take(row_step > 1 ? 8 * (size_t)n : 0);
+    l.off_gram = take(gram_workspace_bytes_impl(n, p, 8));
+    l.total = o;
+    return l;
+}
+
+static int pois_const(const double* y, const double* off, int64_t n, char* ws, const PoisLayout& l, hipStream_t s) {
+    const int blocks = (int)std::min<int64_t>(POIS_CONST_BLOCKS, std::max<int64_t>(1, (n + 255) / 256));
+    double* part = (double*)(ws + l.off_cpart);
+    hipLaunchKernelGGL(poisson_const_kernel, dim3(blocks), dim3(256), 0, s, y, off, n, part);
+    hipLaunchKernelGGL(poisson_const_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)part, blocks, (double*)(ws + l.off_cst));
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+template <int NC, int RB, bool VEC, bool OFF>
+static void launch_pois_b(const PoissonArgs& a, bool border, int blocks, hipStream_t s) {
+    if (border) hipLaunchKernelGGL((poisson_kernel<NC, RB, VEC, OFF, true>), dim3(blocks), dim3(POIS_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((poisson_kernel<NC, RB, VEC, OFF, false>), dim3(blocks), dim3(POIS_THREADS), 0, s, a);
+}
+template <int NC, int RB>
+static void launch_pois(const PoissonArgs& a, bool vec, bool border, int blocks, hipStream_t s) {
+    if (vec) {
+        if (a.off) launch_pois_b<NC, RB, true, true>(a, border, blocks, s);
+        else launch_pois_b<NC, RB, true, false>(a, border, blocks, s);
+    } else {
+        if (a.off) launch_pois_b<NC, RB, false, true>(a, border, blocks, s);
+        else launch_pois_b<NC, RB, false, false>(a, border, blocks, s);
+    }
+}
+
+// One partition at a fixed beta (pe = p + intercept entries, intercept first).  H (nullable) needs w (mu per row: the
+// Gram's weights); g, loglik (the sum of y eta - mu, without the constant), w nullable otherwise.
+static int pois_pass_impl(const double* X, int64_t ldx, const double* y, const double* off, const double* beta, int64_t n, int p,
+                          int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w, char* ws, const PoisLayout& l,
+                          hipStream_t s) {
+    const int nc = pois_nc(p), rb = pois_rb(nc);
+    const bool border = H && intercept;
+    PoissonArgs a{};
+    a.X = X; a.y = y; a.off = off; a.beta = intercept ? beta + 1 : beta; a.beta0 = intercept ? beta : nullptr;
+    a.w_out = w; a.ldx = ldx; a.n = n; a.p = p;
+    a.gpart = (double*)(ws + l.off_gpart); a.llpart = (double*)(ws + l.off_llpart); a.s0part = (double*)(ws + l.off_s0part);
+    a.hpart = (double*)(ws + l.off_hpart); a.swpart = (double*)(ws + l.off_swpart);
+    const bool vec = (ldx % 2 == 0) && (p % 2 == 0) && (((uintptr_t)X & 15) == 0);
+    const int blocks = pois_blocks(n, rb);
+    switch (nc) {
+        case 1: launch_pois<1, 8>(a, vec, border, blocks, s); break;
+        case 2: launch_pois<2, 8>(a, vec, border, blocks, s); break;
+        case 4: launch_pois<4, 4>(a, vec, border, blocks, s); break;
+        case 8: launch_pois<8, 2>(a, vec, border, blocks, s); break;
+        default: launch_pois<16, 1>(a, vec, border, blocks, s); break;
+    }
+    DLSA_HIP_CHECK(hipGetLastError());
+    if (g || loglik) {
+        logit_finish_launch(a.gpart, a.llpart, blocks, nc * 128, p, (g && intercept) ? g + 1 : g, loglik, s,
+                            (g && intercept) ? a.s0part : nullptr, (g && intercept) ? g : nullptr);
+        DLSA_HIP_CHECK(hipGetLastError());
+    }
+    if (!H) return DLSA_OK;
+    void* gws = ws + l.off_gram;
+    const size_t gws_bytes = l.total - l.off_gram;
+    if (!intercept) return gram_impl_f64(X, ldx, w, n, p, H, ldh, 0, gws, gws_bytes, s);
+    double* bd = (double*)(ws + l.off_border);          // [sum mu | X'mu]: row 0 of [1 | X]' diag(mu) [1 | X]
+    logit_finish_launch(a.hpart, a.swpart, blocks, nc * 128, p, bd + 1, bd, s, nullptr, nullptr);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return gram_icpt_impl(X, ldx, w, n, p, H, ldh, gws, gws_bytes, s, bd);
+}
+
+static size_t pois_state_bytes(int pe) {                 // stats, beta, prev, delta, g; then the Cholesky factor
+    return align_up(8 * (size_t)(4 * pe + 8), 256) + align_up(8 * (size_t)pe * pe, 256);
+}
+
+}  // namespace dlsa
+
+extern "C" {
+
+size_t dlsa_poisson_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step) {
+    if (p <= 0 || p + (intercept ? 1 : 0) > 2048 || max_rows < 0 || row_step < 1) return 0;
+    return dlsa::align_up(dlsa::pois_layout(max_rows, p, row_step).total, 256) + dlsa::pois_state_bytes(p + (intercept ? 1 : 0));
+}
+
+int dlsa_poisson_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, int64_t n, int p,
+                          int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes,
+                          void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && y && beta, "poisson_pass: null X, y or beta");
+    const int pe = p + (intercept ? 1 : 0);
+    DLSA_REQUIRE(n >= 1 && p > 0 && pe <= 2048 && ldx >= p && (!H || ldh >= pe), "poisson_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
+                 (long long)n, p, (long long)ldx, (long long)ldh);
+    const PoisLayout l = pois_layout(n, p, 1);
+    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
+        set_error("poisson_pass: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* wsc = (char*)ws;
+    double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
+    int rc = pois_pass_impl(X, ldx, y, offset, beta, n, p, intercept, H, ldh, g, loglik, w, wsc, l, s);
+    if (rc || !loglik) return rc;
+    rc = pois_const(y, offset, n, wsc, l, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(poisson_ll_fix_kernel, dim3(1), dim3(64), 0, s, loglik, (const double*)(wsc + l.off_cst));
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
+                         const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double tol, int max_iter,
+                         double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
+                         void* ws, size_t ws_bytes, void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && y && part_first_host && part_rows_host && coef && Sig_inv && Sig_invMcoef, "poisson_fit: null argument");
+    const int pe = p + (intercept ? 1 : 0);
+    DLSA_REQUIRE(K > 0 && p > 0 && pe <= 2048 && ldx >= p && row_step >= 1, "poisson_fit: bad shape K=%d p=%d ldx=%lld step=%lld", K, p,
+                 (long long)ldx, (long long)row_step);
+    DLSA_REQUIRE(max_iter > 0 && tol > 0, "poisson_fit: bad tol/max_iter");
+    int64_t max_rows = 0;
+    for (int k = 0; k < K; ++k) {
+        DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "poisson_fit: negative partition shape (partition %d)", k);
+        max_rows = std::max(max_rows, part_rows_host[k]);
+    }
+    const PoisLayout l = pois_layout(max_rows, p, row_step);
+    const size_t need = dlsa_poisson_workspace_bytes(max_rows, p, intercept, row_step);
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
+        set_error("poisson_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* wsc = (char*)ws;
+    double* st = (double*)(wsc + align_up(l.total, 256));
+    double* stats = st;                 // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] sum y eta - mu
+    double* beta = st + 8;
+    double* prev = beta + pe;
+    double* delta = prev + pe;
+    double* g = delta + pe;
+    double* Lf = (double*)(wsc + align_up(l.total, 256) + align_up(8 * (size_t)(4 * pe + 8), 256));
+    double* wv = (double*)(wsc + l.off_w);
+    const int64_t pitch = ldx * row_step;                     // rows first, first + step, ...: a strided view, no copy of X
+    int overall = DLSA_OK;
+    for (int k = 0; k < K; ++k) {
+        const int64_t nk = part_rows_host[k];
+        const double* Xk = X + part_first_host[k] * ldx;
+        const double* yk = y + part_first_host[k];
+        const double* ok = offset ? offset + part_first_host[k] : nullptr;
+        double* Hk = Sig_inv + (size_t)k * pe * pe;
+        double* ck = coef + (size_t)k * pe;
+        double* sk = Sig_invMcoef + (size_t)k * pe;
+        int st_k = DLSA_PART_EMPTY, iters = 0;
+        double ll = 0.0, cst[4] = {0.0, 0.0, 0.0, 0.0};
+        if (nk > 0) {
+            if (row_step > 1) {                               // the partition's counts and offsets, gathered once (8 bytes per row each)
+                const dim3 grid((unsigned)((nk + 255) / 256));
+                hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, y, part_first_host[k], row_step, nk, (double*)(wsc + l.off_y));
+                yk = (const double*)(wsc + l.off_y);
+                if (offset) {
+                    hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, offset, part_first_host[k], row_step, nk,
+                                       (double*)(wsc + l.off_o));
+                    ok = (const double*)(wsc + l.off_o);
+                }
+                DLSA_HIP_CHECK(hipGetLastError());
+            }
+            int rc = pois_const(yk, ok, nk, wsc, l, s);
+            if (rc) return rc;
+            DLSA_HIP_CHECK(hipMemcpyAsync(cst, wsc + l.off_cst, sizeof(cst), hipMemcpyDeviceToHost, s));
+            DLSA_HIP_CHECK(hipStreamSynchronize(s));
+            if (cst[3] > 0.0) {
+                set_error("poisson_fit: partition %d has %.0f rows with a negative or non-finite count or offset", k, cst[3]);
+                return DLSA_ERR_INVALID;
+            }
+        }
+        // sum y = 0: the MLE lies at eta -> -inf, where H -> 0 and H theta -> 0: the zero block is the block's limit
+        if (nk > 0 && cst[1] > 0.0) {
+            // the intercept starts at log(sum y / sum e^o), the exact MLE of the intercept-only model
+            const double b0 = (intercept && cst[2] > 0.0 && isfinite(cst[2])) ? log(cst[1] / cst[2]) : 0.0;
+            hipLaunchKernelGGL(poisson_start_kernel, dim3((pe + 255) / 256), dim3(256), 0, s, beta, pe, intercept, b0);
+            DLSA_HIP_CHECK(hipGetLastError());
+            double ll_prev = -INFINITY;
+            bool have_prev = false;
+            int halvings = 0;
+            st_k = DLSA_PART_NOT_CONVERGED;
+            for (int it = 0; it < max_iter + 1; ++it) {
+                int rc = pois_pass_impl(Xk, pitch, yk, ok, beta, nk, p, intercept, Hk, pe, g, stats + 3, wv, wsc, l, s);
+                if (rc) return rc;
+                rc = launch_chol_solve(Hk, pe, 0, g, 0, beta, 0, pe, 1, Lf, delta, 0, stats, 0, s, 0);
+                if (rc) return rc;
+                double h[4];
+                DLSA_HIP_CHECK(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, s));
+                DLSA_HIP_CHECK(hipStreamSynchronize(s));
+                ll = h[3];
+                // the previous step overshot (the likelihood dropped, or mu overflowed): halve it
+                const bool worse = !isfinite(ll) || (have_prev && ll < ll_prev - 1e-12 * fabs(ll_prev));
+                if (have_prev && worse && halvings < 30) {
+                    ++halvings;
+                    rc = launch_axpby(beta, prev, -1.0, pe, delta, s);     // delta = beta - prev
+                    if (rc) return rc;
+                    rc = launch_axpby(prev, delta, 0.5, pe, beta, s);      // beta = prev + delta / 2
+                    if (rc) return rc;
+                    continue;
+                }
+                if (!isfinite(ll)) { st_k = DLSA_PART_NAN; break; }
+                halvings = 0;
+                if (h[2] == 1.0) { st_k = DLSA_PART_NOT_SPD; break; }
+                if (h[2] == 2.0) { st_k = DLSA_PART_NAN; break; }
+                iters = it + 1;
+                if (h[0] <= tol * std::max(1.0, h[1])) { st_k = DLSA_PART_OK; break; }     // H, g, loglik are at beta
+                if (it == max_iter) break;          // (the extra pass evaluated H at the last iterate)
+                rc = launch_advance(prev, beta, delta, pe, s);
+                if (rc) return rc;
+                ll_prev = ll;
+                have_prev = true;
+            }
+        }
+        if (st_k == DLSA_PART_EMPTY) {
+            ll = 0.0;
+            DLSA_HIP_CHECK(hipMemsetAsync(Hk, 0, (size_t)pe * pe * sizeof(double), s));
+            DLSA_HIP_CHECK(hipMemsetAsync(ck, 0, (size_t)pe * sizeof(double), s));
+            DLSA_HIP_CHECK(hipMemsetAsync(sk, 0, (size_t)pe * sizeof(double), s));
+        } else {
+            ll -= cst[0];
+            DLSA_HIP_CHECK(hipMemcpyAsync(ck, beta, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
+            const int rc = launch_matvec(Hk, pe, beta, pe, sk, s);
+            if (rc) return rc;
+        }
+        if (n_iter_host) n_iter_host[k] = iters;
+        if (status_host) status_host[k] = st_k;
+        if (loglik_host) loglik_host[k] = ll;
+        if (st_k == DLSA_PART_NOT_CONVERGED && overall == DLSA_OK) overall = DLSA_ERR_NOT_CONVERGED;
+        if (st_k == DLSA_PART_NOT_SPD && overall == DLSA_OK) overall = DLSA_ERR_NOT_SPD;
+        if (st_k == DLSA_PART_NAN && overall == DLSA_OK) overall = DLSA_ERR_NAN;
+    }
+    DLSA_HIP_CHECK(hipStreamSynchronize(s));
+    return overall;
+}
+
+}  // extern "C"

@@ -726,6 +726,62 @@ def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100):
             "loglik": list(ll), "rc": rc}
 
 
+def poisson_pass(X, y, beta, offset=None, fit_intercept=False, want_H=True, want_w=False):
+    """One Poisson partition at a fixed beta (dlsa_poisson_pass_f64): eta = [1 | X] beta + offset, mu = exp(eta).  fit_intercept: the
+    ones column is implicit -- beta, g and H have p + 1 entries, intercept first.  Returns (H [pe,pe] = [1 | X]' diag(mu) [1 | X] or
+    None, g [pe] = [1 | X]'(y - mu), loglik [1] = sum y eta - mu - lgamma(y + 1), w [n] = mu or None)."""
+    lib = _lib.load()
+    _require_gpu(X, y, beta, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
+    n, p = X.shape
+    pe = p + (1 if fit_intercept else 0)
+    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
+        raise ValueError("poisson_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
+    dev = X.device
+    H = torch.empty((pe, pe), dtype=torch.float64, device=dev) if want_H else None
+    g = torch.empty((pe,), dtype=torch.float64, device=dev)
+    ll = torch.empty((1,), dtype=torch.float64, device=dev)
+    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
+    ws = _workspace(lib.dlsa_poisson_workspace_bytes(n, p, 1 if fit_intercept else 0, 1), dev)
+    check(lib.dlsa_poisson_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), n, p, 1 if fit_intercept else 0,
+                                    _ptr(H), pe, _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, w
+
+
+def poisson_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, tol=1e-13, max_iter=100):
+    """Per-partition Poisson fit (dlsa_poisson_fit_f64): partition k = rows part_first[k] + j * row_step, j < part_rows[k] (a strided
+    view: partition_id = i % K is part_first = 0..K-1, row_step = K), log link, optional offset [n], implicit intercept with
+    fit_intercept.  Same result dict as irls_fit_ex; `loglik` is the full log-likelihood at coef."""
+    lib = _lib.load()
+    _require_gpu(X, y, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
+    n, p = X.shape
+    if y.numel() != n or (offset is not None and offset.numel() != n):
+        raise ValueError("poisson_fit_ex: y and offset must have n = %d elements" % n)
+    first = [int(v) for v in part_first]
+    rows = [int(v) for v in part_rows]
+    K, step = len(first), int(row_step)
+    if len(rows) != K or K == 0 or step < 1:
+        raise ValueError("poisson_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
+    for f, r in zip(first, rows):
+        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
+            raise ValueError("poisson_fit_ex: partition outside the %d rows of X" % n)
+    pe = p + (1 if fit_intercept else 0)
+    dev = X.device
+    coef = torch.empty((K, pe), dtype=torch.float64, device=dev)
+    smc = torch.empty((K, pe), dtype=torch.float64, device=dev)
+    sig = torch.empty((K, pe, pe), dtype=torch.float64, device=dev)
+    ws = _workspace(lib.dlsa_poisson_workspace_bytes(max(rows), p, 1 if fit_intercept else 0, step), dev)
+    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
+    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
+    rc = lib.dlsa_poisson_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, 1 if fit_intercept else 0,
+                                  tol, max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
+    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
+        check(rc)
+    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
+            "loglik": list(ll), "rc": rc}
+
+
 def sum_blocks(coef, smc, sig, mask=None):
     """[sum Sig_inv | sum Sig_invMcoef | sum coef]: the rank's all-reduce message (dlsa.py:30-34)."""
     lib = _lib.load()

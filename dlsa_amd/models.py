@@ -582,3 +582,127 @@ def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_bas
     if out.isna().values.any():
         warnings.warn("NAs appear in the final output")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Poisson regression map step (log link, optional offset / exposure): counts, event rates, traffic.  Partition k's local
+# objective is its own log-likelihood sum y eta - mu - lgamma(y + 1) with eta = [1 | x]' beta + o; the block is coef = the
+# partition's MLE, Sig_inv = the Fisher information [1 | X]' diag(mu) [1 | X] there, Sig_invMcoef = Sig_inv coef, so
+# dlsa_mapred / dlsa apply unchanged.  The intercept is implicit, as in fit_logistic_partitions.
+# ---------------------------------------------------------------------------------------------
+def simulate_poisson(sample_size, p, partition_num, seed=20260101, base_rate=1.0, coef_value=0.5, exposure=False):
+    """Seeded count rows: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), beta* = coef_value on the first int(0.4p)
+    coefficients, y ~ Poisson(base_rate * exposure * exp(x beta*)) drawn with numpy; exposure (with exposure=True) ~ U(0.5, 2), else 1.
+    partition_id = i % partition_num.  Returns the frame partition_id, y, [exposure,] x0 .. x{p-1}."""
+    n, p = int(sample_size), int(p)
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    X = X.cpu().numpy()
+    beta = np.zeros(p)
+    beta[:int(0.4 * p)] = float(coef_value)
+    rng = np.random.default_rng(seed)
+    e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
+    y = rng.poisson(float(base_rate) * e * np.exp(X @ beta)).astype(np.float64)
+    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
+    return pd.DataFrame(np.concatenate(cols, 1),
+                        columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
+
+
+def _poisson_offset(offset, exposure, n, device):
+    if offset is not None and exposure is not None:
+        raise ValueError("poisson: give an offset or an exposure, not both (offset = log exposure)")
+    if exposure is not None:
+        exposure = torch.as_tensor(exposure, dtype=torch.float64, device=device)
+        if bool((exposure <= 0).any()):
+            raise ValueError("poisson: exposure must be positive")
+        offset = torch.log(exposure)
+    if offset is None:
+        return None
+    offset = torch.as_tensor(offset, dtype=torch.float64, device=device).contiguous()
+    if offset.numel() != n:
+        raise ValueError("poisson: offset / exposure must have n = %d elements" % n)
+    return offset
+
+
+def fit_poisson_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, names=None,
+                           tol=1e-13, max_iter=100):
+    """Poisson map step for the partitions of one device-resident shard: X [n, p] fp64 row-major, y [n] counts on the GPU.
+    Partitions as fit_logistic_partitions: `part_offsets` (K+1 ints, contiguous row ranges) or `partition_num` (partition_id = i % K,
+    strided views: nothing is copied but the partition's counts and offsets, 8 bytes per row each).  With fit_intercept the ones column
+    is implicit (results have p + 1 columns, `intercept` first).  `offset` [n] enters eta as is; `exposure` [n] is turned into
+    offset = log(exposure).  Returns MappedBlocks with `loglik` = the full log-likelihood per partition."""
+    if not X.is_cuda:
+        raise RuntimeError("fit_poisson_partitions runs on the GPU only (no CPU fallback)")
+    if X.dtype != torch.float64:
+        raise TypeError("fit_poisson_partitions: X must be float64, got %s" % X.dtype)
+    n, p = X.shape
+    y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
+    if y.numel() != n:
+        raise ValueError("fit_poisson_partitions: y must have n = %d elements" % n)
+    if bool((y < 0).any()):
+        raise ValueError("fit_poisson_partitions: counts must be non-negative")
+    offset = _poisson_offset(offset, exposure, n, X.device)
+    if names is None:
+        names = ["x" + str(i) for i in range(p)]
+    names = (["intercept"] if fit_intercept else []) + list(names)
+    if part_offsets is None:
+        K = int(partition_num) if partition_num else 1
+        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
+    else:
+        offs = [int(v) for v in part_offsets]
+        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+    r = engine.poisson_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept,
+                              tol=tol, max_iter=max_iter)
+    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
+
+
+def _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info,
+                   for_eval=False):
+    """(X device design WITHOUT the ones column -- the kernels carry the intercept -- or None, names, y, offset) of one chunk."""
+    drop = [c for c in (offset_name, exposure_name) if c is not None]
+    Xd, names = _device_design(sample_df.drop(columns=drop), Y_name, False, dummy_info, dummy_factors_baseline, data_info,
+                               for_eval=for_eval)
+    names = (["intercept"] if fit_intercept else []) + list(names)
+    yd = torch.from_numpy(np.ascontiguousarray(sample_df[Y_name].to_numpy(dtype=np.float64))).cuda()
+
+    def col(name):
+        return None if name is None else torch.from_numpy(np.ascontiguousarray(sample_df[name].to_numpy(dtype=np.float64))).cuda()
+    return Xd, names, yd, col(offset_name), col(exposure_name)
+
+
+def poisson_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                  dummy_factors_baseline=[], data_info=[]):
+    """Frame-level sibling of logistic_model / cox_model for count data: one partition (a pandas frame) with the count column
+    Y_name and optionally an offset or an exposure column.  Returns the p x (3+p) frame `par_id, coef, Sig_invMcoef,
+    [intercept,] <features>`; a chunk that lacks an expected dummy level returns the all-zero block with a warning."""
+    Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                                           dummy_factors_baseline, data_info)
+    if Xd is None:
+        return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+    mb = fit_poisson_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, names=names[1:] if fit_intercept else names)
+    st = mb.status[0]
+    if st == 1:
+        warnings.warn("poisson_model: Newton iterations did not converge (max_iter reached)")
+    elif st == 2:
+        warnings.warn("poisson_model: information matrix not positive definite (collinear design)")
+    out = mb.block_frame(0)
+    if out.isna().values.any():
+        warnings.warn("NAs appear in the final output")
+    return out
+
+
+def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                       dummy_factors_baseline=[], data_info=[]):
+    """Log-likelihood (sum y eta - mu - lgamma(y + 1)) of every estimator column of `par` on one partition, shaped like
+    logistic_model_eval's output: one row, a column per estimator."""
+    Xd, _, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                                       dummy_factors_baseline, data_info, for_eval=True)
+    od = _poisson_offset(od, ed, yd.numel(), yd.device)
+    X = engine.row_major(Xd)
+    pard = np.asarray(par, dtype=np.float64)
+    out = {}
+    for i in range(pard.shape[1]):
+        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+        _, _, ll, _ = engine.poisson_pass(X, yd, b, offset=od, fit_intercept=fit_intercept, want_H=False)
+        out[par.columns[i]] = [float(ll.item())]
+    return pd.DataFrame(out)

@@ -270,6 +270,30 @@ int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const dou
                      double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                      double* loglik_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Poisson regression map step (log link; the count-data family of the DLSA method) -------------------------------
+ * y_i ~ Poisson(mu_i), log mu_i = eta_i = [1 | x_i]' beta + o_i.  intercept != 0: the implicit intercept is column 0 of a
+ * (p + 1)-column design (beta / g / coef have p + 1 entries, H is (p + 1) x (p + 1), intercept first), as the *_icpt entries.
+ * offset (device, nullable) = o, e.g. log exposure.  Counts are doubles (y >= 0; non-integers are accepted).
+ * dlsa_poisson_pass_f64 at a fixed beta, one read of the rows (+ the Gram when H is wanted): H = [1 | X]' diag(mu) [1 | X]
+ * (nullable, ldh >= p + intercept, both triangles), g = [1 | X]'(y - mu) (nullable), loglik = sum y eta - mu - lgamma(y + 1)
+ * (1 value, nullable; NaN when a count is negative or a count / offset is not finite), w_out = mu (n, nullable).  The data of
+ * the pass are not checked otherwise.  mu overflows to +inf above eta = 709.78.
+ * dlsa_poisson_fit_f64: partitions as dlsa_irls_fit_ex_f64 (first row, rows, one common row_step: i % K partitions are strided
+ * views; their counts and offsets are gathered into the workspace).  Newton from beta = 0 with the intercept at
+ * log(sum y / sum e^o), step halving (at most 30 times) while the likelihood drops or is not finite, the IRLS stopping rule;
+ * outputs as dlsa_irls_fit_ex_f64 with Sig_inv = H at coef and loglik the full log-likelihood.  A partition without rows or with
+ * sum y = 0 is DLSA_PART_EMPTY with the all-zero block (the block's limit as eta -> -inf).  A negative or non-finite count or
+ * offset returns DLSA_ERR_INVALID naming the partition.  Workspace: dlsa_poisson_workspace_bytes(max rows, p, intercept,
+ * row_step); the pass takes the same query with row_step = 1. */
+size_t dlsa_poisson_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step);
+int dlsa_poisson_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, int64_t n, int p,
+                          int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                          void* ws, size_t ws_bytes, void* stream);
+int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
+                         const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double tol, int max_iter,
+                         double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                         double* loglik_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a9: local sum of partition blocks before the one-round all-reduce (dlsa.py:30-34) -
  * out = [ sum_k Sig_inv (p*p) | sum_k Sig_invMcoef (p) | sum_k coef (p) ] contiguous,
  * the message a rank contributes to the RCCL all-reduce.  Blocks whose status is not OK may
