@@ -18,7 +18,8 @@ FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -Wall -Wno-unused
 # -Wno-inline-asm ONLY for the translation units whose generated MFMA blocks name AGPRs beyond a127 in kernels bounded to
 # two waves per SIMD: hipcc calls them "reserved" but allocates them.  What the warning would have guarded is checked after
 # the build instead, on the shipped code objects (`make check` = tools/check_agpr_kernels.py: no scratch, planned AGPR
-# counts, VGPR + AGPR <= 256, no accumulator moves inside a loop).
+# counts, VGPR + AGPR <= 256, no accumulator moves inside a loop; tools/check_grid_barriers.py: every wave drains its global stores
+# before the workgroup barrier in front of a grid barrier's arrival).
 AGPR_UNITS := gram_narrow.hip gram_cyclic.hip irls_pass.hip
 $(patsubst %,$(BUILD)/%.o,$(AGPR_UNITS)) $(patsubst %,$(BUILD)/gram_plan_unit_%.o,$(PLAN_UNITS)): FLAGS += -Wno-inline-asm
 
@@ -50,6 +51,7 @@ $(OUT): $(OBJS)
 
 check: $(OUT)
 	python3 tools/check_agpr_kernels.py $(OUT)
+	python3 tools/check_grid_barriers.py $(OUT)
 
 knobs:
 	$(MAKE) BUILD=build/knobs OUT=bench/libdlsa_hip_knobs.so EXTRA=-DDLSA_DEBUG_KNOBS

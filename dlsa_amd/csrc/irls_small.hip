@@ -64,7 +64,13 @@ constexpr int SM_BSLOT = SM_MAXP + 8;
 // with ONE acquire after the match; a wait longer than the timeout sets the launch's abort word and every workgroup leaves.
 __device__ __forceinline__ bool cluster_barrier(unsigned* bar, unsigned* abort_word, unsigned nwg, unsigned& phase, long long timeout) {
     __shared__ int cb_ok;
-    __syncthreads();                 // this workgroup's global stores have been issued by every wave
+    // every wave waits for its own global stores: vmcnt counts per wave and __syncthreads() is a workgroup-scope fence (it drains
+    // LDS, not vmcnt), so without this wait thread 0's release below would not cover the other waves' stores.  Once waited for
+    // they are in this XCD's L2, whose dirty lines that one release writes back.  (An agent-scope fence in every thread instead:
+    // one L2 write-back per wave, +22 % on the p = 2000 path.)  Inline asm: hipcc may drop a fence's own vmcnt(0) (it did, on a
+    // path round lars.hip's step loop that carries a store).  tools/check_grid_barriers.py checks the shipped ISA.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     if (threadIdx.x == 0) {
         ++phase;
         const unsigned target = phase * nwg;

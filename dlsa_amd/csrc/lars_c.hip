@@ -59,7 +59,13 @@ struct CGrid {
 };
 __device__ __forceinline__ bool c_grid_barrier(CGrid& gr) {
     __shared__ int gb_ok;
-    __syncthreads();                 // this workgroup's global stores have completed in every wave
+    // every wave waits for its own global stores: vmcnt counts per wave and __syncthreads() is a workgroup-scope fence (it drains
+    // LDS, not vmcnt), so without this wait thread 0's release below would not cover the other waves' stores.  Once waited for
+    // they are in this XCD's L2, whose dirty lines that one release writes back.  (An agent-scope fence in every thread instead:
+    // one L2 write-back per wave, +22 % on the p = 2000 path.)  Inline asm: hipcc may drop a fence's own vmcnt(0) (it did, on a
+    // path round lars.hip's step loop that carries a store).  tools/check_grid_barriers.py checks the shipped ISA.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     ++gr.phase;
     if (threadIdx.x == 0) {
         const unsigned target = gr.phase * (unsigned)gr.nwg;

@@ -40,3 +40,42 @@ def test_loop_detection_flags_a_move_inside_a_loop():
     ins2 = [(0, "s_branch", 12), (4, "v_accvgpr_read_b32", None), (8, "s_endpgm", None), (12, "s_nop", None), (16, "s_branch", 4)]
     inloop2, nblocks2 = chk._cyclic_blocks(ins2)
     assert nblocks2 == 0 and not inloop2
+
+
+def test_grid_barriers_drain_every_wave_before_the_arrival():
+    """The grid barriers of lars_c / lars_q / lars.hip (both builds) / irls_small: on the shipped code objects, no global store
+    reaches the workgroup barrier in front of an arrival (s_barrier, buffer_wbl2, global_atomic_add) without an s_waitcnt vmcnt(0)
+    -- thread 0's release orders only its own wave's stores."""
+    import check_grid_barriers as chk
+    lib = os.path.join(ROOT, "dlsa_amd", "libdlsa_hip.so")
+    if not os.path.exists(lib):
+        pytest.fail("libdlsa_hip.so has not been built (run `make`)")
+    if not (os.path.exists(chk.tool("llvm-objdump")) or shutil.which("llvm-objdump")):
+        pytest.skip("llvm-objdump not available")
+    kernels, problems = chk.check(lib)
+    # lars_c 1 + lars_q 2 (the LDS-resident builds run on one workgroup) + lars.hip's grid kernel 2 + irls_small 4
+    assert len(kernels) >= 9, sorted(kernels)
+    assert not problems, "\n".join("%s: %s" % p for p in problems)
+
+
+def test_grid_barrier_check_flags_a_store_that_is_not_waited_for():
+    """The checker on hand-made instruction lists: __syncthreads() alone (lgkmcnt) in front of thread 0's release is flagged, also
+    when the wait comes before the last store; a vmcnt(0) in every wave after the stores passes."""
+    import check_grid_barriers as chk
+
+    def arrival(pre):
+        ins = [(0, "global_store_dwordx2", "v[0:1], v[2:3], off", None)] + pre + [
+            (20, "s_waitcnt", "lgkmcnt(0)", None), (24, "s_barrier", "", None), (28, "s_cbranch_execz", "", 48),
+            (32, "buffer_wbl2", "sc1", None), (40, "s_waitcnt", "vmcnt(0)", None), (44, "global_atomic_add", "v1, v2, s[0:1]", None),
+            (48, "s_endpgm", "", None)]
+        return chk.arrivals(ins)
+
+    bad = arrival([])
+    assert len(bad) == 1 and bad[0][2] == 0
+    assert arrival([(8, "buffer_wbl2", "sc1", None), (16, "s_waitcnt", "vmcnt(0) lgkmcnt(0)", None)])[0][2] is None
+    # a loop whose head waits, with a store after the wait: 8 store -> 12 -> 16 -> 20 barrier
+    loop = [(0, "s_waitcnt", "vmcnt(0)", None), (4, "s_barrier", "", None), (8, "global_store_dword", "v0, v1, off", None),
+            (12, "s_cbranch_scc1", "", 0), (16, "s_waitcnt", "lgkmcnt(0)", None), (20, "s_barrier", "", None),
+            (24, "buffer_wbl2", "sc1", None), (28, "global_atomic_add", "v1, v2, s[0:1]", None), (32, "s_endpgm", "", None)]
+    arr = chk.arrivals(loop)
+    assert len(arr) == 1 and arr[0][2] == 2
