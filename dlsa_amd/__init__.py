@@ -8,7 +8,7 @@ interface (dlsa/models.py, dlsa/dlsa.py, dlsa/lsa.py).  There is no CPU fallback
 __version__ = "0.1.0"
 
 from .models import (MappedBlocks, cox_model, fit_cox_partitions, fit_linear_chunks, fit_linear_partitions, fit_linear_streaming, fit_logistic_design, fit_logistic_partitions, linear_model,   # noqa: E402,F401
-                     fit_poisson_partitions, logistic_model, logistic_model_eval, poisson_model, poisson_model_eval, simulate_cox, simulate_logistic,
+                     fit_poisson_design, fit_poisson_partitions, logistic_model, logistic_model_eval, poisson_model, poisson_model_eval, simulate_cox, simulate_logistic,
                      simulate_poisson)
 from .design import DesignSpec, design_matrix                                                    # noqa: E402,F401
 from .dlsa import dlsa, dlsa_fit, dlsa_mapred, dlsa_mapreduce                                   # noqa: E402,F401

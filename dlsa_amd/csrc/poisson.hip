@@ -15,7 +15,10 @@
 //   3 the Gram              dlsa_gram_f64's dispatch on (X, mu) into the p x p block (gram_icpt_impl with the border).
 // The constant sum lgamma(y + 1) is a small reduction of its own, once per partition (poisson_const_kernel), which also
 // counts the rows with a negative or non-finite count or offset and sums y and e^o for the intercept's start value.
+// The Newton loop (pois_fit_core) takes the evaluation at beta as a callable and is shared with the structured one-hot fit
+// (onehot_poisson.hip) through poisson_internal.h, as are the constant-term and log-likelihood-fix launchers.
 #include "common.h"
+#include "poisson_internal.h"
 #include <math.h>
 #include <algorithm>
 
@@ -24,6 +27,7 @@ typedef double dlsa_pois_d2v __attribute__((ext_vector_type(2)));
 namespace dlsa {
 
 #include "rowdot.h"       // merged_reduce, row_of_lane, rep_mask, rank1_update
+#include "poisson_exp.h"  // exp_full
 
 int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
                   int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
@@ -42,33 +46,6 @@ int launch_advance(double* prev, double* beta, const double* delta, int n, hipSt
 constexpr int POIS_THREADS = 256;
 constexpr int POIS_WAVES = POIS_THREADS / 64;
 constexpr int POIS_MAX_BLOCKS = 2048;
-constexpr int POIS_CONST_BLOCKS = 512;
-
-// exp(a) over the whole signed range in ~20 instructions (CDNA has no fp64 exp): k = rint(a log2 e), r = a - k ln2 with a
-// two-part ln2 (|r| <= 0.347), the degree-13 Taylor polynomial of exp_neg (logistic.h), ldexp.  <= 2 ulp over the normal
-// range.  a below -746 gives 0 (exp(-745.13) is the smallest subnormal), a above 709.78 gives +inf (2^k overflows), NaN
-// stays NaN (the clamps are comparisons, not fmin / fmax).
-__device__ __forceinline__ double exp_full(double a) {
-    a = a < -746.0 ? -746.0 : (a > 710.0 ? 710.0 : a);
-    const double kf = rint(a * 1.4426950408889634);
-    double r = fma(kf, -6.93147180369123816490e-01, a);
-    r = fma(kf, -1.90821492927058770002e-10, r);
-    double q = 1.6059043836821613e-10;                      // 1/13!
-    q = fma(q, r, 2.08767569878681e-09);
-    q = fma(q, r, 2.505210838544172e-08);
-    q = fma(q, r, 2.755731922398589e-07);
-    q = fma(q, r, 2.7557319223985893e-06);
-    q = fma(q, r, 2.48015873015873e-05);
-    q = fma(q, r, 1.984126984126984e-04);
-    q = fma(q, r, 1.388888888888889e-03);
-    q = fma(q, r, 8.333333333333333e-03);
-    q = fma(q, r, 4.1666666666666664e-02);
-    q = fma(q, r, 1.6666666666666666e-01);
-    q = fma(q, r, 0.5);
-    q = fma(q, r, 1.0);
-    q = fma(q, r, 1.0);
-    return ldexp(q, (int)kf);
-}
 
 struct PoissonArgs {
     const double* X;
@@ -274,10 +251,10 @@ __global__ void poisson_gather_kernel(const double* __restrict__ v, int64_t firs
     if (j < n) out[j] = v[first + j * step];
 }
 
-// Newton start: beta = 0, the intercept (entry 0) at b0
-__global__ void poisson_start_kernel(double* __restrict__ beta, int pe, int intercept, double b0) {
+// Newton start: beta = 0, the intercept (entry icpt_col; -1: none) at b0
+__global__ void poisson_start_kernel(double* __restrict__ beta, int pe, int icpt_col, double b0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < pe) beta[i] = (intercept && i == 0) ? b0 : 0.0;
+    if (i < pe) beta[i] = i == icpt_col ? b0 : 0.0;
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -324,11 +301,16 @@ static PoisLayout pois_layout(int64_t max_rows, int p, int64_t row_step) {
     return l;
 }
 
-static int pois_const(const double* y, const double* off, int64_t n, char* ws, const PoisLayout& l, hipStream_t s) {
+int pois_const(const double* y, const double* off, int64_t n, double* cpart, double* cst, hipStream_t s) {
     const int blocks = (int)std::min<int64_t>(POIS_CONST_BLOCKS, std::max<int64_t>(1, (n + 255) / 256));
-    double* part = (double*)(ws + l.off_cpart);
-    hipLaunchKernelGGL(poisson_const_kernel, dim3(blocks), dim3(256), 0, s, y, off, n, part);
-    hipLaunchKernelGGL(poisson_const_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)part, blocks, (double*)(ws + l.off_cst));
+    hipLaunchKernelGGL(poisson_const_kernel, dim3(blocks), dim3(256), 0, s, y, off, n, cpart);
+    hipLaunchKernelGGL(poisson_const_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cpart, blocks, cst);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int pois_ll_fix(double* ll, const double* cst, hipStream_t s) {
+    hipLaunchKernelGGL(poisson_ll_fix_kernel, dim3(1), dim3(64), 0, s, ll, cst);
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
@@ -386,80 +368,21 @@ static int pois_pass_impl(const double* X, int64_t ldx, const double* y, const d
     return gram_icpt_impl(X, ldx, w, n, p, H, ldh, gws, gws_bytes, s, bd);
 }
 
-static size_t pois_state_bytes(int pe) {                 // stats, beta, prev, delta, g; then the Cholesky factor
-    return align_up(8 * (size_t)(4 * pe + 8), 256) + align_up(8 * (size_t)pe * pe, 256);
-}
-
-}  // namespace dlsa
-
-extern "C" {
-
-size_t dlsa_poisson_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step) {
-    if (p <= 0 || p + (intercept ? 1 : 0) > 2048 || max_rows < 0 || row_step < 1) return 0;
-    return dlsa::align_up(dlsa::pois_layout(max_rows, p, row_step).total, 256) + dlsa::pois_state_bytes(p + (intercept ? 1 : 0));
-}
-
-int dlsa_poisson_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, int64_t n, int p,
-                          int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes,
-                          void* stream) {
-    using namespace dlsa;
-    DLSA_REQUIRE(X && y && beta, "poisson_pass: null X, y or beta");
-    const int pe = p + (intercept ? 1 : 0);
-    DLSA_REQUIRE(n >= 1 && p > 0 && pe <= 2048 && ldx >= p && (!H || ldh >= pe), "poisson_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
-                 (long long)n, p, (long long)ldx, (long long)ldh);
-    const PoisLayout l = pois_layout(n, p, 1);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
-        set_error("poisson_pass: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    char* wsc = (char*)ws;
-    double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
-    int rc = pois_pass_impl(X, ldx, y, offset, beta, n, p, intercept, H, ldh, g, loglik, w, wsc, l, s);
-    if (rc || !loglik) return rc;
-    rc = pois_const(y, offset, n, wsc, l, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(poisson_ll_fix_kernel, dim3(1), dim3(64), 0, s, loglik, (const double*)(wsc + l.off_cst));
-    DLSA_HIP_CHECK(hipGetLastError());
-    return DLSA_OK;
-}
-
-int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
-                         const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double tol, int max_iter,
-                         double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
-                         void* ws, size_t ws_bytes, void* stream) {
-    using namespace dlsa;
-    DLSA_REQUIRE(X && y && part_first_host && part_rows_host && coef && Sig_inv && Sig_invMcoef, "poisson_fit: null argument");
-    const int pe = p + (intercept ? 1 : 0);
-    DLSA_REQUIRE(K > 0 && p > 0 && pe <= 2048 && ldx >= p && row_step >= 1, "poisson_fit: bad shape K=%d p=%d ldx=%lld step=%lld", K, p,
-                 (long long)ldx, (long long)row_step);
-    DLSA_REQUIRE(max_iter > 0 && tol > 0, "poisson_fit: bad tol/max_iter");
-    int64_t max_rows = 0;
-    for (int k = 0; k < K; ++k) {
-        DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "poisson_fit: negative partition shape (partition %d)", k);
-        max_rows = std::max(max_rows, part_rows_host[k]);
-    }
-    const PoisLayout l = pois_layout(max_rows, p, row_step);
-    const size_t need = dlsa_poisson_workspace_bytes(max_rows, p, intercept, row_step);
-    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
-        set_error("poisson_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    char* wsc = (char*)ws;
-    double* st = (double*)(wsc + align_up(l.total, 256));
-    double* stats = st;                 // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] sum y eta - mu
-    double* beta = st + 8;
+// The Newton loop of the Poisson fits (dense rows here, raw one-hot rows in onehot_poisson.hip): `eval` is the only part that
+// knows the representation of the design.
+int pois_fit_core(const char* who, const double* y, const double* offset, const int64_t* part_first_host,
+                  const int64_t* part_rows_host, int64_t row_step, int K, int pe, int icpt_col, double tol, int max_iter,
+                  double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
+                  const PoisFitBufs& b, const PoisEval& eval, hipStream_t s) {
+    double* stats = b.state;            // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] sum y eta - mu
+    double* beta = b.state + 8;
     double* prev = beta + pe;
     double* delta = prev + pe;
     double* g = delta + pe;
-    double* Lf = (double*)(wsc + align_up(l.total, 256) + align_up(8 * (size_t)(4 * pe + 8), 256));
-    double* wv = (double*)(wsc + l.off_w);
-    const int64_t pitch = ldx * row_step;                     // rows first, first + step, ...: a strided view, no copy of X
+    double* Lf = b.Lf;
     int overall = DLSA_OK;
     for (int k = 0; k < K; ++k) {
         const int64_t nk = part_rows_host[k];
-        const double* Xk = X + part_first_host[k] * ldx;
         const double* yk = y + part_first_host[k];
         const double* ok = offset ? offset + part_first_host[k] : nullptr;
         double* Hk = Sig_inv + (size_t)k * pe * pe;
@@ -470,36 +393,35 @@ int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const do
         if (nk > 0) {
             if (row_step > 1) {                               // the partition's counts and offsets, gathered once (8 bytes per row each)
                 const dim3 grid((unsigned)((nk + 255) / 256));
-                hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, y, part_first_host[k], row_step, nk, (double*)(wsc + l.off_y));
-                yk = (const double*)(wsc + l.off_y);
+                hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, y, part_first_host[k], row_step, nk, b.ybuf);
+                yk = b.ybuf;
                 if (offset) {
-                    hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, offset, part_first_host[k], row_step, nk,
-                                       (double*)(wsc + l.off_o));
-                    ok = (const double*)(wsc + l.off_o);
+                    hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, offset, part_first_host[k], row_step, nk, b.obuf);
+                    ok = b.obuf;
                 }
                 DLSA_HIP_CHECK(hipGetLastError());
             }
-            int rc = pois_const(yk, ok, nk, wsc, l, s);
+            int rc = pois_const(yk, ok, nk, b.cpart, b.cst, s);
             if (rc) return rc;
-            DLSA_HIP_CHECK(hipMemcpyAsync(cst, wsc + l.off_cst, sizeof(cst), hipMemcpyDeviceToHost, s));
+            DLSA_HIP_CHECK(hipMemcpyAsync(cst, b.cst, sizeof(cst), hipMemcpyDeviceToHost, s));
             DLSA_HIP_CHECK(hipStreamSynchronize(s));
             if (cst[3] > 0.0) {
-                set_error("poisson_fit: partition %d has %.0f rows with a negative or non-finite count or offset", k, cst[3]);
+                set_error("%s: partition %d has %.0f rows with a negative or non-finite count or offset", who, k, cst[3]);
                 return DLSA_ERR_INVALID;
             }
         }
         // sum y = 0: the MLE lies at eta -> -inf, where H -> 0 and H theta -> 0: the zero block is the block's limit
         if (nk > 0 && cst[1] > 0.0) {
             // the intercept starts at log(sum y / sum e^o), the exact MLE of the intercept-only model
-            const double b0 = (intercept && cst[2] > 0.0 && isfinite(cst[2])) ? log(cst[1] / cst[2]) : 0.0;
-            hipLaunchKernelGGL(poisson_start_kernel, dim3((pe + 255) / 256), dim3(256), 0, s, beta, pe, intercept, b0);
+            const double b0 = (icpt_col >= 0 && cst[2] > 0.0 && isfinite(cst[2])) ? log(cst[1] / cst[2]) : 0.0;
+            hipLaunchKernelGGL(poisson_start_kernel, dim3((pe + 255) / 256), dim3(256), 0, s, beta, pe, icpt_col, b0);
             DLSA_HIP_CHECK(hipGetLastError());
             double ll_prev = -INFINITY;
             bool have_prev = false;
             int halvings = 0;
             st_k = DLSA_PART_NOT_CONVERGED;
             for (int it = 0; it < max_iter + 1; ++it) {
-                int rc = pois_pass_impl(Xk, pitch, yk, ok, beta, nk, p, intercept, Hk, pe, g, stats + 3, wv, wsc, l, s);
+                int rc = eval(k, yk, ok, nk, beta, Hk, g, stats + 3);
                 if (rc) return rc;
                 rc = launch_chol_solve(Hk, pe, 0, g, 0, beta, 0, pe, 1, Lf, delta, 0, stats, 0, s, 0);
                 if (rc) return rc;
@@ -550,6 +472,76 @@ int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const do
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;
+}
+
+}  // namespace dlsa
+
+extern "C" {
+
+size_t dlsa_poisson_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step) {
+    if (p <= 0 || p + (intercept ? 1 : 0) > 2048 || max_rows < 0 || row_step < 1) return 0;
+    return dlsa::align_up(dlsa::pois_layout(max_rows, p, row_step).total, 256) + dlsa::pois_state_bytes(p + (intercept ? 1 : 0));
+}
+
+int dlsa_poisson_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, int64_t n, int p,
+                          int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes,
+                          void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && y && beta, "poisson_pass: null X, y or beta");
+    const int pe = p + (intercept ? 1 : 0);
+    DLSA_REQUIRE(n >= 1 && p > 0 && pe <= 2048 && ldx >= p && (!H || ldh >= pe), "poisson_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
+                 (long long)n, p, (long long)ldx, (long long)ldh);
+    const PoisLayout l = pois_layout(n, p, 1);
+    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
+        set_error("poisson_pass: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* wsc = (char*)ws;
+    double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
+    int rc = pois_pass_impl(X, ldx, y, offset, beta, n, p, intercept, H, ldh, g, loglik, w, wsc, l, s);
+    if (rc || !loglik) return rc;
+    rc = pois_const(y, offset, n, (double*)(wsc + l.off_cpart), (double*)(wsc + l.off_cst), s);
+    if (rc) return rc;
+    return pois_ll_fix(loglik, (const double*)(wsc + l.off_cst), s);
+}
+
+int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
+                         const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double tol, int max_iter,
+                         double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
+                         void* ws, size_t ws_bytes, void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && y && part_first_host && part_rows_host && coef && Sig_inv && Sig_invMcoef, "poisson_fit: null argument");
+    const int pe = p + (intercept ? 1 : 0);
+    DLSA_REQUIRE(K > 0 && p > 0 && pe <= 2048 && ldx >= p && row_step >= 1, "poisson_fit: bad shape K=%d p=%d ldx=%lld step=%lld", K, p,
+                 (long long)ldx, (long long)row_step);
+    DLSA_REQUIRE(max_iter > 0 && tol > 0, "poisson_fit: bad tol/max_iter");
+    int64_t max_rows = 0;
+    for (int k = 0; k < K; ++k) {
+        DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "poisson_fit: negative partition shape (partition %d)", k);
+        max_rows = std::max(max_rows, part_rows_host[k]);
+    }
+    const PoisLayout l = pois_layout(max_rows, p, row_step);
+    const size_t need = dlsa_poisson_workspace_bytes(max_rows, p, intercept, row_step);
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
+        set_error("poisson_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* wsc = (char*)ws;
+    PoisFitBufs b{};
+    b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
+    b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
+    b.state = (double*)(wsc + align_up(l.total, 256));
+    b.Lf = (double*)(wsc + align_up(l.total, 256) + align_up(8 * (size_t)(4 * pe + 8), 256));
+    double* wv = (double*)(wsc + l.off_w);
+    const int64_t pitch = ldx * row_step;                     // rows first, first + step, ...: a strided view, no copy of X
+    const PoisEval eval = [=](int k, const double* yk, const double* ok, int64_t nk, const double* beta, double* Hk, double* g,
+                              double* ll) {
+        return pois_pass_impl(X + part_first_host[k] * ldx, pitch, yk, ok, beta, nk, p, intercept, Hk, pe, g, ll, wv, wsc, l, s);
+    };
+    return pois_fit_core("poisson_fit", y, offset, part_first_host, part_rows_host, row_step, K, pe, intercept ? 0 : -1, tol, max_iter,
+                         coef, Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host, b, eval, s);
 }
 
 }  // extern "C"

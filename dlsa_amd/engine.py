@@ -1009,6 +1009,70 @@ def onehot_irls_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, t
             "loglik": list(ll), "rc": rc}
 
 
+def _oh_poisson_rows(plan, num, codes, y, offset, who):
+    _require_gpu(y, offset)
+    _f64(y, "y"); _f64(offset, "offset")
+    n = y.numel()
+    if (offset is not None and offset.numel() != n) or (num is not None and num.shape[0] != n) or \
+            (codes is not None and codes.shape[0] != n):
+        raise ValueError("%s: num, codes, y and offset must have the same n = %d rows" % (who, n))
+    return n
+
+
+def onehot_poisson_pass(plan, num, codes, y, beta, offset=None, want_H=True, want_w=False):
+    """poisson_pass on the raw representation of a one-hot design (dlsa_onehot_poisson_pass_f64): num [n,q] fp64, codes [n,f]
+    int32, counts y [n], optional offset [n]; beta has plan.p entries in the plan's column order (an intercept is the plan's
+    constant column).  Returns (H [p,p] = X' diag(mu) X or None, g [p] = X'(y - mu), loglik [1], w [n] = mu or None) of the matrix
+    dlsa_design_f64 would build -- which is never built."""
+    lib = _lib.load()
+    _require_gpu(beta)
+    _f64(beta, "beta")
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_poisson_pass")
+    p = plan.p
+    if n < 1 or beta.numel() != p:
+        raise ValueError("onehot_poisson_pass: need n >= 1 rows and beta with %d elements" % p)
+    dev = y.device
+    H = torch.empty((p, p), dtype=torch.float64, device=dev) if want_H else None
+    g = torch.empty((p,), dtype=torch.float64, device=dev)
+    ll = torch.empty((1,), dtype=torch.float64, device=dev)
+    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
+    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, n, 1), dev)
+    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
+    check(lib.dlsa_onehot_poisson_pass_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), _ptr(beta), n, _ptr(H), p, _ptr(g),
+                                           _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, w
+
+
+def onehot_poisson_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, tol=1e-13, max_iter=100):
+    """poisson_fit_ex on the raw representation of a one-hot design (dlsa_onehot_poisson_fit_f64): partition k = rows
+    part_first[k] + j * row_step, j < part_rows[k] -- strided views of num / codes, only the counts and offsets of a strided
+    partition are gathered.  Same result dict as poisson_fit_ex, plan.p columns in the plan's order."""
+    lib = _lib.load()
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_poisson_fit_ex")
+    p = plan.p
+    first, rows = [int(v) for v in part_first], [int(v) for v in part_rows]
+    K, step = len(first), int(row_step)
+    if len(rows) != K or K == 0 or step < 1:
+        raise ValueError("onehot_poisson_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
+    for f, r in zip(first, rows):
+        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
+            raise ValueError("onehot_poisson_fit_ex: partition outside the %d rows" % n)
+    dev = y.device
+    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
+    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
+    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
+    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, max(rows), step), dev)
+    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
+    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
+    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
+    rc = lib.dlsa_onehot_poisson_fit_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), c_first, c_rows, step, K, tol, max_iter,
+                                         _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
+    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
+        check(rc)
+    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
+            "loglik": list(ll), "rc": rc}
+
+
 class RcclComm:
     """An RCCL communicator opened through the C ABI (dlsa_comm_unique_id / dlsa_comm_init_rank), for hosts that do not
     use torch.distributed: rank 0 creates `RcclComm.unique_id()`, ships the 128 bytes to the other ranks out of band, every

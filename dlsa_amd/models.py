@@ -656,6 +656,57 @@ def fit_poisson_partitions(X, y, partition_num=None, part_offsets=None, fit_inte
     return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
 
 
+def fit_poisson_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, structured=True,
+                       tol=1e-13, max_iter=100):
+    """Poisson map step for a design given by its RAW columns, the sibling of fit_logistic_design: num [n, q] fp64 (columns in
+    spec.numeric_cols order), codes [n, f] int32 level codes (DesignSpec.encode) and counts y [n], all on the GPU.  With
+    structured=True and a qualifying design (spec.onehot_plan(): <= 8 dense columns, <= 8 factors) the fit runs on the raw
+    representation -- gather / histogram passes, the dense [n, p] matrix is never built; otherwise the matrix is built once by the
+    design kernel and the dense Poisson fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and
+    `exposure` as fit_poisson_partitions.  Same MappedBlocks either way (names = spec.names)."""
+    if not torch.is_tensor(y) or not y.is_cuda:
+        raise RuntimeError("fit_poisson_design runs on the GPU only (no CPU fallback)")
+    if num is not None and num.dtype != torch.float64:
+        raise TypeError("fit_poisson_design: num must be float64, got %s" % num.dtype)
+    y = y.to(torch.float64).contiguous()
+    n = y.numel()
+    if bool((y < 0).any()):
+        raise ValueError("fit_poisson_design: counts must be non-negative")
+    offset = _poisson_offset(offset, exposure, n, y.device)
+    if part_offsets is None:
+        K = int(partition_num) if partition_num else 1
+        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
+    else:
+        offs = [int(v) for v in part_offsets]
+        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+    plan = spec.onehot_plan() if structured else None
+    if plan is not None:
+        r = engine.onehot_poisson_fit_ex(plan, engine.row_major(num) if num is not None else None,
+                                         engine.row_major(codes) if codes is not None else None, y, first, rows, row_step=step,
+                                         offset=offset, tol=tol, max_iter=max_iter)
+    else:
+        X, _ = spec.build(num, codes)
+        r = engine.poisson_fit_ex(X, y, first, rows, row_step=step, offset=offset, tol=tol, max_iter=max_iter)
+    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], spec.names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
+
+
+def _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info):
+    """The raw representation of one chunk for the structured Poisson path: (spec, plan or None when the design does not qualify,
+    codes host array, unknown, y, offset column, exposure column).  The intercept is the plan's constant column."""
+    drop = [c for c in (offset_name, exposure_name) if c is not None]
+    frame = sample_df.drop(columns=drop)
+    spec = DesignSpec.from_reference(list(frame.columns), Y_name, fit_intercept, dummy_info, dummy_factors_baseline, data_info)
+    plan = spec.onehot_plan()
+    if plan is None:
+        return spec, None, None, False, None, None, None
+    _, codes, unknown = spec.encode(frame, dummy_info, numeric=False)
+    yd = torch.from_numpy(np.ascontiguousarray(sample_df[Y_name].to_numpy(dtype=np.float64))).cuda()
+
+    def col(name):
+        return None if name is None else torch.from_numpy(np.ascontiguousarray(sample_df[name].to_numpy(dtype=np.float64))).cuda()
+    return spec, plan, codes, unknown, yd, col(offset_name), col(exposure_name)
+
+
 def _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info,
                    for_eval=False):
     """(X device design WITHOUT the ones column -- the kernels carry the intercept -- or None, names, y, offset) of one chunk."""
@@ -671,15 +722,31 @@ def _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
 
 
 def poisson_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
-                  dummy_factors_baseline=[], data_info=[]):
+                  dummy_factors_baseline=[], data_info=[], structured=False):
     """Frame-level sibling of logistic_model / cox_model for count data: one partition (a pandas frame) with the count column
     Y_name and optionally an offset or an exposure column.  Returns the p x (3+p) frame `par_id, coef, Sig_invMcoef,
-    [intercept,] <features>`; a chunk that lacks an expected dummy level returns the all-zero block with a warning."""
-    Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
-                                           dummy_factors_baseline, data_info)
-    if Xd is None:
-        return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-    mb = fit_poisson_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, names=names[1:] if fit_intercept else names)
+    [intercept,] <features>`; a chunk that lacks an expected dummy level returns the all-zero block with a warning.
+    structured=True with a dummy_info and a qualifying design fits on the raw numerics + level codes (fit_poisson_design; the
+    dense one-hot matrix is never built, the missing-level check runs on the codes); the default is the dense path."""
+    mb = None
+    if structured and len(dummy_info) > 0:
+        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
+                                                                    dummy_info, dummy_factors_baseline, data_info)
+        if plan is not None:
+            names = spec.names
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                shape = (len(sample_df), len(names) - (1 if fit_intercept else 0) - len(missing))
+                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape)
+                              + "Skip modeling this part of data.")
+                return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+            mb = fit_poisson_design(spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, spec, offset=od, exposure=ed)
+    if mb is None:
+        Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                                               dummy_factors_baseline, data_info)
+        if Xd is None:
+            return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+        mb = fit_poisson_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, names=names[1:] if fit_intercept else names)
     st = mb.status[0]
     if st == 1:
         warnings.warn("poisson_model: Newton iterations did not converge (max_iter reached)")
@@ -692,14 +759,31 @@ def poisson_model(sample_df, Y_name, fit_intercept=False, offset_name=None, expo
 
 
 def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
-                       dummy_factors_baseline=[], data_info=[]):
+                       dummy_factors_baseline=[], data_info=[], structured=False):
     """Log-likelihood (sum y eta - mu - lgamma(y + 1)) of every estimator column of `par` on one partition, shaped like
-    logistic_model_eval's output: one row, a column per estimator."""
+    logistic_model_eval's output: one row, a column per estimator.  structured=True with a dummy_info and a qualifying design
+    evaluates on the raw numerics + level codes (one structured pass per estimator column); the default is the dense path."""
+    pard = np.asarray(par, dtype=np.float64)
+    if structured and len(dummy_info) > 0:
+        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
+                                                                    dummy_info, dummy_factors_baseline, data_info)
+        if plan is not None:
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                shape = (len(sample_df), len(spec.names) - (1 if fit_intercept else 0) - len(missing))
+                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape))
+            od = _poisson_offset(od, ed, yd.numel(), yd.device)
+            num, cd = spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda()
+            out = {}
+            for i in range(pard.shape[1]):
+                b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+                _, _, ll, _ = engine.onehot_poisson_pass(plan, num, cd, yd, b, offset=od, want_H=False)
+                out[par.columns[i]] = [float(ll.item())]
+            return pd.DataFrame(out)
     Xd, _, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
                                        dummy_factors_baseline, data_info, for_eval=True)
     od = _poisson_offset(od, ed, yd.numel(), yd.device)
     X = engine.row_major(Xd)
-    pard = np.asarray(par, dtype=np.float64)
     out = {}
     for i in range(pard.shape[1]):
         b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()

@@ -439,6 +439,32 @@ int dlsa_onehot_irls_fit_ex_f64(const dlsa_onehot_plan* plan, const double* num,
                                 double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
                                 void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Poisson map step on the raw representation of a one-hot design (the structured sibling of dlsa_poisson_*_f64) ----
+ * num [n x q] fp64 (ldn), codes [n x f] int32 (ldc), counts y [n], offset [n] (nullable) under a dlsa_onehot_plan: the dense
+ * n x p matrix is never built, and the results equal dlsa_poisson_pass_f64 / dlsa_poisson_fit_f64 (intercept = 0) on the matrix
+ * dlsa_design_f64 would build.  p and the column order come from the plan: beta / g / coef have plan.p entries, H is
+ * plan.p x plan.p (both triangles).  A code outside [0, nlevels) or a level without a column contributes nothing to eta.
+ * dlsa_onehot_poisson_pass_f64 at a fixed beta (n >= 1): H = X' diag(mu) X (nullable, ldh >= p), g = X'(y - mu) (nullable),
+ * loglik = sum y eta - mu - lgamma(y + 1) (1 value, nullable; NaN when a count is negative or a count / offset is not finite),
+ * w_out = mu (n, nullable).  One read of the raw rows (8q + 4f + 24 bytes per row with an offset) + the structured Gram when
+ * H is wanted, which sums mu in ordered floating point (as dlsa_onehot_gram_f64: full relative accuracy at any scale);
+ * g, loglik and H are bit-reproducible from run to run.
+ * dlsa_onehot_poisson_fit_f64: partitions as dlsa_poisson_fit_f64 (first row, rows, one common row_step; num and codes of a
+ * strided partition are read in place, its counts and offsets are gathered into the workspace), the same Newton loop -- the
+ * intercept that starts at log(sum y / sum e^o) is the plan's constant column, if it has one --, outputs, statuses and
+ * DLSA_ERR_INVALID (naming the partition) for a negative or non-finite count or offset.
+ * Workspace: dlsa_onehot_poisson_workspace_bytes(plan, max rows, row_step) (0 for a null plan, max_rows < 0 or row_step < 1);
+ * the pass takes the same query with row_step = 1. */
+size_t dlsa_onehot_poisson_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows, int64_t row_step);
+int dlsa_onehot_poisson_pass_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                 const double* y, const double* offset, const double* beta, int64_t n, double* H, int64_t ldh,
+                                 double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes, void* stream);
+int dlsa_onehot_poisson_fit_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                const double* y, const double* offset, const int64_t* part_first_host,
+                                const int64_t* part_rows_host, int64_t row_step, int K, double tol, int max_iter, double* coef,
+                                double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
+                                void* ws, size_t ws_bytes, void* stream);
+
 /* test hook: host-only validation of the Gram tile plan for p (0 = every tile on/above the diagonal
  * is stored exactly once; outputs: workgroup items, tile slots computed, tiles stored). */
 int dlsa_gram_plan_check(int p, int* nitems, int* nslots, int* ntiles);
