@@ -1,0 +1,162 @@
+"""Timing of the negative-binomial map step (csrc/negbin.hip) next to the Poisson one on the same rows.  Prints one JSON line per case:
+  pass    the NB pass alone (w, mu, g, row log-likelihood) next to dlsa_poisson_pass_f64, alternating in one call (medians), with the
+          algorithmic bandwidth of one read of the rows (8 p bytes per row); expectation: ratio <= 1.15;
+  theta   the pass entry with the dispersion terms at p and over a one-column design (8 bytes per row of rows next to the theta step's
+          own 16): an upper bound of one theta evaluation's time and a lower bound of its bandwidth;
+  eval    a Newton evaluation (pass + H + the Cholesky solve) next to the Poisson evaluation, alternating;
+  fit     a whole fit with an intercept and offsets (one partition) next to the Poisson fit of the same rows and to the NB fit at
+          the fixed alpha-hat: times, row passes, and the share of the fit the theta iterations take at most (1 - fixed / estimated).
+Without --case every case runs in a child process of its own under its own time limit, one after another; the first failure
+stops the run.  Run one case under rocprofv3 --kernel-trace --stats for the per-kernel split."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ALPHA = 0.5
+
+
+def timed(fn, reps):
+    import torch
+    fn(); fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def alternating(fa, fb, reps, rounds=5):
+    """fa and fb timed in turns in the same call: (median ms of fa, median ms of fb) over `rounds` rounds of `reps` calls each"""
+    ta, tb = [], []
+    for _ in range(rounds):
+        ta.append(timed(fa, reps))
+        tb.append(timed(fb, reps))
+    ta.sort(); tb.sort()
+    return ta[len(ta) // 2], tb[len(tb) // 2]
+
+
+def data(n, p, seed=321, intercept=0.2):
+    """synth rows, beta* = 0.5 on the first 40 % of the columns, offsets log U(0.5, 2), counts Poisson(mu G) with G ~ Gamma(2, 1/2)
+    (the sum of two exponentials, drawn on the device): NB2 with alpha = 0.5"""
+    import torch
+    from dlsa_amd import engine
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    beta = torch.zeros(p, dtype=torch.float64, device="cuda")
+    beta[: int(0.4 * p)] = 0.5
+    g = torch.Generator(device="cuda").manual_seed(9)
+    o = torch.log(torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 1.5 + 0.5)
+    u = torch.rand((2, n), dtype=torch.float64, device="cuda", generator=g).clamp_min_(1e-300)
+    mix = -ALPHA * (torch.log(u[0]) + torch.log(u[1]))
+    y = torch.poisson(torch.exp(X @ beta + intercept + o) * mix, generator=g)
+    return X, y, o, beta
+
+
+def pass_case(n, p, reps):
+    from dlsa_amd import engine
+    X, y, o, beta = data(n, p)
+    b = beta * 0.5
+    t_nb, t_po = alternating(lambda: engine.negbin_pass(X, y, b, ALPHA, offset=o, want_H=False, want_w=True),
+                             lambda: engine.poisson_pass(X, y, b, offset=o, want_H=False, want_w=True), reps)
+    gb = 8.0 * n * p
+    return {"case": "pass", "n": n, "p": p, "negbin_ms": round(t_nb, 3), "poisson_ms": round(t_po, 3), "ratio": round(t_nb / t_po, 3),
+            "expected_ratio": 1.15, "met": bool(t_nb / t_po <= 1.15), "negbin_TBps": round(gb / (t_nb * 1e-3) / 1e12, 3),
+            "poisson_TBps": round(gb / (t_po * 1e-3) / 1e12, 3),
+            "note": "both passes include their beta-free reduction (lgamma(y+1); c(theta) with lgamma(y+1))"}
+
+
+def theta_case(n, p, reps):
+    import torch
+    from dlsa_amd import engine
+    X, y, o, beta = data(n, p)
+    b = beta * 0.5
+    # the pass entry returns the full log-likelihood, so it runs negbin_kernel + one theta evaluation (with lgamma(y + 1))
+    with_t = lambda: engine.negbin_pass(X, y, b, ALPHA, offset=o, want_H=False, want_w=True, want_theta=True)
+    t_with = timed(with_t, reps)
+    del X
+    torch.cuda.empty_cache()
+    # nearly alone: over a one-column design the row pass reads 8 bytes per row, less than the theta step's own 16
+    X1 = y.reshape(-1, 1).contiguous() * 0.0
+    b1 = torch.zeros(1, dtype=torch.float64, device="cuda")
+    t_small = timed(lambda: engine.negbin_pass(X1, y, b1, ALPHA, offset=o, want_H=False, want_w=True, want_theta=True), reps * 2)
+    return {"case": "theta", "n": n, "p": p, "pass_with_theta_ms": round(t_with, 3), "p1_pass_with_theta_ms": round(t_small, 3),
+            "theta_upper_bound_TBps": round(16.0 * n / (t_small * 1e-3) / 1e12, 3),
+            "note": "p1 = row pass over one column + theta evaluation + finish launches: an upper bound of the theta step's time"}
+
+
+def eval_case(n, p, reps):
+    from dlsa_amd import engine
+    X, y, o, beta = data(n, p)
+    b = beta * 0.5
+
+    def nb():
+        H, g = engine.negbin_pass(X, y, b, ALPHA, offset=o)[:2]
+        engine.spd_solve(H, g)
+
+    def po():
+        H, g = engine.poisson_pass(X, y, b, offset=o)[:2]
+        engine.spd_solve(H, g)
+    t_nb, t_po = alternating(nb, po, reps)
+    return {"case": "eval", "n": n, "p": p, "negbin_eval_ms": round(t_nb, 3), "poisson_eval_ms": round(t_po, 3), "ratio": round(t_nb / t_po, 3)}
+
+
+def fit_case(n, p, reps):
+    import torch
+    import dlsa_amd
+    X, y, o, _ = data(n, p)
+
+    def wall(fn):
+        mb = fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            mb = fn()
+        torch.cuda.synchronize()
+        return mb, (time.perf_counter() - t0) * 1e3 / reps
+    nb, t_nb = wall(lambda: dlsa_amd.fit_negbin_partitions(X, y, fit_intercept=True, offset=o))
+    po, t_po = wall(lambda: dlsa_amd.fit_poisson_partitions(X, y, fit_intercept=True, offset=o))
+    fx, t_fx = wall(lambda: dlsa_amd.fit_negbin_partitions(X, y, fit_intercept=True, offset=o, alpha=nb.extra["alpha"][0]))
+    return {"case": "fit", "n": n, "p": p, "negbin_fit_ms": round(t_nb, 2), "poisson_fit_ms": round(t_po, 2),
+            "negbin_fixed_alpha_fit_ms": round(t_fx, 2), "negbin_row_passes": nb.n_iter[0], "poisson_row_passes": po.n_iter[0],
+            "fixed_alpha_row_passes": fx.n_iter[0], "alpha_hat": nb.extra["alpha"][0], "pearson_over_n": nb.extra["pearson"][0] / n,
+            "theta_share_upper_bound": round(max(0.0, 1.0 - t_fx / t_nb), 3), "status_ok": nb.status == [0] and po.status == [0]}
+
+
+CASES = {"pass": pass_case, "theta": theta_case, "eval": eval_case, "fit": fit_case}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--small", action="store_true", help="1e6 x 100 only (a quick check)")
+    ap.add_argument("--case", choices=sorted(CASES), help="run this case in this process")
+    ap.add_argument("--n", type=int, default=10_000_000)
+    ap.add_argument("--p", type=int, default=100)
+    ap.add_argument("--limit", type=int, default=240, help="time limit of each child process, seconds")
+    a = ap.parse_args()
+    if a.case:
+        reps = max(1, a.reps // 2) if a.case == "fit" else a.reps
+        print(json.dumps(CASES[a.case](a.n, a.p, reps)), flush=True)
+        return 0
+    shapes = [(1_000_000, 100)] if a.small else [(10_000_000, 100), (2_000_000, 500)]
+    jobs = [(c, n, p) for n, p in shapes for c in ("pass", "theta", "eval")] + [("fit", shapes[0][0], shapes[0][1])]
+    for c, n, p in jobs:             # a fresh child per case, each under its own time limit; nothing more after a failure
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--case", c, "--n", str(n), "--p", str(p),
+               "--reps", str(a.reps)]
+        rc = subprocess.call(cmd)
+        if rc != 0:
+            print(json.dumps({"case": c, "n": n, "p": p, "failed_with_exit_status": rc}), flush=True)
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -81,6 +81,14 @@ SIGNATURES = {
     "dlsa_poisson_fit_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_i64, c_int, c_int, c_int,
                                      c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_dbl),
                                      c_vp, c_sz, c_vp]),
+    "dlsa_negbin_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
+    "dlsa_negbin_pass_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_sz, c_vp]),
+    "dlsa_negbin_fit_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_i64, c_int, c_int, c_int,
+                                    c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                    ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
+                                    c_vp, c_sz, c_vp]),
+    "dlsa_negbin_special_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "dlsa_sum_blocks_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp]),
     "dlsa_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "dlsa_comm_init_rank": (c_int, [ctypes.POINTER(c_vp), c_int, ctypes.c_char_p, c_int]),

@@ -1,0 +1,709 @@
+// Negative-binomial (NB2) regression map step for overdispersed counts (log link, optional offsets / exposure, estimated or
+// fixed dispersion): one partition's log-likelihood, score and Fisher information at a fixed (beta, alpha), the dispersion
+// terms at a fixed theta = 1 / alpha, and the per-partition fit that alternates the two.  The block a partition returns
+// (coef, Sig_inv = the information about beta at (coef, alpha), Sig_inv coef) feeds the unchanged one-round combine: beta and
+// alpha are information-orthogonal in NB2, so the beta block needs no cross term.
+//
+// Algebra (one partition; D = [1 | X] with the implicit intercept, X otherwise; o = offset, 0 when absent; theta = 1/alpha):
+//   eta = D beta + o,  mu = exp(eta),  L = log1p(alpha mu),  q = 1 / (1 + alpha mu),
+//   loglik = sum [ y eta - (y + theta) L ]                                           (the row pass)
+//          + sum [ lgamma(y + theta) - lgamma(theta) - y log(theta) - lgamma(y + 1) ] (beta-free: the theta step)
+//   g = D'[(y - mu) q],  H = D' diag(mu q) D    (expected information),
+//   s(theta) = sum [ psi(y+theta) - psi(theta) - L + (mu - y) alpha q ]                         = d loglik / d theta
+//   i(theta) = sum [ psi'(theta) - psi'(y+theta) - alpha + alpha q (2 - (1 + alpha y) q) ]      = -d2 loglik / d theta2
+// (s and i are the textbook forms with log(theta) + 1 - log(theta + mu) - (y+theta)/(mu+theta) and -1/theta + 2/(mu+theta)
+// - (y+theta)/(mu+theta)^2 rewritten in alpha, so every term is O(alpha) as theta grows and nothing is formed at theta itself).
+//
+// Launches per evaluation at (beta, alpha) (every partial combines in a fixed order: no float atomics):
+//   1 negbin_kernel         poisson_kernel's skeleton (rowdot.h, RB rows per wave, non-temporal 16-byte loads, any row pitch) with
+//                           the NB terms: w = mu q (-> the Gram's weights), mu (-> the theta step), per-block partials of g,
+//                           sum (y - mu) q, sum y eta - (y + theta) L and, with the intercept and H wanted, X'w and sum w;
+//   2 logit_finish_launch   the fixed-order column sums (shared with logit.hip / poisson.hip);
+//   3 the Gram              dlsa_gram_f64's dispatch on (X, w).
+// The theta step reads y and mu only (16 bytes per row): negbin_theta_kernel + its finish, once per Newton iteration on log theta.
+//
+// Range: mu = exp_full(eta) is finite up to eta = 709.78 and 0 below -746.  alpha mu overflows before mu does; the kernel then
+// takes w = 1 / alpha, q = 0 and L = eta + log(alpha) (exact to 2^-53 once alpha mu > 2^53), so w, g and loglik are finite for
+// every eta <= 709.78 and every alpha.  Above that mu = +inf and loglik = -inf: the driver's failed step, as in the Poisson fit.
+#include "common.h"
+#include "poisson_internal.h"
+#include <math.h>
+#include <algorithm>
+
+typedef double dlsa_nb_d2v __attribute__((ext_vector_type(2)));
+
+namespace dlsa {
+
+#include "rowdot.h"          // merged_reduce, row_of_lane, rep_mask, rank1_update
+#include "poisson_exp.h"     // exp_full
+#include "negbin_special.h"  // nb_gamma_parts, nb_diffs
+
+int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
+                  int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t gram_workspace_bytes_impl(int64_t n, int p, int elem_bytes);
+int gram_icpt_impl(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
+                   void* ws, size_t ws_bytes, hipStream_t s, const double* border);
+void logit_finish_launch(const double* gpart, const double* llpart, int nblocks, int pitch, int p, double* g,
+                         double* loglik, hipStream_t stream, const double* s0part, double* s0);
+int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
+                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
+                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);
+int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s);
+int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
+int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
+
+constexpr int NB_THREADS = 256;
+constexpr int NB_WAVES = NB_THREADS / 64;
+constexpr int NB_MAX_BLOCKS = 2048;
+constexpr int NB_THETA_BLOCKS = 2048;
+// theta-step sums: c (without lgamma(y+1)), s, i, Pearson, sum (y-mu)^2 - y, bad rows, sum (y-mu)^2 - mu, sum mu^2, sum lgamma(y+1),
+// sum (y + theta) L (the alpha-dependent part of the row log-likelihood: lets the driver move it from one alpha to the next)
+constexpr int NB_NQ = 10;
+enum { NB_C = 0, NB_S = 1, NB_I = 2, NB_PEARSON = 3, NB_D0 = 4, NB_BAD = 5, NB_M1 = 6, NB_M2 = 7, NB_LG = 8, NB_YL = 9 };
+
+struct NegbinArgs {
+    const double* X;
+    const double* y;
+    const double* off;     // nullable (OFF = false)
+    const double* beta;    // the p coefficients of X's columns
+    const double* beta0;   // the intercept's coefficient (nullable: no intercept)
+    double* w_out;         // mu q per row (nullable)
+    double* mu_out;        // mu per row (nullable)
+    double* gpart;         // [nblocks][NC*128]
+    double* llpart;        // [nblocks]: sum y eta - (y + theta) L
+    double* s0part;        // [nblocks]: sum (y - mu) q (the intercept's entry of g)
+    double* hpart;         // BORDER: [nblocks][NC*128] X'w
+    double* swpart;        // BORDER: [nblocks] sum w
+    int64_t ldx;
+    int64_t n;
+    int p;
+    double alpha;          // >= 0 (0: the Poisson limit, used by the fit at its start)
+    double theta;          // 1 / alpha
+    double log_alpha;
+};
+
+static __device__ __forceinline__ double2 nb_ld2(const double* ptr) {
+    const dlsa_nb_d2v t = __builtin_nontemporal_load(reinterpret_cast<const dlsa_nb_d2v*>(ptr));
+    double2 r; r.x = t.x; r.y = t.y; return r;
+}
+
+// poisson_kernel's skeleton with the NB terms: branch-free clamped loads, the lane's own row's count and offset travel with the
+// batch, a second register set prefetches the next batch at NC = 1.
+template <int NC, int RB, bool VEC, bool OFF, bool BORDER>
+__global__ __launch_bounds__(NB_THREADS) void negbin_kernel(NegbinArgs a) {
+    __shared__ double red[NC * 128 + 2];
+    __shared__ double redh[BORDER ? NC * 128 + 1 : 1];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const double b0 = a.beta0 ? *a.beta0 : 0.0;
+    const double alpha = a.alpha, theta = a.theta, log_alpha = a.log_alpha;
+    double s0 = 0.0, sw = 0.0, ll = 0.0;
+    double2 b[NC], g[NC], h[BORDER ? NC : 1];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 128 + 2 * lane;
+        b[c].x = col < a.p ? a.beta[col] : 0.0;
+        b[c].y = col + 1 < a.p ? a.beta[col + 1] : 0.0;
+        g[c].x = 0.0; g[c].y = 0.0;
+        if constexpr (BORDER) { h[c].x = 0.0; h[c].y = 0.0; }
+    }
+    const int myrow = row_of_lane<RB>(lane);
+    const bool rep = (lane & rep_mask<RB>()) == 0;
+    const int64_t nbatch = (a.n + RB - 1) / RB;
+    const int64_t stride = (int64_t)gridDim.x * NB_WAVES;
+
+    auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], double& yv, double& ov) {
+        const int64_t row0 = bt * RB;
+        const int64_t ry = min(row0 + myrow, a.n - 1);
+        const double ytmp = a.y[ry];
+        const double otmp = OFF ? a.off[ry] : 0.0;
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const int64_t r = min(row0 + i, a.n - 1);
+            const double* rowp = a.X + r * a.ldx;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int col = c * 128 + 2 * lane;
+                const int c0 = col < a.p ? col : 0;                   // clamped columns meet beta = 0
+                if (VEC) {                                            // VEC implies p even: a pair never straddles p
+                    x[i][c] = nb_ld2(rowp + c0);
+                } else {
+                    x[i][c].x = __builtin_nontemporal_load(rowp + c0);
+                    x[i][c].y = __builtin_nontemporal_load(rowp + (col + 1 < a.p ? col + 1 : 0));
+                }
+            }
+        }
+        yv = ytmp;
+        ov = otmp;
+    };
+    auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const double yraw, const double oraw) {
+        const int64_t row0 = bt * RB;
+        double dot[RB];
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) s = fma(x[i][c].x, b[c].x, fma(x[i][c].y, b[c].y, s));
+            dot[i] = s;
+        }
+        const int64_t r = row0 + myrow;
+        const bool valid = r < a.n;
+        const double yv = valid ? yraw : 0.0;
+        const double eta = merged_reduce<RB>(dot, lane) + b0 + (OFF ? oraw : 0.0);
+        const double mu = exp_full(eta);
+        const double amu = alpha * mu;
+        // one reciprocal: q = 1 / (1 + alpha mu), w = mu q; where alpha mu overflowed (or is NaN) the limits w = 1 / alpha, q = 0
+        const bool big = !(amu <= 1e300);
+        const double q = big ? 0.0 : 1.0 / (1.0 + amu);
+        const double wgt = big ? theta : mu * q;
+        const double L = amu < 9007199254740992.0 ? log1p(amu) : (mu < INFINITY ? eta + log_alpha : INFINITY);
+        const double rs = big ? -theta : (yv - mu) * q;
+        const double resid = valid ? rs : 0.0;
+        if (valid && rep) {
+            if (a.w_out) a.w_out[r] = wgt;
+            if (a.mu_out) a.mu_out[r] = mu;
+            ll += yv * eta - (alpha > 0.0 ? (yv + theta) * L : mu);      // (y + theta) L -> mu as alpha -> 0
+            s0 += resid;
+        }
+        rank1_update<RB, NC, 0>(resid, x, g);
+        if constexpr (BORDER) {                 // X'w and sum w of the same rows (a clamped row past n weighs nothing)
+            const double wv = valid ? wgt : 0.0;
+            if (rep) sw += wv;
+            rank1_update<RB, NC, 0>(wv, x, h);
+        }
+    };
+
+    int64_t bt = (int64_t)blockIdx.x * NB_WAVES + wave;
+    if constexpr (NC == 1) {
+        double2 xa[RB][NC], xb[RB][NC];
+        double ya = 0.0, yb = 0.0, oa = 0.0, ob = 0.0;
+        if (a.n > 0) {
+            load_batch(bt, xa, ya, oa);
+            for (; bt < nbatch; bt += 2 * stride) {
+                const int64_t b1 = bt + stride, b2 = bt + 2 * stride;
+                load_batch(b1, xb, yb, ob);
+                process(bt, xa, ya, oa);
+                load_batch(b2, xa, ya, oa);
+                if (b1 < nbatch) process(b1, xb, yb, ob);
+            }
+        }
+    } else {
+        for (; bt < nbatch; bt += stride) {
+            double2 x[RB][NC];
+            double yv, ov;
+            load_batch(bt, x, yv, ov);
+            process(bt, x, yv, ov);
+        }
+    }
+
+    // block reduction: waves add into LDS one after another (fixed order)
+    ll = wave_allreduce_sum(ll);
+    s0 = wave_allreduce_sum(s0);
+    if constexpr (BORDER) sw = wave_allreduce_sum(sw);
+    for (int wv = 0; wv < NB_WAVES; ++wv) {
+        if (wave == wv) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                double* dst = red + c * 128 + 2 * lane;
+                if (wv == 0) { dst[0] = g[c].x; dst[1] = g[c].y; }
+                else { dst[0] += g[c].x; dst[1] += g[c].y; }
+                if constexpr (BORDER) {
+                    double* dh = redh + c * 128 + 2 * lane;
+                    if (wv == 0) { dh[0] = h[c].x; dh[1] = h[c].y; }
+                    else { dh[0] += h[c].x; dh[1] += h[c].y; }
+                }
+            }
+            if (lane == 0) {
+                if (wv == 0) { red[NC * 128] = ll; red[NC * 128 + 1] = s0; }
+                else { red[NC * 128] += ll; red[NC * 128 + 1] += s0; }
+                if constexpr (BORDER) { if (wv == 0) redh[NC * 128] = sw; else redh[NC * 128] += sw; }
+            }
+        }
+        __syncthreads();
+    }
+    double* gp = a.gpart + (int64_t)blockIdx.x * (NC * 128);
+    for (int col = tid; col < NC * 128; col += NB_THREADS) gp[col] = red[col];
+    if (tid == 0) { a.llpart[blockIdx.x] = red[NC * 128]; a.s0part[blockIdx.x] = red[NC * 128 + 1]; }
+    if constexpr (BORDER) {
+        double* hp = a.hpart + (int64_t)blockIdx.x * (NC * 128);
+        for (int col = tid; col < NC * 128; col += NB_THREADS) hp[col] = redh[col];
+        if (tid == 0) a.swpart[blockIdx.x] = redh[NC * 128];
+    }
+}
+
+// ---- the dispersion step: the NB_NQ sums over (y, mu) at one theta -----------------------------------------------------
+// alpha = 0 (the fit's look at the Poisson MLE) skips the special functions: only Pearson, the two moment sums and the check.
+// want_lg: also sum lgamma(y + 1) (theta-free: the fit asks once per partition).  off (nullable) is read for the data check only.
+__global__ __launch_bounds__(256) void negbin_theta_kernel(const double* __restrict__ y, const double* __restrict__ mu,
+                                                           const double* __restrict__ off, int64_t n, double alpha, double theta,
+                                                           int want_lg, double* __restrict__ part) {
+    __shared__ double red[4][NB_NQ];
+    double acc[NB_NQ];
+#pragma unroll
+    for (int j = 0; j < NB_NQ; ++j) acc[j] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double yv = y[i], m = mu[i], ov = off ? off[i] : 0.0;
+        if (!(yv >= 0.0 && isfinite(yv) && isfinite(ov))) { acc[NB_BAD] += 1.0; continue; }     // (NaN fails yv >= 0)
+        const double d = yv - m, d2 = d * d;
+        const double den = m * fma(alpha, m, 1.0);
+        acc[NB_PEARSON] += den > 0.0 ? d2 / den : (yv > 0.0 ? INFINITY : 0.0);
+        acc[NB_D0] += d2 - yv;
+        acc[NB_M1] += d2 - m;
+        acc[NB_M2] = fma(m, m, acc[NB_M2]);
+        if (want_lg) acc[NB_LG] += lgamma(yv + 1.0);
+        if (alpha > 0.0) {
+            double D1, D2, C;
+            nb_diffs(yv, theta, alpha, D1, D2, C);
+            const double amu = alpha * m;
+            const bool big = !(amu <= 1e300);
+            const double q = big ? 0.0 : 1.0 / (1.0 + amu);
+            const double L = amu < 9007199254740992.0 ? log1p(amu) : (m < INFINITY ? log(m) + log(alpha) : INFINITY);
+            const double aq = alpha * q;
+            acc[NB_C] += C;
+            acc[NB_YL] += (yv + theta) * L;
+            acc[NB_S] += D1 - L + (big ? 1.0 : (m - yv) * aq);              // (mu - y) / (mu + theta) -> 1
+            acc[NB_I] += D2 - alpha + aq * (2.0 - fma(alpha, yv, 1.0) * q);
+        }
+    }
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < NB_NQ; ++j) {
+        const double t = wave_allreduce_sum(acc[j]);
+        if ((threadIdx.x & 63) == 0) red[wave][j] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < NB_NQ) {
+        double t = red[0][threadIdx.x];
+        for (int k = 1; k < 4; ++k) t += red[k][threadIdx.x];
+        part[(int64_t)blockIdx.x * NB_NQ + threadIdx.x] = t;
+    }
+}
+
+// one wave per quantity, the block partials in a fixed order
+__global__ __launch_bounds__(64 * NB_NQ) void negbin_theta_finish_kernel(const double* __restrict__ part, int nblocks,
+                                                                         double* __restrict__ out) {
+    const int j = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double s = 0.0;
+    for (int b = lane; b < nblocks; b += 64) s += part[(int64_t)b * NB_NQ + j];
+    s = wave_allreduce_sum(s);
+    if (lane == 0) out[j] = s;
+}
+
+// the pass entry's full log-likelihood: the row sum plus c(theta) (NaN when a row is not a valid count)
+__global__ void negbin_ll_fix_kernel(double* __restrict__ ll, const double* __restrict__ tst) {
+    if (threadIdx.x == 0) ll[0] = tst[NB_BAD] > 0.0 ? NAN : ll[0] + (tst[NB_C] - tst[NB_LG]);
+}
+
+// out[j] = v[first + j * step]
+__global__ void negbin_gather_kernel(const double* __restrict__ v, int64_t first, int64_t step, int64_t n, double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = v[first + j * step];
+}
+
+// test entry: out[4 i ..] = psi(theta_i), psi'(theta_i), psi(y_i + theta_i) - psi(theta_i), lgamma(y_i + theta_i) - lgamma(theta_i) - y_i log theta_i
+__global__ void negbin_special_kernel(const double* __restrict__ theta, const double* __restrict__ y, int64_t n, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double D1, D2, C;
+    nb_diffs(y[i], theta[i], 1.0 / theta[i], D1, D2, C);
+    out[4 * i] = nb_digamma(theta[i]);
+    out[4 * i + 1] = nb_trigamma(theta[i]);
+    out[4 * i + 2] = D1;
+    out[4 * i + 3] = C;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+static int nb_nc(int p) {
+    const int chunks = (p + 127) / 128;
+    int nc = 1;
+    while (nc < chunks) nc *= 2;
+    return nc;
+}
+
+static int nb_rb(int nc) { return nc <= 2 ? 8 : nc == 4 ? 4 : nc == 8 ? 2 : 1; }
+
+static int nb_blocks(int64_t n, int rb) {
+    const int64_t nbatch = (n + rb - 1) / rb;
+    int64_t blocks = (nbatch + NB_WAVES * 4 - 1) / (NB_WAVES * 4);   // >= 4 batches per wave
+    return (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), NB_MAX_BLOCKS);
+}
+
+struct NbLayout {
+    size_t off_y, off_o, off_pois, off_gpart, off_llpart, off_s0part, off_hpart, off_swpart, off_border, off_tpart, off_tst, off_w,
+        off_mu, off_gram, off_state, total;
+};
+
+// [gathered counts | gathered offsets] of a strided partition, then the Poisson start's workspace (pois_bytes; 0 for the pass)
+// overlaid with the NB scratch: the two never run at the same time
+static NbLayout nb_layout(int64_t max_rows, int p, int intercept, int64_t row_step, size_t pois_bytes) {
+    NbLayout l{};
+    const int64_t n = std::max<int64_t>(max_rows, 1);
+    const int pe = p + (intercept ? 1 : 0);
+    const size_t gp = (size_t)NB_MAX_BLOCKS * nb_nc(p) * 128 * sizeof(double);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
+    l.off_y = take(row_step > 1 ? 8 * (size_t)n : 0);
+    l.off_o = take(row_step > 1 ? 8 * (size_t)n : 0);
+    l.off_pois = o;
+    l.off_gpart = take(gp);
+    l.off_llpart = take(8 * (size_t)NB_MAX_BLOCKS);
+    l.off_s0part = take(8 * (size_t)NB_MAX_BLOCKS);
+    l.off_hpart = take(gp);
+    l.off_swpart = take(8 * (size_t)NB_MAX_BLOCKS);
+    l.off_border = take(8 * (size_t)(p + 1));
+    l.off_tpart = take(8 * (size_t)NB_NQ * NB_THETA_BLOCKS);
+    l.off_tst = take(8 * 16);
+    l.off_w = take(8 * (size_t)n);
+    l.off_mu = take(8 * (size_t)n);
+    l.off_state = take(pois_state_bytes(pe));
+    l.off_gram = take(gram_workspace_bytes_impl(n, p, 8));
+    l.total = std::max(o, align_up(l.off_pois + pois_bytes, 256));
+    return l;
+}
+
+template <int NC, int RB, bool VEC, bool OFF>
+static void launch_nb_b(const NegbinArgs& a, bool border, int blocks, hipStream_t s) {
+    if (border) hipLaunchKernelGGL((negbin_kernel<NC, RB, VEC, OFF, true>), dim3(blocks), dim3(NB_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((negbin_kernel<NC, RB, VEC, OFF, false>), dim3(blocks), dim3(NB_THREADS), 0, s, a);
+}
+template <int NC, int RB>
+static void launch_nb(const NegbinArgs& a, bool vec, bool border, int blocks, hipStream_t s) {
+    if (vec) {
+        if (a.off) launch_nb_b<NC, RB, true, true>(a, border, blocks, s);
+        else launch_nb_b<NC, RB, true, false>(a, border, blocks, s);
+    } else {
+        if (a.off) launch_nb_b<NC, RB, false, true>(a, border, blocks, s);
+        else launch_nb_b<NC, RB, false, false>(a, border, blocks, s);
+    }
+}
+
+// One partition at a fixed (beta, alpha) (pe = p + intercept entries, intercept first).  H (nullable) needs w (the Gram's
+// weights); g, loglik (the row sum of y eta - (y + theta) L, without c(theta)), w, mu nullable otherwise.
+static int nb_pass_impl(const double* X, int64_t ldx, const double* y, const double* off, const double* beta, double alpha, int64_t n,
+                        int p, int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w, double* mu, char* ws,
+                        const NbLayout& l, hipStream_t s) {
+    const int nc = nb_nc(p), rb = nb_rb(nc);
+    const bool border = H && intercept;
+    NegbinArgs a{};
+    a.X = X; a.y = y; a.off = off; a.beta = intercept ? beta + 1 : beta; a.beta0 = intercept ? beta : nullptr;
+    a.w_out = w; a.mu_out = mu; a.ldx = ldx; a.n = n; a.p = p;
+    a.alpha = alpha; a.theta = 1.0 / alpha; a.log_alpha = log(alpha);
+    a.gpart = (double*)(ws + l.off_gpart); a.llpart = (double*)(ws + l.off_llpart); a.s0part = (double*)(ws + l.off_s0part);
+    a.hpart = (double*)(ws + l.off_hpart); a.swpart = (double*)(ws + l.off_swpart);
+    const bool vec = (ldx % 2 == 0) && (p % 2 == 0) && (((uintptr_t)X & 15) == 0);
+    const int blocks = nb_blocks(n, rb);
+    switch (nc) {
+        case 1: launch_nb<1, 8>(a, vec, border, blocks, s); break;
+        case 2: launch_nb<2, 8>(a, vec, border, blocks, s); break;
+        case 4: launch_nb<4, 4>(a, vec, border, blocks, s); break;
+        case 8: launch_nb<8, 2>(a, vec, border, blocks, s); break;
+        default: launch_nb<16, 1>(a, vec, border, blocks, s); break;
+    }
+    DLSA_HIP_CHECK(hipGetLastError());
+    if (g || loglik) {
+        logit_finish_launch(a.gpart, a.llpart, blocks, nc * 128, p, (g && intercept) ? g + 1 : g, loglik, s,
+                            (g && intercept) ? a.s0part : nullptr, (g && intercept) ? g : nullptr);
+        DLSA_HIP_CHECK(hipGetLastError());
+    }
+    if (!H) return DLSA_OK;
+    void* gws = ws + l.off_gram;
+    const size_t gws_bytes = l.total - l.off_gram;
+    if (!intercept) return gram_impl_f64(X, ldx, w, n, p, H, ldh, 0, gws, gws_bytes, s);
+    double* bd = (double*)(ws + l.off_border);          // [sum w | X'w]: row 0 of [1 | X]' diag(w) [1 | X]
+    logit_finish_launch(a.hpart, a.swpart, blocks, nc * 128, p, bd + 1, bd, s, nullptr, nullptr);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return gram_icpt_impl(X, ldx, w, n, p, H, ldh, gws, gws_bytes, s, bd);
+}
+
+// the NB_NQ sums at theta = 1 / alpha (alpha = 0: no special functions) into tst (device)
+static int nb_theta_launch(const double* y, const double* mu, const double* off, int64_t n, double alpha, int want_lg, double* tpart,
+                           double* tst, hipStream_t s) {
+    const int blocks = (int)std::min<int64_t>(NB_THETA_BLOCKS, std::max<int64_t>(1, (n + 255) / 256));
+    hipLaunchKernelGGL(negbin_theta_kernel, dim3(blocks), dim3(256), 0, s, y, mu, off, n, alpha, 1.0 / alpha, want_lg, tpart);
+    hipLaunchKernelGGL(negbin_theta_finish_kernel, dim3(1), dim3(64 * NB_NQ), 0, s, (const double*)tpart, blocks, tst);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+constexpr double NB_ALPHA_START_MIN = 1e-3;     // floor of the moment start
+constexpr double NB_ALPHA_POISSON = 1e-8;       // the theta iteration below this alpha: the partition is Poisson (alpha = 0)
+
+struct NbFitCtx {
+    const double* Xk; int64_t pitch; const double* yk; const double* ok; int64_t nk;
+    int p, intercept, pe;
+    double tol;
+    double* Hk; double* stats; double* beta; double* prev; double* delta; double* g; double* Lf;
+    double* w; double* mu; double* tpart; double* tst;
+    char* ws; const NbLayout* l; hipStream_t s;
+};
+
+static int nb_theta_eval(const NbFitCtx& c, double alpha, int want_lg, double* t) {
+    const int rc = nb_theta_launch(c.yk, c.mu, nullptr, c.nk, alpha, want_lg, c.tpart, c.tst, c.s);
+    if (rc) return rc;
+    DLSA_HIP_CHECK(hipMemcpyAsync(t, c.tst, NB_NQ * sizeof(double), hipMemcpyDeviceToHost, c.s));
+    DLSA_HIP_CHECK(hipStreamSynchronize(c.s));
+    return DLSA_OK;
+}
+
+// Newton on log theta at the current mu: step s / (i theta), clamped to [-1, 1]; stops (without stepping) at |step| <= 100 tol, or
+// where the step has stopped shrinking below 1e-8 (the rounding floor of the score).  t holds the sums at the returned alpha,
+// first_step the size of the first step (0 <=> alpha did not move), yl_first sum (y + theta) L at the alpha it came in with.
+// poisson = true: alpha fell below NB_ALPHA_POISSON.
+
+// The fit proper, from the Poisson MLE in c.beta and the start alpha: after every ACCEPTED evaluation at (beta, alpha) -- H, g, the
+// row log-likelihood, w, mu -- theta is solved for that mu (16 bytes per row and iteration), then beta takes the Newton step that
+// evaluation gave.  H is the expected information, so at alpha > 0 the beta iteration is Fisher scoring (linear convergence); one
+// theta solve per step keeps the two in lockstep instead of nesting one iteration in the other.  A step is halved (<= 30 times) while
+// the row log-likelihood at the SAME alpha drops or is not finite: the previous point's value is moved to the new alpha with
+// sum (y + theta) L of its mu.  Converged where the step of beta meets the IRLS rule and theta did not move: then H, g and t are at
+// the returned (beta, alpha).  fixed: no theta steps.
+static int nb_theta_solve(const NbFitCtx& c, double& alpha, double* t, int& theta_iters, bool& poisson, double& first_step,
+                          double& yl_first) {
+    double prev_step = INFINITY;
+    poisson = false;
+    first_step = 0.0;
+    for (int it = 0; it < 60; ++it) {
+        const int rc = nb_theta_eval(c, alpha, 0, t);
+        if (rc) return rc;
+        ++theta_iters;
+        if (it == 0) yl_first = t[NB_YL];
+        const double theta = 1.0 / alpha;
+        double step = t[NB_S] / (t[NB_I] * theta);
+        if (!(t[NB_I] > 0.0) || !isfinite(step)) step = t[NB_S] > 0.0 ? 1.0 : -1.0;
+        step = std::min(1.0, std::max(-1.0, step));
+        const double as = fabs(step);
+        if (it == 0) first_step = as;
+        if (as <= 100.0 * c.tol || (as <= 1e-8 && as >= 0.5 * prev_step)) return DLSA_OK;
+        prev_step = as;
+        alpha *= exp(-step);                                  // log theta += step
+        if (alpha < NB_ALPHA_POISSON) { poisson = true; return DLSA_OK; }
+    }
+    return DLSA_OK;
+}
+
+static int nb_joint_loop(const NbFitCtx& c, bool fixed, double& alpha, double* t, int& passes, int max_passes, int& theta_iters,
+                         bool& poisson, double& ll1, int& st) {
+    double ll_prev = -INFINITY;
+    bool have_prev = false;
+    int halvings = 0;
+    st = DLSA_PART_NOT_CONVERGED;
+    poisson = false;
+    while (passes < max_passes) {
+        int rc = nb_pass_impl(c.Xk, c.pitch, c.yk, c.ok, c.beta, alpha, c.nk, c.p, c.intercept, c.Hk, c.pe, c.g, c.stats + 3, c.w, c.mu,
+                              c.ws, *c.l, c.s);
+        if (rc) return rc;
+        ++passes;
+        rc = launch_chol_solve(c.Hk, c.pe, 0, c.g, 0, c.beta, 0, c.pe, 1, c.Lf, c.delta, 0, c.stats, 0, c.s, 0);
+        if (rc) return rc;
+        double h[4];
+        DLSA_HIP_CHECK(hipMemcpyAsync(h, c.stats, sizeof(h), hipMemcpyDeviceToHost, c.s));
+        DLSA_HIP_CHECK(hipStreamSynchronize(c.s));
+        ll1 = h[3];
+        const bool worse = !isfinite(ll1) || (have_prev && ll1 < ll_prev - 1e-12 * fabs(ll_prev));
+        if (have_prev && worse && halvings < 30) {
+            ++halvings;
+            rc = launch_axpby(c.beta, c.prev, -1.0, c.pe, c.delta, c.s);     // delta = beta - prev
+            if (rc) return rc;
+            rc = launch_axpby(c.prev, c.delta, 0.5, c.pe, c.beta, c.s);      // beta = prev + delta / 2
+            if (rc) return rc;
+            continue;
+        }
+        if (!isfinite(ll1)) { st = DLSA_PART_NAN; break; }
+        halvings = 0;
+        if (h[2] == 1.0) { st = DLSA_PART_NOT_SPD; break; }
+        if (h[2] == 2.0) { st = DLSA_PART_NAN; break; }
+        double first_step = 0.0, yl_old = 0.0;
+        if (!fixed) {
+            rc = nb_theta_solve(c, alpha, t, theta_iters, poisson, first_step, yl_old);
+            if (rc) return rc;
+            if (poisson) break;
+        }
+        if (h[0] <= c.tol * std::max(1.0, h[1]) && first_step <= 100.0 * c.tol) { st = DLSA_PART_OK; break; }
+        rc = launch_advance(c.prev, c.beta, c.delta, c.pe, c.s);
+        if (rc) return rc;
+        ll_prev = fixed ? ll1 : ll1 + (yl_old - t[NB_YL]);                   // this point's row log-likelihood at the new alpha
+        have_prev = true;
+    }
+    return DLSA_OK;
+}
+
+}  // namespace dlsa
+
+extern "C" {
+
+size_t dlsa_negbin_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step) {
+    if (p <= 0 || p + (intercept ? 1 : 0) > 2048 || max_rows < 0 || row_step < 1) return 0;
+    const size_t pois = dlsa_poisson_workspace_bytes(max_rows, p, intercept, row_step);
+    return dlsa::nb_layout(max_rows, p, intercept, row_step, pois).total;
+}
+
+int dlsa_negbin_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, double alpha,
+                         int64_t n, int p, int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                         double* mu_out, double* theta_terms, void* ws, size_t ws_bytes, void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && y && beta, "negbin_pass: null X, y or beta");
+    const int pe = p + (intercept ? 1 : 0);
+    DLSA_REQUIRE(n >= 1 && p > 0 && pe <= 2048 && ldx >= p && (!H || ldh >= pe), "negbin_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
+                 (long long)n, p, (long long)ldx, (long long)ldh);
+    DLSA_REQUIRE(alpha > 0 && isfinite(alpha), "negbin_pass: alpha must be positive and finite (alpha = 0 is dlsa_poisson_pass_f64)");
+    const NbLayout l = nb_layout(n, p, intercept, 1, 0);
+    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
+        set_error("negbin_pass: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* wsc = (char*)ws;
+    double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
+    const bool want_theta = loglik || theta_terms;
+    double* mu = mu_out ? mu_out : (want_theta ? (double*)(wsc + l.off_mu) : nullptr);
+    int rc = nb_pass_impl(X, ldx, y, offset, beta, alpha, n, p, intercept, H, ldh, g, loglik, w, mu, wsc, l, s);
+    if (rc || !want_theta) return rc;
+    double* tst = (double*)(wsc + l.off_tst);
+    rc = nb_theta_launch(y, mu, offset, n, alpha, loglik ? 1 : 0, (double*)(wsc + l.off_tpart), tst, s);
+    if (rc) return rc;
+    if (theta_terms) DLSA_HIP_CHECK(hipMemcpyAsync(theta_terms, tst + NB_S, 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (loglik) {
+        hipLaunchKernelGGL(negbin_ll_fix_kernel, dim3(1), dim3(64), 0, s, loglik, (const double*)tst);
+        DLSA_HIP_CHECK(hipGetLastError());
+    }
+    return DLSA_OK;
+}
+
+int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
+                        const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double alpha_fixed, double tol,
+                        int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                        double* loglik_host, double* alpha_host, double* alpha_info_host, double* pearson_host, void* ws,
+                        size_t ws_bytes, void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(X && y && part_first_host && part_rows_host && coef && Sig_inv && Sig_invMcoef, "negbin_fit: null argument");
+    const int pe = p + (intercept ? 1 : 0);
+    DLSA_REQUIRE(K > 0 && p > 0 && pe <= 2048 && ldx >= p && row_step >= 1, "negbin_fit: bad shape K=%d p=%d ldx=%lld step=%lld", K, p,
+                 (long long)ldx, (long long)row_step);
+    DLSA_REQUIRE(max_iter > 0 && tol > 0, "negbin_fit: bad tol/max_iter");
+    DLSA_REQUIRE(!(alpha_fixed > 0) || isfinite(alpha_fixed), "negbin_fit: a fixed alpha must be finite");
+    const bool fixed = alpha_fixed > 0;
+    int64_t max_rows = 0;
+    for (int k = 0; k < K; ++k) {
+        DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "negbin_fit: negative partition shape (partition %d)", k);
+        max_rows = std::max(max_rows, part_rows_host[k]);
+    }
+    const size_t pois_bytes = dlsa_poisson_workspace_bytes(max_rows, p, intercept, row_step);
+    const NbLayout l = nb_layout(max_rows, p, intercept, row_step, pois_bytes);
+    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
+        set_error("negbin_fit: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* wsc = (char*)ws;
+    NbFitCtx c{};
+    c.pitch = ldx * row_step; c.p = p; c.intercept = intercept; c.pe = pe; c.tol = tol;
+    c.stats = (double*)(wsc + l.off_state);        // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] the row log-likelihood
+    c.beta = c.stats + 8; c.prev = c.beta + pe; c.delta = c.prev + pe; c.g = c.delta + pe;
+    c.Lf = (double*)(wsc + l.off_state + align_up(8 * (size_t)(4 * pe + 8), 256));
+    c.w = (double*)(wsc + l.off_w); c.mu = (double*)(wsc + l.off_mu);
+    c.tpart = (double*)(wsc + l.off_tpart); c.tst = (double*)(wsc + l.off_tst);
+    c.ws = wsc; c.l = &l; c.s = s;
+    int overall = DLSA_OK;
+    for (int k = 0; k < K; ++k) {
+        const int64_t nk = part_rows_host[k];
+        double* Hk = Sig_inv + (size_t)k * pe * pe;
+        double* ck = coef + (size_t)k * pe;
+        double* sk = Sig_invMcoef + (size_t)k * pe;
+        // 1. the Poisson fit of the partition: the start, the data check, the EMPTY block, and the answer where alpha = 0
+        int st_k = DLSA_PART_EMPTY, iters = 0;
+        double ll = 0.0, alpha = 0.0, info = 0.0, pearson = 0.0;
+        int rc = dlsa_poisson_fit_f64(X, ldx, y, offset, part_first_host + k, part_rows_host + k, row_step, 1, p, intercept, tol, max_iter,
+                                      ck, Hk, sk, &iters, &st_k, &ll, wsc + l.off_pois, l.total - l.off_pois, stream);
+        if (rc == DLSA_ERR_INVALID) {
+            set_error("negbin_fit: partition %d has rows with a negative or non-finite count or offset", k);
+            return rc;
+        }
+        if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
+        if (st_k == DLSA_PART_OK) {
+            c.Xk = X + part_first_host[k] * ldx; c.nk = nk; c.Hk = Hk;
+            c.yk = y + part_first_host[k];
+            c.ok = offset ? offset + part_first_host[k] : nullptr;
+            if (row_step > 1) {                               // the partition's counts and offsets, gathered once
+                const dim3 grid((unsigned)((nk + 255) / 256));
+                double* yb = (double*)(wsc + l.off_y);
+                hipLaunchKernelGGL(negbin_gather_kernel, grid, dim3(256), 0, s, y, part_first_host[k], row_step, nk, yb);
+                c.yk = yb;
+                if (offset) {
+                    double* ob = (double*)(wsc + l.off_o);
+                    hipLaunchKernelGGL(negbin_gather_kernel, grid, dim3(256), 0, s, offset, part_first_host[k], row_step, nk, ob);
+                    c.ok = ob;
+                }
+                DLSA_HIP_CHECK(hipGetLastError());
+            }
+            DLSA_HIP_CHECK(hipMemcpyAsync(c.beta, ck, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
+            // mu at the Poisson MLE (alpha = 0: the kernel's Poisson limit; no H, no g), then the moment sums
+            rc = nb_pass_impl(c.Xk, c.pitch, c.yk, c.ok, c.beta, 0.0, nk, p, intercept, nullptr, pe, nullptr, nullptr, nullptr, c.mu, wsc, l, s);
+            if (rc) return rc;
+            int passes = 1, theta_iters = 0;
+            double t[NB_NQ];
+            rc = nb_theta_eval(c, 0.0, 1, t);
+            if (rc) return rc;
+            const double lg1 = t[NB_LG];
+            pearson = t[NB_PEARSON];
+            bool poisson = !fixed && !(t[NB_D0] > 0.0);        // 3. not overdispersed: the MLE is alpha = 0, the Poisson block stands
+            if (!poisson) {
+                alpha = fixed ? alpha_fixed : std::max(t[NB_M1] / t[NB_M2], NB_ALPHA_START_MIN);
+                if (!isfinite(alpha)) alpha = NB_ALPHA_START_MIN;
+                const int max_passes = max_iter + 2;
+                double ll1 = 0.0, fs = 0.0, yl = 0.0;
+                if (!fixed) {                                  // theta for the Poisson fit's mu
+                    rc = nb_theta_solve(c, alpha, t, theta_iters, poisson, fs, yl);
+                    if (rc) return rc;
+                }
+                if (!poisson) {
+                    rc = nb_joint_loop(c, fixed, alpha, t, passes, max_passes, theta_iters, poisson, ll1, st_k);
+                    if (rc) return rc;
+                }
+                if (poisson && passes == 1) {                  // the dispersion iterate ran off to 0 before H was touched
+                    alpha = 0.0;
+                } else if (poisson) {                          // ... or later: the Poisson block again
+                    rc = dlsa_poisson_fit_f64(X, ldx, y, offset, part_first_host + k, part_rows_host + k, row_step, 1, p, intercept, tol,
+                                              max_iter, ck, Hk, sk, nullptr, &st_k, &ll, wsc + l.off_pois, l.total - l.off_pois, stream);
+                    if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
+                    alpha = 0.0;
+                } else {
+                    if (fixed && st_k == DLSA_PART_OK) {
+                        rc = nb_theta_eval(c, alpha, 0, t);
+                        if (rc) return rc;
+                    }
+                    ll = ll1 + (t[NB_C] - lg1);
+                    info = t[NB_I] / (alpha * alpha);
+                    pearson = t[NB_PEARSON];
+                    DLSA_HIP_CHECK(hipMemcpyAsync(ck, c.beta, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
+                    rc = launch_matvec(Hk, pe, c.beta, pe, sk, s);
+                    if (rc) return rc;
+                }
+            }
+            iters += passes;
+        } else if (st_k != DLSA_PART_EMPTY) {
+            alpha = NAN; info = NAN; pearson = NAN;
+        }
+        if (n_iter_host) n_iter_host[k] = iters;
+        if (status_host) status_host[k] = st_k;
+        if (loglik_host) loglik_host[k] = ll;
+        if (alpha_host) alpha_host[k] = alpha;
+        if (alpha_info_host) alpha_info_host[k] = info;
+        if (pearson_host) pearson_host[k] = pearson;
+        if (st_k == DLSA_PART_NOT_CONVERGED && overall == DLSA_OK) overall = DLSA_ERR_NOT_CONVERGED;
+        if (st_k == DLSA_PART_NOT_SPD && overall == DLSA_OK) overall = DLSA_ERR_NOT_SPD;
+        if (st_k == DLSA_PART_NAN && overall == DLSA_OK) overall = DLSA_ERR_NAN;
+    }
+    DLSA_HIP_CHECK(hipStreamSynchronize(s));
+    return overall;
+}
+
+int dlsa_negbin_special_f64(const double* theta, const double* y, int64_t n, double* out, void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(theta && y && out && n >= 1, "negbin_special: null argument or n < 1");
+    hipLaunchKernelGGL(negbin_special_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, theta, y, n, out);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+}  // extern "C"

@@ -782,6 +782,92 @@ def poisson_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_int
             "loglik": list(ll), "rc": rc}
 
 
+def negbin_pass(X, y, beta, alpha, offset=None, fit_intercept=False, want_H=True, want_w=False, want_theta=False):
+    """One negative-binomial (NB2) partition at a fixed beta and alpha > 0 (dlsa_negbin_pass_f64): eta = [1 | X] beta + offset,
+    mu = exp(eta), Var y = mu + alpha mu^2.  Arguments as poisson_pass.  Returns (H [pe,pe] = [1 | X]' diag(mu / (1 + alpha mu)) [1 | X]
+    or None, g [pe], loglik [1] = the full log-likelihood, w [n] = mu / (1 + alpha mu) or None, mu [n] or None (with want_w),
+    theta_terms [3] = (s, i, pearson) at theta = 1 / alpha or None (with want_theta))."""
+    lib = _lib.load()
+    _require_gpu(X, y, beta, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
+    n, p = X.shape
+    pe = p + (1 if fit_intercept else 0)
+    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
+        raise ValueError("negbin_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
+    alpha = float(alpha)
+    if not (alpha > 0.0 and alpha < float("inf")):
+        raise ValueError("negbin_pass: alpha must be positive and finite (alpha = 0 is poisson_pass)")
+    dev = X.device
+    H = torch.empty((pe, pe), dtype=torch.float64, device=dev) if want_H else None
+    g = torch.empty((pe,), dtype=torch.float64, device=dev)
+    ll = torch.empty((1,), dtype=torch.float64, device=dev)
+    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
+    mu = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
+    tt = torch.empty((3,), dtype=torch.float64, device=dev) if want_theta else None
+    ws = _workspace(lib.dlsa_negbin_workspace_bytes(n, p, 1 if fit_intercept else 0, 1), dev)
+    check(lib.dlsa_negbin_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), alpha, n, p, 1 if fit_intercept else 0,
+                                   _ptr(H), pe, _ptr(g), _ptr(ll), _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, w, mu, tt
+
+
+def negbin_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, alpha=None, tol=1e-13, max_iter=100):
+    """Per-partition negative-binomial fit (dlsa_negbin_fit_f64): partitions, offset and intercept as poisson_fit_ex.  alpha=None
+    estimates the dispersion of every partition (0 for a partition that is not overdispersed: its block is the Poisson block);
+    alpha > 0 fits beta at that fixed dispersion.  The result dict of poisson_fit_ex plus the per-partition lists `alpha`,
+    `alpha_info` (the information about log alpha) and `pearson`; `loglik` is the full log-likelihood at (coef, alpha)."""
+    lib = _lib.load()
+    _require_gpu(X, y, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
+    n, p = X.shape
+    if y.numel() != n or (offset is not None and offset.numel() != n):
+        raise ValueError("negbin_fit_ex: y and offset must have n = %d elements" % n)
+    if alpha is not None:
+        alpha = float(alpha)
+        if alpha == 0.0:
+            raise ValueError("negbin_fit_ex: alpha = 0 is the Poisson model: use poisson_fit_ex")
+        if not (alpha > 0.0 and alpha < float("inf")):
+            raise ValueError("negbin_fit_ex: a fixed alpha must be positive and finite")
+    first = [int(v) for v in part_first]
+    rows = [int(v) for v in part_rows]
+    K, step = len(first), int(row_step)
+    if len(rows) != K or K == 0 or step < 1:
+        raise ValueError("negbin_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
+    for f, r in zip(first, rows):
+        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
+            raise ValueError("negbin_fit_ex: partition outside the %d rows of X" % n)
+    pe = p + (1 if fit_intercept else 0)
+    dev = X.device
+    coef = torch.empty((K, pe), dtype=torch.float64, device=dev)
+    smc = torch.empty((K, pe), dtype=torch.float64, device=dev)
+    sig = torch.empty((K, pe, pe), dtype=torch.float64, device=dev)
+    ws = _workspace(lib.dlsa_negbin_workspace_bytes(max(rows), p, 1 if fit_intercept else 0, step), dev)
+    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
+    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
+    al, info, pear = (ctypes.c_double * K)(), (ctypes.c_double * K)(), (ctypes.c_double * K)()
+    rc = lib.dlsa_negbin_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, 1 if fit_intercept else 0,
+                                 alpha if alpha is not None else 0.0, tol, max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll,
+                                 al, info, pear, _ptr(ws), ws.numel(), _stream())
+    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
+        check(rc)
+    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
+            "loglik": list(ll), "alpha": list(al), "alpha_info": list(info), "pearson": list(pear), "rc": rc}
+
+
+def negbin_special(theta, y):
+    """The dispersion kernel's special functions (dlsa_negbin_special_f64, a test entry): theta [m] > 0, y [m] >= 0 on the GPU;
+    returns [m, 4] = psi(theta), psi'(theta), psi(y + theta) - psi(theta), lgamma(y + theta) - lgamma(theta) - y log(theta)."""
+    lib = _lib.load()
+    _require_gpu(theta, y)
+    _f64(theta, "theta"); _f64(y, "y")
+    m = theta.numel()
+    if m < 1 or y.numel() != m:
+        raise ValueError("negbin_special: theta and y must have the same number (>= 1) of elements")
+    theta, y = theta.contiguous(), y.contiguous()
+    out = torch.empty((m, 4), dtype=torch.float64, device=theta.device)
+    check(lib.dlsa_negbin_special_f64(_ptr(theta), _ptr(y), m, _ptr(out), _stream()))
+    return out
+
+
 def sum_blocks(coef, smc, sig, mask=None):
     """[sum Sig_inv | sum Sig_invMcoef | sum coef]: the rank's all-reduce message (dlsa.py:30-34)."""
     lib = _lib.load()

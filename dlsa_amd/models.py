@@ -28,7 +28,7 @@ class MappedBlocks:
     `par_id, coef, Sig_invMcoef, <names...>` (models.py:136-142)."""
 
     def __init__(self, coef, Sig_invMcoef, Sig_inv, names, status=None, n_iter=None, loglik=None,
-                 num_partitions=None, sample_size=None):
+                 num_partitions=None, sample_size=None, extra=None):
         self.coef, self.Sig_invMcoef, self.Sig_inv = coef, Sig_invMcoef, Sig_inv
         self.names = list(names)
         K = coef.shape[0]
@@ -37,6 +37,7 @@ class MappedBlocks:
         self.loglik = list(loglik) if loglik is not None else [0.0] * K
         self.num_partitions = K if num_partitions is None else int(num_partitions)
         self.sample_size = sample_size
+        self.extra = {} if extra is None else {k: list(v) for k, v in extra.items()}     # per-partition lists of a family's own
 
     @property
     def columns(self):
@@ -788,5 +789,121 @@ def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=
     for i in range(pard.shape[1]):
         b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
         _, _, ll, _ = engine.poisson_pass(X, yd, b, offset=od, fit_intercept=fit_intercept, want_H=False)
+        out[par.columns[i]] = [float(ll.item())]
+    return pd.DataFrame(out)
+
+
+# ---------------------------------------------------------------------------------------------
+# Negative-binomial (NB2) map step for overdispersed counts: Var y = mu + alpha mu^2.  On such data a Poisson block has the right
+# coef and a Sig_inv too large by the dispersion factor, which the combine's weights and the AIC / BIC choice inherit.  beta and
+# alpha are information-orthogonal, so the block stays [coef | Sig_inv coef | Sig_inv] over the regression coefficients with
+# Sig_inv = [1 | X]' diag(mu / (1 + alpha mu)) [1 | X], and dlsa_mapred / dlsa apply unchanged.
+# ---------------------------------------------------------------------------------------------
+def simulate_negbin(sample_size, p, partition_num, alpha, seed=20260101, base_rate=1.0, coef_value=0.5, exposure=False):
+    """simulate_poisson's rows and frame with overdispersed counts: y ~ Poisson(mu * G), G ~ Gamma(shape 1 / alpha, scale alpha)
+    (mean 1), so y ~ NB2(mu, alpha) with mu = base_rate * exposure * exp(x beta*)."""
+    n, p, alpha = int(sample_size), int(p), float(alpha)
+    if not alpha > 0:
+        raise ValueError("simulate_negbin: alpha must be positive (alpha = 0 is simulate_poisson)")
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    X = X.cpu().numpy()
+    beta = np.zeros(p)
+    beta[:int(0.4 * p)] = float(coef_value)
+    rng = np.random.default_rng(seed)
+    e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
+    mu = float(base_rate) * e * np.exp(X @ beta)
+    y = rng.poisson(mu * rng.gamma(1.0 / alpha, alpha, n)).astype(np.float64)
+    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
+    return pd.DataFrame(np.concatenate(cols, 1),
+                        columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
+
+
+def fit_negbin_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, alpha=None,
+                          names=None, tol=1e-13, max_iter=100):
+    """Negative-binomial map step for the partitions of one device-resident shard; arguments as fit_poisson_partitions.  alpha=None
+    estimates every partition's own dispersion (a partition that is not overdispersed gets alpha = 0 and exactly its Poisson block);
+    alpha > 0 fits every partition at that common dispersion (e.g. combine_dispersion of a first map step); alpha = 0 is refused:
+    that is fit_poisson_partitions.  Returns MappedBlocks with `loglik` = the full log-likelihood per partition and
+    `extra` = {"alpha", "alpha_info" (the information about log alpha), "pearson"} per partition."""
+    if not X.is_cuda:
+        raise RuntimeError("fit_negbin_partitions runs on the GPU only (no CPU fallback)")
+    if X.dtype != torch.float64:
+        raise TypeError("fit_negbin_partitions: X must be float64, got %s" % X.dtype)
+    if alpha is not None and float(alpha) == 0.0:
+        raise ValueError("fit_negbin_partitions: alpha = 0 is the Poisson model: use fit_poisson_partitions")
+    n, p = X.shape
+    y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
+    if y.numel() != n:
+        raise ValueError("fit_negbin_partitions: y must have n = %d elements" % n)
+    if bool((y < 0).any()):
+        raise ValueError("fit_negbin_partitions: counts must be non-negative")
+    offset = _poisson_offset(offset, exposure, n, X.device)
+    if names is None:
+        names = ["x" + str(i) for i in range(p)]
+    names = (["intercept"] if fit_intercept else []) + list(names)
+    if part_offsets is None:
+        K = int(partition_num) if partition_num else 1
+        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
+    else:
+        offs = [int(v) for v in part_offsets]
+        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+    r = engine.negbin_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept, alpha=alpha,
+                             tol=tol, max_iter=max_iter)
+    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n,
+                        extra={"alpha": r["alpha"], "alpha_info": r["alpha_info"], "pearson": r["pearson"]})
+
+
+def combine_dispersion(mb):
+    """The common dispersion of a negative-binomial map step: the information-weighted mean of log alpha_k over the partitions with
+    status OK and alpha_k > 0 (weights alpha_info), returned as alpha -- the one-round combine of the dispersion, to be passed as
+    `alpha=` to a second map step.  0.0 when no partition is overdispersed."""
+    al, info = mb.extra["alpha"], mb.extra["alpha_info"]
+    use = [k for k in range(len(al)) if mb.status[k] == 0 and al[k] > 0 and info[k] > 0]
+    if not use:
+        return 0.0
+    wsum = sum(info[k] for k in use)
+    return float(np.exp(sum(info[k] * np.log(al[k]) for k in use) / wsum))
+
+
+def negbin_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, alpha=None, dummy_info=[],
+                 dummy_factors_baseline=[], data_info=[]):
+    """Frame-level sibling of poisson_model for overdispersed counts: one partition (a pandas frame) with the count column Y_name and
+    optionally an offset or an exposure column; alpha as fit_negbin_partitions.  Returns the p x (3+p) frame `par_id, coef,
+    Sig_invMcoef, [intercept,] <features>` with the dispersion in `out.attrs["alpha"]`; a chunk that lacks an expected dummy level
+    returns the all-zero block with a warning."""
+    Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                                           dummy_factors_baseline, data_info)
+    if Xd is None:
+        out = pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+        out.attrs["alpha"] = 0.0
+        return out
+    mb = fit_negbin_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, alpha=alpha,
+                               names=names[1:] if fit_intercept else names)
+    st = mb.status[0]
+    if st == 1:
+        warnings.warn("negbin_model: Newton iterations did not converge (max_iter reached)")
+    elif st == 2:
+        warnings.warn("negbin_model: information matrix not positive definite (collinear design)")
+    out = mb.block_frame(0)
+    if out.isna().values.any():
+        warnings.warn("NAs appear in the final output")
+    out.attrs["alpha"] = mb.extra["alpha"][0]
+    return out
+
+
+def negbin_model_eval(sample_df, Y_name, par, alpha, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                      dummy_factors_baseline=[], data_info=[]):
+    """Negative-binomial log-likelihood at dispersion alpha > 0 of every estimator column of `par` on one partition, shaped like
+    poisson_model_eval's output: one row, a column per estimator (one pass without the information per column)."""
+    pard = np.asarray(par, dtype=np.float64)
+    Xd, _, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                                       dummy_factors_baseline, data_info, for_eval=True)
+    od = _poisson_offset(od, ed, yd.numel(), yd.device)
+    X = engine.row_major(Xd)
+    out = {}
+    for i in range(pard.shape[1]):
+        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+        ll = engine.negbin_pass(X, yd, b, alpha, offset=od, fit_intercept=fit_intercept, want_H=False)[2]
         out[par.columns[i]] = [float(ll.item())]
     return pd.DataFrame(out)

@@ -294,6 +294,40 @@ int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const do
                          double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                          double* loglik_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Negative-binomial (NB2) regression map step (log link; overdispersed counts) --------------------------------------
+ * y_i ~ NB(mu_i, alpha), Var y = mu + alpha mu^2, theta = 1 / alpha, log mu_i = eta_i = [1 | x_i]' beta + o_i.  intercept, offset
+ * and counts as the Poisson entries.  beta and alpha are information-orthogonal, so a partition's block stays
+ * [coef | Sig_inv coef | Sig_inv] over the regression coefficients with Sig_inv the expected information about beta.
+ * dlsa_negbin_pass_f64 at a fixed beta and alpha > 0 (finite; alpha = 0 is dlsa_poisson_pass_f64), one read of the rows (+ the Gram
+ * when H is wanted): H = [1 | X]' diag(mu / (1 + alpha mu)) [1 | X] (nullable, ldh >= p + intercept, both triangles),
+ * g = [1 | X]'[(y - mu) / (1 + alpha mu)] (nullable), loglik = the full log-likelihood (1 value, nullable; NaN when a count is negative
+ * or a count / offset is not finite), w_out = mu / (1 + alpha mu) (n, nullable), mu_out = mu (n, nullable), theta_terms (3 device
+ * doubles, nullable) = [s, i, pearson]: the score and the information about theta at (beta, alpha) and sum (y - mu)^2 / (mu + alpha
+ * mu^2).  The data of the pass are not checked otherwise.  mu overflows to +inf above eta = 709.78 (loglik = -inf); below that w, g
+ * and loglik stay finite even where alpha mu overflows.
+ * dlsa_negbin_fit_f64: partitions as dlsa_poisson_fit_f64.  Each partition is first fitted as Poisson (dlsa_poisson_fit_f64: the
+ * start, the data check, DLSA_PART_EMPTY with the all-zero block, DLSA_ERR_INVALID naming the partition).  alpha_fixed > 0: Newton
+ * on beta at that alpha only.  alpha_fixed <= 0: alpha is estimated -- where sum (y - mu)^2 - y <= 0 at the Poisson fit the MLE is
+ * alpha = 0 and the Poisson block is returned as it is (DLSA_PART_OK, alpha_host = 0); otherwise Newton on log theta (16 bytes per
+ * row and iteration, |step| <= 100 tol) alternates with Newton on beta (step halving at most 30 times, the IRLS stopping rule)
+ * until neither moves.  An iterate below alpha = 1e-8 is taken as alpha = 0 (the Poisson block).  Outputs as
+ * dlsa_poisson_fit_f64 with Sig_inv = H at (coef, alpha), n_iter the row passes (the Poisson start included), loglik the full
+ * log-likelihood; alpha_host, alpha_info_host (i theta^2: the information about log alpha) and pearson_host are host arrays of K
+ * (each nullable; NaN for a partition whose Poisson start failed).  Workspace: dlsa_negbin_workspace_bytes(max rows, p, intercept,
+ * row_step); the pass takes the same query with row_step = 1.
+ * dlsa_negbin_special_f64 (a test entry): out[4 i ..] = psi(theta_i), psi'(theta_i), psi(y_i + theta_i) - psi(theta_i) and
+ * lgamma(y_i + theta_i) - lgamma(theta_i) - y_i log(theta_i) as the dispersion kernel computes them (theta > 0, y >= 0; device). */
+size_t dlsa_negbin_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step);
+int dlsa_negbin_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, double alpha,
+                         int64_t n, int p, int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                         double* mu_out, double* theta_terms, void* ws, size_t ws_bytes, void* stream);
+int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
+                        const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double alpha_fixed, double tol,
+                        int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                        double* loglik_host, double* alpha_host, double* alpha_info_host, double* pearson_host,
+                        void* ws, size_t ws_bytes, void* stream);
+int dlsa_negbin_special_f64(const double* theta, const double* y, int64_t n, double* out, void* stream);
+
 /* ---- a9: local sum of partition blocks before the one-round all-reduce (dlsa.py:30-34) -
  * out = [ sum_k Sig_inv (p*p) | sum_k Sig_invMcoef (p) | sum_k coef (p) ] contiguous,
  * the message a rank contributes to the RCCL all-reduce.  Blocks whose status is not OK may
