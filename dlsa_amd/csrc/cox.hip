@@ -1,4 +1,4 @@
-// Cox proportional-hazards map step (Breslow ties): one partition's log partial likelihood, score and observed information
+// Cox proportional-hazards map step (Breslow or Efron ties): one partition's log partial likelihood, score and observed information
 // at a fixed beta, and the per-partition Newton fit on top of it.  The local objective of a partition is its own partial
 // likelihood with risk sets taken inside the partition (a Cox model stratified by partition with a common beta); the blocks
 // it returns (coef, Sig_inv = observed information at coef, Sig_inv coef) feed the unchanged one-round combine.
@@ -11,6 +11,17 @@
 // so H is two weighted Grams on the existing MFMA kernels (X in its own row layout, and the D event rows of A) and no
 // p x p work per event.
 //
+// Efron's approximation (ties = DLSA_COX_TIES_EFRON; every kernel below carries it as the instantiation EF, the Breslow
+// instantiation is the code above): T0_i, T1_i are the sums of S0_i, S1_i over the EVENT rows of group i only,
+// f_l = l / d_i, phi_il = S0_i - f_l T0_i for l = 0 .. d_i - 1, and
+//   loglik = sum_events eta - sum_i sum_l log phi_il
+//   U = X' delta - sum_i (h1_i S1_i - h2_i T1_i),            h1_i = sum_l 1 / phi_il, h2_i = sum_l f_l / phi_il
+//   H = X' diag(w) X - sum_i [S1_i T1_i] K_i [S1_i T1_i]',   K_i = [[k0, -k1], [-k1, k2]], k_m = sum_l f_l^m / phi_il^2
+//   w_j = exp(eta_j) (c_j - delta_j h2_g(j)),                c_j = sum_{i : e_i >= pos(j)} h1_i
+// With the 2 x 2 Cholesky factor K = L L' a group gives the A rows L11 S1 + L21 T1 and (d_i >= 2) L22 T1, both of weight
+// -1, so H stays two weighted Grams.  d_i = 1 gives k1 = k2 = 0 and Breslow's terms.  A group end costs O(p) vector work
+// and the scalar sums over l, which the wave's 64 lanes share (lane t takes l = t, t + 64, ..; one fixed butterfly).
+//
 // Passes (every partial combines in a fixed order: no float atomics, no waits between workgroups inside a launch):
 //   1 cox_eta_kernel      one wave per segment of L consecutive positions: eta (written per position), the segment's
 //                         max eta M and sums of exp(eta - M) [1, x], and the tie-group bookkeeping of the segment;
@@ -18,7 +29,7 @@
 //                         max when combined), plus the open tie group entering every segment and the index of its
 //                         first event row of A;
 //   3 cox_scan_kernel     the segment re-walked from its prefix: A rows (a chunk of them per launch), the segment's
-//                         partials of loglik and U, and d_i / S0_i at every group end;
+//                         partials of loglik and U, and d_i / S0_i (Efron: h1_i, and h2_i beside it) at every group end;
 //   4 cox_finish_kernel + cox_w_kernel: the suffix sum of d_i / S0_i (over segments, then inside each segment by wave
 //                         scans) and w; the column sums of the loglik and U partials;
 //   5 the two Grams: dlsa_gram_f64(A, -d) per chunk and dlsa_gram_f64(X, w) accumulated into H.
@@ -103,6 +114,14 @@ struct CoxArgs {
     double* A; int64_t lda; double* dA; int64_t g0; int64_t ca; int chunk; int nchunks;
     double* wv; int64_t vlo; int64_t vstep; int64_t vrows;      // Gram weights of the view rows [vlo + r vstep, r < vrows]
     double* w_out;                   // [n] per position, nullable
+    // Efron only (appended: the fields above keep their kernel-argument offsets)
+    int ties;
+    double* tailV;                   // [(p + 1) x nseg]: sums over the segment's event rows after its last end (all of them without one), scaled by segM
+    double* tcM; double* tcV;        // [nseg], [(p + 1) x nseg]: T0 / T1 of the tie group open at the segment's start
+    int* tie2;                       // [nseg]: ends of the segment whose own run holds two events or more
+    double* h2v;                     // [n] h2 at group ends as (hzq, v); -1 at every other position
+    double* segNq; double* segNv;    // [nseg] (Q, h2) of the segment's first end
+    double* sufNq; double* sufNv;    // [nseg] (Q, h2) of the first end after the segment
 };
 
 // ---- pass 1 ----------------------------------------------------------------------------------------------------------
@@ -114,7 +133,7 @@ __device__ __forceinline__ void bcast_rows(double v, double (&out)[RB]) {
     }
 }
 
-template <int NC, bool VEC>
+template <int NC, bool VEC, bool EF>
 __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
     constexpr int RB = NC >= 8 ? 1 : COX_RB;        // (wide rows: one row per step keeps the row registers from spilling)
     const int lane = threadIdx.x & 63;
@@ -130,6 +149,14 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
     }
     double M = -INFINITY, s0 = 0.0;
     int has_end = 0, head = 0, tail = 0, nend = 0;
+    double t0 = 0.0;                                // (EF) the sums over the event rows of the open tie group
+    double2 t1[EF ? NC : 1];
+    int nend2 = 0;
+    (void)t0; (void)t1; (void)nend2;
+    if constexpr (EF) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
+    }
     const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
     const int myrow = row_of_lane<RB>(lane);
     for (int64_t q0 = p0; q0 < p1; q0 += RB) {
@@ -161,6 +188,11 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
                 s0 *= r;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) { s1[c].x *= r; s1[c].y *= r; }
+                if constexpr (EF) {
+                    t0 *= r;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { t1[c].x *= r; t1[c].y *= r; }
+                }
                 M = et;
             }
             const double e = exp_neg(M - et);
@@ -171,9 +203,22 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
             const int ev = a.event[r] != 0.0;
             const bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
             tail += ev;
+            if constexpr (EF) {
+                if (ev) {
+                    t0 += e;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { t1[c].x = fma(e, x[i][c].x, t1[c].x); t1[c].y = fma(e, x[i][c].y, t1[c].y); }
+                }
+            }
             if (end) {
                 if (!has_end) head = tail;
                 nend += tail > 0;
+                if constexpr (EF) {
+                    nend2 += tail > 1;
+                    t0 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
+                }
                 has_end = 1;
                 tail = 0;
             }
@@ -183,12 +228,17 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
         a.segM[s] = M;
         a.segV[s] = s0;
         a.tie[s] = has_end; a.tie[a.ld + s] = head; a.tie[2 * a.ld + s] = tail; a.tie[3 * a.ld + s] = nend;
+        if constexpr (EF) { a.tie2[s] = nend2; a.tailV[s] = t0; }
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int col = c * 128 + 2 * lane;
         if (col < a.p) a.segV[(int64_t)(1 + col) * a.ld + s] = s1[c].x;
         if (col + 1 < a.p) a.segV[(int64_t)(2 + col) * a.ld + s] = s1[c].y;
+        if constexpr (EF) {
+            if (col < a.p) a.tailV[(int64_t)(1 + col) * a.ld + s] = t1[c].x;
+            if (col + 1 < a.p) a.tailV[(int64_t)(2 + col) * a.ld + s] = t1[c].y;
+        }
     }
 }
 
@@ -217,13 +267,30 @@ __device__ void seg_scan(int nseg, State ident, Load load, Comb comb, Store stor
 
 struct PreS { double M, v; };
 struct TieS { int f, c; };
+struct TcS { int f; double M, v; };     // (Efron) a scaled sum that a segment with a group end restarts
 
-// ---- pass 2: blocks 0 .. p: prefix of column (S0, S1_c); block p + 1: tie groups and A-row indices ---------------------
+// ---- pass 2: blocks 0 .. p: prefix of column (S0, S1_c); block p + 1: tie groups and A-row indices; Efron: blocks
+// p + 2 .. 2 p + 2: column (T0, T1_c) of the tie group open at every segment's start -------------------------------------
 __global__ __launch_bounds__(COX_THREADS) void cox_segscan_kernel(CoxArgs a) {
     __shared__ PreS shp[COX_THREADS];
     __shared__ TieS sht[COX_THREADS];
     __shared__ int64_t shg[COX_THREADS];
     const int c = blockIdx.x;
+    if (c > a.p + 1) {
+        // TieS's operator on scaled sums: a segment with an end restarts the sum at its tail, any other adds all its event rows
+        __shared__ TcS shc[COX_THREADS];
+        const int cc = c - a.p - 2;
+        const double* V = a.tailV + (int64_t)cc * a.ld;
+        double* P = a.tcV + (int64_t)cc * a.ld;
+        seg_scan<TcS>(a.nseg, TcS{0, -INFINITY, 0.0},
+                      [&](int s) { return TcS{a.tie[s], a.segM[s], V[s]}; },
+                      [](TcS& x, const TcS& y) {
+                          if (y.f) { x.M = y.M; x.v = y.v; x.f = 1; }
+                          else pre_comb(x.M, x.v, y.M, y.v);
+                      },
+                      [&](int s, const TcS& e) { P[s] = e.v; if (cc == 0) a.tcM[s] = e.M; }, shc, false);
+        return;
+    }
     if (c <= a.p) {
         const double* V = a.segV + (int64_t)c * a.ld;
         double* P = a.preV + (int64_t)c * a.ld;
@@ -242,7 +309,10 @@ __global__ __launch_bounds__(COX_THREADS) void cox_segscan_kernel(CoxArgs a) {
     auto count = [&](int s) -> int64_t {
         if (!a.tie[s]) return 0;
         const int head = a.tie[a.ld + s], nend = a.tie[3 * a.ld + s];
-        return nend - (head > 0) + (head + a.carry[s] > 0);
+        int rows = nend - (head > 0) + (head + a.carry[s] > 0);
+        // Efron: a second A row for every group of two events or more (the first end's group counted with its carry)
+        if (a.ties) rows += a.tie2[s] - (head > 1) + (head + a.carry[s] > 1);
+        return rows;
     };
     seg_scan<int64_t>(a.nseg, (int64_t)0, count, [](int64_t& x, const int64_t& y) { x += y; },
                       [&](int s, const int64_t& e) { a.gidx[s] = e; }, shg, false);
@@ -254,7 +324,33 @@ __global__ __launch_bounds__(COX_THREADS) void cox_segscan_kernel(CoxArgs a) {
 }
 
 // ---- pass 3 ------------------------------------------------------------------------------------------------------------
-template <int NC, bool VEC>
+// Efron's sums over l = 0 .. d - 1 at a group end (d >= 2; s0, t0, d are the same in every lane): lane t takes l = t, t + 64, ..
+// in ascending order and one butterfly of fixed shape adds the 64 partials, so every lane holds the same bits.
+struct EfronSums { double h1, h2, slog, k0, k1, k2; };
+static __device__ __forceinline__ double wave_sum(double v) {
+    v = xor_add<32>(v); v = xor_add<16>(v); v = xor_add<8>(v); v = xor_add<4>(v); v = xor_add<2>(v);
+    return xor_add<1>(v);
+}
+static __device__ __forceinline__ EfronSums efron_sums(double s0, double t0, int d, int lane) {
+    EfronSums r{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const double dd = (double)d;
+    for (int l = lane; l < d; l += 64) {
+        const double f = (double)l / dd;
+        const double phi = s0 - f * t0;              // >= s0 / d: t0 <= s0 and f <= (d - 1) / d
+        const double ip = 1.0 / phi, fp = f * ip;
+        r.h1 += ip; r.h2 += fp; r.slog += log(phi);
+        r.k0 = fma(ip, ip, r.k0); r.k1 = fma(fp, ip, r.k1); r.k2 = fma(fp, fp, r.k2);
+    }
+    r.h1 = wave_sum(r.h1);
+    r.h2 = wave_sum(r.h2);
+    r.slog = wave_sum(r.slog);
+    r.k0 = wave_sum(r.k0);
+    r.k1 = wave_sum(r.k1);
+    r.k2 = wave_sum(r.k2);
+    return r;
+}
+
+template <int NC, bool VEC, bool EF>
 __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
     constexpr int RB = NC >= 8 ? 1 : COX_RB;
     const int lane = threadIdx.x & 63;
@@ -276,6 +372,22 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
     int open = a.carry[s];
     int64_t g = gs;
     double ll = 0.0, hq = 0.0, hv = 0.0;
+    // (EF) T0 / T1 of the open tie group under the same running max, and the (Q, h2) of the segment's first end
+    double t0 = 0.0, nq = 0.0, nv = 0.0;
+    double2 t1[EF ? NC : 1];
+    bool seen_end = false;
+    (void)t0; (void)t1; (void)nq; (void)nv; (void)seen_end;
+    if constexpr (EF) {
+        const double cM = a.tcM[s];
+        const double r = (cM == -INFINITY || M == -INFINITY) ? 0.0 : exp_neg(M - cM);     // (the prefix max covers the group's rows)
+        t0 = a.tcV[s] * r;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int col = c * 128 + 2 * lane;
+            t1[c].x = col < a.p ? a.tcV[(int64_t)(1 + col) * a.ld + s] * r : 0.0;
+            t1[c].y = col + 1 < a.p ? a.tcV[(int64_t)(2 + col) * a.ld + s] * r : 0.0;
+        }
+    }
     const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
     for (int64_t q0 = p0; q0 < p1; q0 += RB) {
         double2 x[RB][NC];
@@ -296,6 +408,11 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
                 s0 *= r;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) { s1[c].x *= r; s1[c].y *= r; }
+                if constexpr (EF) {
+                    t0 *= r;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { t1[c].x *= r; t1[c].y *= r; }
+                }
                 M = et;
             }
             const double e = exp_neg(M - et);
@@ -307,6 +424,11 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
             const bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
             if (ev) {
                 ++open;
+                if constexpr (EF) {
+                    t0 += e;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { t1[c].x = fma(e, x[i][c].x, t1[c].x); t1[c].y = fma(e, x[i][c].y, t1[c].y); }
+                }
                 if (own) {
                     ll += et;
 #pragma unroll
@@ -314,6 +436,66 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
                 }
             }
             double hzv = 0.0;
+            if constexpr (EF) {
+                double h2 = 0.0;
+                if (end && open > 0) {
+                    const double inv = 1.0 / s0;
+                    // d = 1: Breslow's terms; otherwise the sums over l and the Cholesky factor of K
+                    double h1 = inv, slog = 0.0, L11 = inv, L21 = 0.0, L22 = 0.0;
+                    if (open > 1) {
+                        const EfronSums es = efron_sums(s0, t0, open, lane);
+                        h1 = es.h1; h2 = es.h2; slog = es.slog;
+                        L11 = sqrt(es.k0);
+                        L21 = -es.k1 / L11;
+                        L22 = sqrt(fmax(es.k2 - L21 * L21, 0.0));
+                    } else if (own) {
+                        slog = log(s0);
+                    }
+                    if (own) {
+                        ll -= (double)open * M + slog;
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) {
+                            u[c].x = fma(-h1, s1[c].x, fma(h2, t1[c].x, u[c].x));
+                            u[c].y = fma(-h1, s1[c].y, fma(h2, t1[c].y, u[c].y));
+                        }
+                        hzv = h1;
+                        suf_comb(hq, hv, M, hzv);
+                    }
+                    if (g >= a.g0 && g < a.g0 + a.ca) {
+                        double* Ar = a.A + (g - a.g0) * a.lda;
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) {
+                            const int col = c * 128 + 2 * lane;
+                            if (col < a.p) Ar[col] = fma(L11, s1[c].x, L21 * t1[c].x);
+                            if (col + 1 < a.p) Ar[col + 1] = fma(L11, s1[c].y, L21 * t1[c].y);
+                        }
+                        if (lane == 0) a.dA[g - a.g0] = -1.0;
+                    }
+                    ++g;
+                    if (open > 1) {          // (the group's two rows may lie in different chunks)
+                        if (g >= a.g0 && g < a.g0 + a.ca) {
+                            double* Ar = a.A + (g - a.g0) * a.lda;
+#pragma unroll
+                            for (int c = 0; c < NC; ++c) {
+                                const int col = c * 128 + 2 * lane;
+                                if (col < a.p) Ar[col] = L22 * t1[c].x;
+                                if (col + 1 < a.p) Ar[col + 1] = L22 * t1[c].y;
+                            }
+                            if (lane == 0) a.dA[g - a.g0] = -1.0;
+                        }
+                        ++g;
+                    }
+                }
+                if (end) {
+                    open = 0;
+                    if (!seen_end) { seen_end = true; nq = M; nv = h2; }
+                    t0 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
+                }
+                if (own && lane == 0) { a.hzv[q] = hzv; a.hzq[q] = M; a.h2v[q] = end ? h2 : -1.0; }
+                continue;
+            }
             if (end && open > 0) {
                 const double d = (double)open;
                 const double inv = 1.0 / s0;
@@ -342,6 +524,9 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
     }
     if (!own) return;
     if (lane == 0) { a.segLL[s] = ll; a.segHq[s] = hq; a.segHv[s] = hv; }
+    if constexpr (EF) {
+        if (lane == 0) { a.segNq[s] = nq; a.segNv[s] = nv; }
+    }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int col = c * 128 + 2 * lane;
@@ -351,9 +536,19 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
 }
 
 // ---- pass 4: suffix of d / S0 over segments (block 0) and the column sums of loglik / U (blocks 1 ..) ------------------
+// Efron: block p + 2: the (Q, h2) of the first group end after every segment.
 __global__ __launch_bounds__(COX_THREADS) void cox_finish_kernel(CoxArgs a, double* g, double* loglik) {
     __shared__ PreS shp[COX_THREADS];
     __shared__ double red[COX_THREADS];
+    if ((int)blockIdx.x == a.p + 2) {
+        __shared__ TcS shc[COX_THREADS];
+        // walked from the last segment: the end met last is the nearest one
+        seg_scan<TcS>(a.nseg, TcS{0, 0.0, 0.0},
+                      [&](int s) { return TcS{a.tie[s], a.segNq[s], a.segNv[s]}; },
+                      [](TcS& x, const TcS& y) { if (y.f) x = y; },
+                      [&](int s, const TcS& e) { a.sufNq[s] = e.M; a.sufNv[s] = e.v; }, shc, true);
+        return;
+    }
     if (blockIdx.x == 0) {
         seg_scan<PreS>(a.nseg, PreS{0.0, 0.0},
                        [&](int s) { return PreS{a.segHq[s], a.segHv[s]}; },
@@ -379,16 +574,36 @@ __global__ __launch_bounds__(COX_THREADS) void cox_finish_kernel(CoxArgs a, doub
 }
 
 // ---- pass 5: w per position from the suffix of d / S0: one wave per segment, 64 positions per step, walked backwards ---
+// Efron: an event row also subtracts the h2 of its own group, which sits at the group's end at or after the row: the
+// nearest end is copied backwards through the 64 positions, then taken from the steps done before or from sufN.
+template <bool EF>
 __global__ __launch_bounds__(COX_THREADS) void cox_w_kernel(CoxArgs a) {
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * COX_WAVES + (threadIdx.x >> 6);
     if (s >= a.nseg) return;
     double cq = a.sufHq[s], cv = a.sufHv[s];          // everything after the segment
+    double nq = 0.0, nv = 0.0;
+    (void)nq; (void)nv;
+    if constexpr (EF) { nq = a.sufNq[s]; nv = a.sufNv[s]; }
     const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
     for (int64_t top = p1; top > p0; top -= 64) {
         const int64_t q = top - 64 + lane;
         const bool valid = q >= p0;
         double hq = valid ? a.hzq[q] : 0.0, hv = valid ? a.hzv[q] : 0.0;
+        double eq = hq, e2 = -1.0;
+        (void)eq; (void)e2;
+        if constexpr (EF) {
+            if (valid) e2 = a.h2v[q];
+            int have = e2 >= 0.0;
+#pragma unroll
+            for (int k = 1; k < 64; k <<= 1) {
+                const double oq = __shfl_down(eq, k, 64), o2 = __shfl_down(e2, k, 64);
+                const int oh = __shfl_down(have, k, 64);
+                if (lane + k < 64 && !have && oh) { eq = oq; e2 = o2; have = 1; }
+            }
+            if (!have) { eq = nq; e2 = nv; }
+            nq = __shfl(eq, 0, 64); nv = __shfl(e2, 0, 64);
+        }
         // inclusive suffix inside the 64 positions (lane l combines lanes >= l)
 #pragma unroll
         for (int k = 1; k < 64; k <<= 1) {
@@ -399,7 +614,10 @@ __global__ __launch_bounds__(COX_THREADS) void cox_w_kernel(CoxArgs a) {
         suf_comb(tq, tv, cq, cv);
         if (valid) {
             const double et = a.eta[q];
-            const double w = tv == 0.0 ? 0.0 : tv * exp_neg(tq - et);
+            double w = tv == 0.0 ? 0.0 : tv * exp_neg(tq - et);
+            if constexpr (EF) {
+                if (a.event[a.order[q]] != 0.0 && e2 > 0.0) w -= e2 * exp_neg(eq - et);      // (c >= h1 >= h2: w >= 0)
+            }
             if (a.w_out) a.w_out[q] = w;
             const int64_t rel = a.order[q] - a.vlo;
             if (rel >= 0 && rel % a.vstep == 0 && rel / a.vstep < a.vrows) a.wv[rel / a.vstep] = w;
@@ -438,10 +656,11 @@ __global__ void cox_fill_kernel(double* __restrict__ v, int64_t n, double val) {
 struct CoxLayout {
     int64_t L, nseg, ca, lda;
     size_t off_eta, off_hzv, off_hzq, off_segM, off_segV, off_preM, off_preV, off_tie, off_gidx, off_carry, off_segLL, off_segU,
-        off_segH, off_suf, off_A, off_dA, off_wv, off_misc, off_gram, total;
+        off_segH, off_suf, off_A, off_dA, off_wv, off_misc, off_gram, gram_bytes, total;
+    size_t off_h2v, off_tailV, off_tcM, off_tcV, off_tie2, off_segN, off_sufN;      // Efron only, after the Breslow layout
 };
 
-static CoxLayout cox_layout(int64_t max_rows, int p) {
+static CoxLayout cox_layout(int64_t max_rows, int p, int ties) {
     CoxLayout l{};
     const int64_t n = std::max<int64_t>(max_rows, 1);
     l.L = std::max<int64_t>(64, (n + COX_MAX_SEGS - 1) / COX_MAX_SEGS);
@@ -471,6 +690,16 @@ static CoxLayout cox_layout(int64_t max_rows, int p) {
     l.off_dA = take(8 * (size_t)l.ca);
     l.off_misc = take(256);
     l.off_gram = take(gram_workspace_bytes_impl(std::max<int64_t>(n, l.ca), p, 8));
+    l.gram_bytes = o - l.off_gram;
+    if (ties == DLSA_COX_TIES_EFRON) {
+        l.off_h2v = take(8 * (size_t)n);
+        l.off_tailV = take(8 * S * (size_t)(p + 1));
+        l.off_tcM = take(8 * S);
+        l.off_tcV = take(8 * S * (size_t)(p + 1));
+        l.off_tie2 = take(4 * S);
+        l.off_segN = take(8 * 2 * S);
+        l.off_sufN = take(8 * 2 * S);
+    }
     l.total = o;
     return l;
 }
@@ -479,25 +708,30 @@ static bool cox_vec_ok(const double* X, int64_t ldx, int p) {
     return (p % 2 == 0) && (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0);
 }
 
-template <int NC>
+template <int NC, bool EF>
 static void launch_rows(bool scan, bool vec, const CoxArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES));
     if (scan) {
-        if (vec) hipLaunchKernelGGL((cox_scan_kernel<NC, true>), grid, dim3(COX_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((cox_scan_kernel<NC, false>), grid, dim3(COX_THREADS), 0, s, a);
+        if (vec) hipLaunchKernelGGL((cox_scan_kernel<NC, true, EF>), grid, dim3(COX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((cox_scan_kernel<NC, false, EF>), grid, dim3(COX_THREADS), 0, s, a);
     } else {
-        if (vec) hipLaunchKernelGGL((cox_eta_kernel<NC, true>), grid, dim3(COX_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((cox_eta_kernel<NC, false>), grid, dim3(COX_THREADS), 0, s, a);
+        if (vec) hipLaunchKernelGGL((cox_eta_kernel<NC, true, EF>), grid, dim3(COX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((cox_eta_kernel<NC, false, EF>), grid, dim3(COX_THREADS), 0, s, a);
     }
+}
+template <bool EF>
+static void launch_rows_nc(bool scan, bool vec, const CoxArgs& a, hipStream_t s) {
+    const int nc = (a.p + 127) / 128;
+    if (nc <= 1) launch_rows<1, EF>(scan, vec, a, s);
+    else if (nc <= 2) launch_rows<2, EF>(scan, vec, a, s);
+    else if (nc <= 4) launch_rows<4, EF>(scan, vec, a, s);
+    else if (nc <= 8) launch_rows<8, EF>(scan, vec, a, s);
+    else launch_rows<16, EF>(scan, vec, a, s);
 }
 static int launch_row_pass(bool scan, const CoxArgs& a, hipStream_t s) {
     const bool vec = cox_vec_ok(a.X, a.ldx, a.p);
-    const int nc = (a.p + 127) / 128;
-    if (nc <= 1) launch_rows<1>(scan, vec, a, s);
-    else if (nc <= 2) launch_rows<2>(scan, vec, a, s);
-    else if (nc <= 4) launch_rows<4>(scan, vec, a, s);
-    else if (nc <= 8) launch_rows<8>(scan, vec, a, s);
-    else launch_rows<16>(scan, vec, a, s);
+    if (a.ties == DLSA_COX_TIES_EFRON) launch_rows_nc<true>(scan, vec, a, s);
+    else launch_rows_nc<false>(scan, vec, a, s);
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
@@ -515,9 +749,10 @@ static int cox_rows(const int64_t* order, int64_t n, int64_t* misc_dev, CoxRows*
     return DLSA_OK;
 }
 
-// One partition at a fixed beta: H (and g, loglik, w_out) as described at the top.  *D_out: number of event groups.
+// One partition at a fixed beta: H (and g, loglik, w_out) as described at the top.  *D_out: number of A rows (Breslow: the
+// event groups; Efron: one more for every group of two events or more; 0 = no event).
 static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
-                         int p, const CoxRows& rows, const double* beta, double* H, int64_t ldh, double* g, double* loglik,
+                         int p, int ties, const CoxRows& rows, const double* beta, double* H, int64_t ldh, double* g, double* loglik,
                          double* w_out, char* ws, const CoxLayout& l, int64_t* D_out, hipStream_t s) {
     CoxArgs a{};
     a.X = X; a.ldx = ldx; a.time = time; a.event = event; a.order = order; a.n = n; a.p = p; a.beta = beta;
@@ -531,13 +766,21 @@ static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const
     a.sufHq = (double*)(ws + l.off_suf); a.sufHv = a.sufHq + COX_MAX_SEGS;
     a.A = (double*)(ws + l.off_A); a.lda = l.lda; a.dA = (double*)(ws + l.off_dA); a.ca = l.ca;
     a.wv = (double*)(ws + l.off_wv); a.w_out = w_out;
+    a.ties = ties;
+    const bool efron = ties == DLSA_COX_TIES_EFRON;
+    if (efron) {
+        a.h2v = (double*)(ws + l.off_h2v); a.tailV = (double*)(ws + l.off_tailV);
+        a.tcM = (double*)(ws + l.off_tcM); a.tcV = (double*)(ws + l.off_tcV); a.tie2 = (int*)(ws + l.off_tie2);
+        a.segNq = (double*)(ws + l.off_segN); a.segNv = a.segNq + COX_MAX_SEGS;
+        a.sufNq = (double*)(ws + l.off_sufN); a.sufNv = a.sufNq + COX_MAX_SEGS;
+    }
     void* gws = ws + l.off_gram;
-    const size_t gws_bytes = l.total - l.off_gram;
+    const size_t gws_bytes = l.gram_bytes;
     int rc;
 
     rc = launch_row_pass(false, a, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(cox_segscan_kernel, dim3(p + 2), dim3(COX_THREADS), 0, s, a);
+    hipLaunchKernelGGL(cox_segscan_kernel, dim3(efron ? 2 * p + 3 : p + 2), dim3(COX_THREADS), 0, s, a);
     DLSA_HIP_CHECK(hipGetLastError());
     int64_t D = 0;
     DLSA_HIP_CHECK(hipMemcpyAsync(&D, a.gidx + a.nseg, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -556,7 +799,7 @@ static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const
             first = false;
         }
     }
-    hipLaunchKernelGGL(cox_finish_kernel, dim3(p + 2), dim3(COX_THREADS), 0, s, a, g, loglik);
+    hipLaunchKernelGGL(cox_finish_kernel, dim3(efron ? p + 3 : p + 2), dim3(COX_THREADS), 0, s, a, g, loglik);
     DLSA_HIP_CHECK(hipGetLastError());
     // w and the X-term Gram over views of the partition's rows
     const int64_t span = rows.step > 0 ? n : rows.hi - rows.lo + 1;
@@ -568,7 +811,9 @@ static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const
             DLSA_HIP_CHECK(hipGetLastError());
         }
         if (v0 > 0) a.w_out = nullptr;
-        hipLaunchKernelGGL(cox_w_kernel, dim3((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES)), dim3(COX_THREADS), 0, s, a);
+        const dim3 wgrid((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES));
+        if (efron) hipLaunchKernelGGL(cox_w_kernel<true>, wgrid, dim3(COX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(cox_w_kernel<false>, wgrid, dim3(COX_THREADS), 0, s, a);
         DLSA_HIP_CHECK(hipGetLastError());
         rc = gram_impl_f64(X + a.vlo * ldx, ldx * vstep, a.wv, a.vrows, p, H, ldh, first ? 0 : 1, gws, gws_bytes, s);
         if (rc) return rc;
@@ -589,21 +834,24 @@ static int cox_check_ws(void* ws, size_t ws_bytes, const CoxLayout& l) {
 
 extern "C" {
 
-size_t dlsa_cox_workspace_bytes(int64_t max_rows, int p) {
-    if (p <= 0 || p > 2048 || max_rows < 0) return 0;
+size_t dlsa_cox_ties_workspace_bytes(int64_t max_rows, int p, int ties) {
+    if (p <= 0 || p > 2048 || max_rows < 0 || (ties != DLSA_COX_TIES_BRESLOW && ties != DLSA_COX_TIES_EFRON)) return 0;
     // Newton state after the pass scratch: beta, prev, delta, g (p each), stats, the Cholesky factor (p x p)
-    return dlsa::align_up(dlsa::cox_layout(max_rows, p).total, 256) + dlsa::align_up(8 * (size_t)(4 * p + 8), 256) +
+    return dlsa::align_up(dlsa::cox_layout(max_rows, p, ties).total, 256) + dlsa::align_up(8 * (size_t)(4 * p + 8), 256) +
            dlsa::align_up(8 * (size_t)p * p, 256);
 }
 
-int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n, int p,
-                      const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes,
-                      void* stream) {
+size_t dlsa_cox_workspace_bytes(int64_t max_rows, int p) { return dlsa_cox_ties_workspace_bytes(max_rows, p, DLSA_COX_TIES_BRESLOW); }
+
+int dlsa_cox_pass_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
+                           int p, int ties, const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                           void* ws, size_t ws_bytes, void* stream) {
     using namespace dlsa;
     DLSA_REQUIRE(X && time && event && order && beta && H, "cox_pass: null argument");
     DLSA_REQUIRE(n >= 1 && p > 0 && p <= 2048 && ldx >= p && ldh >= p, "cox_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
                  (long long)n, p, (long long)ldx, (long long)ldh);
-    const CoxLayout l = cox_layout(n, p);
+    DLSA_REQUIRE(ties == DLSA_COX_TIES_BRESLOW || ties == DLSA_COX_TIES_EFRON, "cox_pass: unknown ties method %d", ties);
+    const CoxLayout l = cox_layout(n, p, ties);
     int rc = cox_check_ws(ws, ws_bytes, l);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -611,24 +859,32 @@ int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const do
     rc = cox_rows(order, n, (int64_t*)((char*)ws + l.off_misc), &rows, s);
     if (rc) return rc;
     int64_t D = 0;
-    return cox_pass_impl(X, ldx, time, event, order, n, p, rows, beta, H, ldh, g, loglik, w_out, (char*)ws, l, &D, s);
+    return cox_pass_impl(X, ldx, time, event, order, n, p, ties, rows, beta, H, ldh, g, loglik, w_out, (char*)ws, l, &D, s);
 }
 
-int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
-                     const int64_t* part_offsets_host, int K, int p, double tol, int max_iter, double* coef, double* Sig_inv,
-                     double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws, size_t ws_bytes,
-                     void* stream) {
+int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n, int p,
+                      const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes,
+                      void* stream) {
+    return dlsa_cox_pass_ties_f64(X, ldx, time, event, order, n, p, DLSA_COX_TIES_BRESLOW, beta, H, ldh, g, loglik, w_out, ws, ws_bytes,
+                                  stream);
+}
+
+int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
+                          const int64_t* part_offsets_host, int K, int p, int ties, double tol, int max_iter, double* coef,
+                          double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws,
+                          size_t ws_bytes, void* stream) {
     using namespace dlsa;
     DLSA_REQUIRE(X && time && event && order && part_offsets_host && coef && Sig_inv && Sig_invMcoef, "cox_fit: null argument");
     DLSA_REQUIRE(K > 0 && p > 0 && p <= 2048 && ldx >= p, "cox_fit: bad shape K=%d p=%d ldx=%lld", K, p, (long long)ldx);
     DLSA_REQUIRE(max_iter > 0 && tol > 0, "cox_fit: bad tol/max_iter");
+    DLSA_REQUIRE(ties == DLSA_COX_TIES_BRESLOW || ties == DLSA_COX_TIES_EFRON, "cox_fit: unknown ties method %d", ties);
     int64_t max_rows = 0;
     for (int k = 0; k < K; ++k) {
         DLSA_REQUIRE(part_offsets_host[k] >= 0 && part_offsets_host[k + 1] >= part_offsets_host[k], "cox_fit: part_offsets must be non-decreasing from 0");
         max_rows = std::max(max_rows, part_offsets_host[k + 1] - part_offsets_host[k]);
     }
-    const CoxLayout l = cox_layout(max_rows, p);
-    const size_t need = dlsa_cox_workspace_bytes(max_rows, p);
+    const CoxLayout l = cox_layout(max_rows, p, ties);
+    const size_t need = dlsa_cox_ties_workspace_bytes(max_rows, p, ties);
     if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
         set_error("cox_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
         return DLSA_ERR_WORKSPACE;
@@ -662,7 +918,7 @@ int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const dou
             st_k = DLSA_PART_NOT_CONVERGED;
             for (int it = 0; it < max_iter + 1 && !done; ++it) {
                 int64_t D = 0;
-                rc = cox_pass_impl(X, ldx, time, event, ok, nk, p, rows, beta, Hk, p, g, stats + 3, nullptr, wsc, l, &D, s);
+                rc = cox_pass_impl(X, ldx, time, event, ok, nk, p, ties, rows, beta, Hk, p, g, stats + 3, nullptr, wsc, l, &D, s);
                 if (rc) return rc;
                 if (D == 0) { st_k = DLSA_PART_EMPTY; break; }
                 rc = launch_chol_solve(Hk, p, 0, g, 0, beta, 0, p, 1, Lf, delta, 0, stats, 0, s, 0);
@@ -712,6 +968,14 @@ int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const dou
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;
+}
+
+int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
+                     const int64_t* part_offsets_host, int K, int p, double tol, int max_iter, double* coef, double* Sig_inv,
+                     double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws, size_t ws_bytes,
+                     void* stream) {
+    return dlsa_cox_fit_ties_f64(X, ldx, time, event, order, part_offsets_host, K, p, DLSA_COX_TIES_BRESLOW, tol, max_iter, coef, Sig_inv,
+                                 Sig_invMcoef, n_iter_host, status_host, loglik_host, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

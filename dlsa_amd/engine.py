@@ -681,10 +681,22 @@ def _cox_args(X, time, event, order):
     return X.shape[1]
 
 
-def cox_pass(X, time, event, order, beta, want_w=False):
-    """One Cox partition at a fixed beta (dlsa_cox_pass_f64): `order` [m] int64 holds the partition's absolute row indices
-    in DESCENDING time.  Returns (H [p,p] observed information, g [p] score, loglik [1] log partial likelihood,
-    w [m] or None -- the Breslow weights of the rows order[i])."""
+COX_TIES = {"breslow": 0, "efron": 1}      # include/dlsa_hip.h: DLSA_COX_TIES_*
+
+
+def cox_ties(ties):
+    """The C ABI's code of a tie method name ("breslow" or "efron", any letter case); ValueError for anything else."""
+    code = COX_TIES.get(ties.lower()) if isinstance(ties, str) else None
+    if code is None:
+        raise ValueError("cox: ties must be 'breslow' or 'efron', got %r" % (ties,))
+    return code
+
+
+def cox_pass(X, time, event, order, beta, want_w=False, ties="breslow"):
+    """One Cox partition at a fixed beta (dlsa_cox_pass_ties_f64): `order` [m] int64 holds the partition's absolute row
+    indices in DESCENDING time.  ties: "breslow" or "efron".  Returns (H [p,p] observed information, g [p] score, loglik [1]
+    log partial likelihood, w [m] or None -- the weights of the rows order[i] in H's X'diag(w)X term), all of the chosen method."""
+    code = cox_ties(ties)
     lib = _lib.load()
     p = _cox_args(X, time, event, order)
     _f64(beta, "beta")
@@ -696,15 +708,17 @@ def cox_pass(X, time, event, order, beta, want_w=False):
     g = torch.empty((p,), dtype=torch.float64, device=dev)
     ll = torch.empty((1,), dtype=torch.float64, device=dev)
     w = torch.empty((m,), dtype=torch.float64, device=dev) if want_w else None
-    ws = _workspace(lib.dlsa_cox_workspace_bytes(m, p), dev)
-    check(lib.dlsa_cox_pass_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), m, p, _ptr(beta), _ptr(H), p,
-                                _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
+    ws = _workspace(lib.dlsa_cox_ties_workspace_bytes(m, p, code), dev)
+    check(lib.dlsa_cox_pass_ties_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), m, p, code, _ptr(beta), _ptr(H), p,
+                                     _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
     return H, g, ll, w
 
 
-def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100):
-    """Per-partition Cox fit (dlsa_cox_fit_f64): partition k = rows order[off[k]:off[k+1]] (each segment in descending
-    time).  Same result dict as irls_fit; `loglik` holds the log partial likelihood at coef."""
+def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100, ties="breslow"):
+    """Per-partition Cox fit (dlsa_cox_fit_ties_f64): partition k = rows order[off[k]:off[k+1]] (each segment in descending
+    time).  ties: "breslow" or "efron".  Same result dict as irls_fit; `loglik` holds the log partial likelihood of the chosen
+    method at coef."""
+    code = cox_ties(ties)
     lib = _lib.load()
     p = _cox_args(X, time, event, order)
     offs = [int(v) for v in part_offsets]
@@ -715,11 +729,11 @@ def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100):
     coef = torch.empty((K, p), dtype=torch.float64, device=dev)
     smc = torch.empty((K, p), dtype=torch.float64, device=dev)
     sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_cox_workspace_bytes(max(offs[k + 1] - offs[k] for k in range(K)), p), dev)
+    ws = _workspace(lib.dlsa_cox_ties_workspace_bytes(max(offs[k + 1] - offs[k] for k in range(K)), p, code), dev)
     c_offs = (ctypes.c_int64 * (K + 1))(*offs)
     n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    rc = lib.dlsa_cox_fit_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), c_offs, K, p, tol, max_iter,
-                              _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
+    rc = lib.dlsa_cox_fit_ties_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), c_offs, K, p, code, tol, max_iter,
+                                   _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
     if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
         check(rc)
     return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),

@@ -485,7 +485,7 @@ def linear_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_fa
 
 
 # ---------------------------------------------------------------------------------------------
-# Cox proportional-hazards map step (Breslow ties): the third model family the DLSA method names.  The local objective of
+# Cox proportional-hazards map step (Breslow ties by default, Efron's approximation on request): the third model family the DLSA method names.  The local objective of
 # partition k is its own partial likelihood with risk sets inside the partition (a Cox model stratified by partition with a
 # common beta); the block is coef = the partition's MLE, Sig_inv = the observed information there, Sig_invMcoef = Sig_inv coef,
 # so dlsa_mapred / dlsa apply unchanged.  No intercept (the partial likelihood does not identify one).
@@ -529,11 +529,13 @@ def cox_order(time, part_id):
     return o1[o2].contiguous()
 
 
-def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, names=None, tol=1e-13, max_iter=100):
+def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, names=None, tol=1e-13, max_iter=100, ties="breslow"):
     """Cox map step for the partitions of one device-resident shard: X [n, p] fp64 row-major, time [n], event [n] (nonzero =
     event) on the GPU.  Partitions as fit_logistic_partitions: `part_offsets` (K+1 ints, contiguous row ranges) or
     `partition_num` (partition_id = i % K).  The rows are read through a permutation (one stable device sort keyed on
-    (partition, -time)); nothing is copied.  Returns MappedBlocks with `loglik` = log partial likelihood per partition."""
+    (partition, -time)); nothing is copied.  ties: "breslow" (the default) or "efron" (the default of R's coxph, lifelines and
+    scikit-survival), any letter case.  Returns MappedBlocks with `loglik` = log partial likelihood of that method per partition."""
+    engine.cox_ties(ties)          # (a wrong name fails before any GPU work)
     if not X.is_cuda:
         raise RuntimeError("fit_cox_partitions runs on the GPU only (no CPU fallback)")
     if X.dtype != torch.float64:
@@ -559,21 +561,22 @@ def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, na
         offs.append(offs[-1] + int(c))
     if names is None:
         names = ["x" + str(i) for i in range(p)]
-    r = engine.cox_fit(X, time, event, order, offs, tol=tol, max_iter=max_iter)
+    r = engine.cox_fit(X, time, event, order, offs, tol=tol, max_iter=max_iter, ties=ties)
     return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
 
 
-def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_baseline=[], data_info=[]):
+def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_baseline=[], data_info=[], ties="breslow"):
     """Frame-level sibling of logistic_model / linear_model for survival data: one partition (a pandas frame) with a time
     and an event column.  Returns the p x (3+p) frame `par_id, coef, Sig_invMcoef, <features>`; a chunk that lacks an
-    expected dummy level returns the all-zero block with a warning, as logistic_model does."""
+    expected dummy level returns the all-zero block with a warning, as logistic_model does.  ties: as fit_cox_partitions."""
+    engine.cox_ties(ties)
     features_df = sample_df.drop(columns=[event_name])
     Xd, names = _device_design(features_df, time_name, False, dummy_info, dummy_factors_baseline, data_info)
     if Xd is None:
         return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
     td = torch.from_numpy(np.ascontiguousarray(sample_df[time_name].to_numpy(dtype=np.float64))).cuda()
     ed = torch.from_numpy(np.ascontiguousarray(sample_df[event_name].to_numpy(dtype=np.float64))).cuda()
-    mb = fit_cox_partitions(Xd, td, ed, names=names)
+    mb = fit_cox_partitions(Xd, td, ed, names=names, ties=ties)
     st = mb.status[0]
     if st == 1:
         warnings.warn("cox_model: Newton iterations did not converge (max_iter reached: monotone likelihood?)")

@@ -252,7 +252,7 @@ int dlsa_irls_fit_ex_f64(const double* X, int64_t ldx, const double* y, const in
                          double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                          double* loglik_host, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- Cox proportional-hazards map step (Breslow ties; the third model family of the DLSA method) ---------------------
+/* ---- Cox proportional-hazards map step (Breslow or Efron ties; the third model family of the DLSA method) ------------
  * One partition's objective is its own partial likelihood with risk sets inside the partition.  `order` (device, int64)
  * holds the partition's n absolute row indices of X / time / event in DESCENDING time; rows tied in time are detected by
  * comparing time at neighbouring positions.  event: 1.0 = event, 0.0 = censored.  No sorted copy of the rows is made.
@@ -260,8 +260,17 @@ int dlsa_irls_fit_ex_f64(const double* X, int64_t ldx, const double* y, const in
  * g = score (p, nullable), loglik = log partial likelihood (1, nullable), w_out (n, nullable: w of the row order[i]).
  * dlsa_cox_fit_f64: partition k = order[part_offsets[k] .. part_offsets[k+1]); Newton from beta = 0, step halving while
  * the likelihood drops, stop as dlsa_irls_fit_f64.  Outputs as dlsa_irls_fit_f64 (Sig_inv = H at coef); a partition
- * without rows or events is DLSA_PART_EMPTY with the all-zero block.  Workspace: dlsa_cox_workspace_bytes(max rows, p). */
+ * without rows or events is DLSA_PART_EMPTY with the all-zero block.  Workspace: dlsa_cox_workspace_bytes(max rows, p).
+ * Tied event times: the entries above use Breslow's method.  The *_ties entries take the method after p: DLSA_COX_TIES_BRESLOW
+ * (the entries above forward with it; same results bit for bit) or DLSA_COX_TIES_EFRON (Efron's approximation, the default of
+ * R's coxph: group i of d_i tied events contributes sum_l log(S0_i - (l / d_i) T0_i), l = 0 .. d_i - 1, with T0_i the sum
+ * over the group's event rows; H = X'diag(w)X minus at most two rank-one terms per group; loglik, g and w_out are those of
+ * the chosen method).  Any other value is DLSA_ERR_INVALID.      Workspace: dlsa_cox_ties_workspace_bytes(max rows, p, ties),
+ * which is dlsa_cox_workspace_bytes for Breslow, larger for Efron, 0 for an unknown method, and non-decreasing in max rows. */
+#define DLSA_COX_TIES_BRESLOW 0
+#define DLSA_COX_TIES_EFRON 1
 size_t dlsa_cox_workspace_bytes(int64_t max_rows, int p);
+size_t dlsa_cox_ties_workspace_bytes(int64_t max_rows, int p, int ties);
 int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n, int p,
                       const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
                       void* ws, size_t ws_bytes, void* stream);
@@ -269,6 +278,13 @@ int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const dou
                      const int64_t* part_offsets_host, int K, int p, double tol, int max_iter,
                      double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                      double* loglik_host, void* ws, size_t ws_bytes, void* stream);
+int dlsa_cox_pass_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
+                           int p, int ties, const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                           void* ws, size_t ws_bytes, void* stream);
+int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
+                          const int64_t* part_offsets_host, int K, int p, int ties, double tol, int max_iter,
+                          double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                          double* loglik_host, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Poisson regression map step (log link; the count-data family of the DLSA method) -------------------------------
  * y_i ~ Poisson(mu_i), log mu_i = eta_i = [1 | x_i]' beta + o_i.  intercept != 0: the implicit intercept is column 0 of a
