@@ -82,6 +82,12 @@ SIGNATURES = {
     "dlsa_cox_fit_ties_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_int, c_int, c_int, c_dbl, c_int,
                                       c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), c_vp, c_sz,
                                       c_vp]),
+    "dlsa_cox_strata_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_int]),
+    "dlsa_cox_pass_strata_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                         c_sz, c_vp]),
+    "dlsa_cox_fit_strata_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_int, c_int, c_int, c_dbl, c_int,
+                                        c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), c_vp, c_sz,
+                                        c_vp]),
     "dlsa_poisson_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
     "dlsa_poisson_pass_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "dlsa_poisson_fit_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_i64, c_int, c_int, c_int,

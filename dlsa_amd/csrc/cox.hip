@@ -36,6 +36,25 @@
 // Scaled sums: a prefix (M, v) stands for v exp(M) with M the max eta it covers, a suffix (Q, v) for v exp(-Q) with Q the
 // smallest group max it covers, so every exponential has a non-positive argument (no overflow at any eta range) and a
 // ratio never sees an underflowed denominator.
+//
+// Strata (a nullable int32 code per row; every row kernel and the w kernel carry them as the instantiation ST): one common
+// beta, one baseline hazard per stratum, so loglik, U and H are the sums over the strata of the quantities above on each
+// stratum's rows.  `order` lists the partition's rows grouped by stratum, descending time inside each; position q STARTS a
+// stratum when the codes of positions q and q - 1 differ (only equality of neighbours is read; position 0 needs no flag).
+// One byte per position holds that flag, written once per partition next to cox_rows (`order` does not change between
+// Newton iterations), so the three walks read it coalesced instead of gathering two codes per position each.  Every running
+// quantity restarts at a flagged position:
+//   1 eta pass   a tie group also ends where the next position starts a stratum; (M, s0, s1) restart from empty before the
+//                row is added, so the segment emits the sums since its last stratum start, and the flag "holds a start";
+//   2 segscan    a flagged segment replaces the (M, v) accumulator instead of combining with it (TcS's operator); the open
+//                tie group's T carry restarts at a segment with an end or a start;
+//   3 scan pass  the same restart inside the walk; the segment emits the (Q, v) total of its ends BEFORE its first start;
+//   4 finish     walking from the right, a flagged segment replaces the hazard accumulator with that head total;
+//   5 w pass     the 64-lane suffix is segmented (lane l absorbs lanes below the first flagged lane above l) and the carry
+//                of the steps already done is dropped once a start lies between them and the lane.
+// M restarts per stratum, so a prefix (M, v) and a suffix (Q, v) only ever cover rows and group ends of one stratum: Q is
+// the smallest group max among ends of the row's own stratum at or after the row, each such max covers the row's eta, and
+// "every exponent <= 0" holds stratum by stratum.  A stratum without events has hazard 0 at all its ends and adds nothing.
 #include "common.h"
 #include <math.h>
 #include <algorithm>
@@ -122,6 +141,9 @@ struct CoxArgs {
     double* h2v;                     // [n] h2 at group ends as (hzq, v); -1 at every other position
     double* segNq; double* segNv;    // [nseg] (Q, h2) of the segment's first end
     double* sufNq; double* sufNv;    // [nseg] (Q, h2) of the first end after the segment
+    // strata only (appended); with them segHq / segHv hold the total of the segment's ends before its first stratum start
+    const unsigned char* sflag;      // [n] per position: 1 = the position starts a stratum (position 0: 0); null = unstratified
+    int* sst;                        // [nseg]: the segment holds a stratum start
 };
 
 // ---- pass 1 ----------------------------------------------------------------------------------------------------------
@@ -133,7 +155,7 @@ __device__ __forceinline__ void bcast_rows(double v, double (&out)[RB]) {
     }
 }
 
-template <int NC, bool VEC, bool EF>
+template <int NC, bool VEC, bool EF, bool ST>
 __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
     constexpr int RB = NC >= 8 ? 1 : COX_RB;        // (wide rows: one row per step keeps the row registers from spilling)
     const int lane = threadIdx.x & 63;
@@ -151,8 +173,8 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
     int has_end = 0, head = 0, tail = 0, nend = 0;
     double t0 = 0.0;                                // (EF) the sums over the event rows of the open tie group
     double2 t1[EF ? NC : 1];
-    int nend2 = 0;
-    (void)t0; (void)t1; (void)nend2;
+    int nend2 = 0, has_start = 0;
+    (void)t0; (void)t1; (void)nend2; (void)has_start;
     if constexpr (EF) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
@@ -183,6 +205,14 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
             const int64_t q = q0 + i;
             if (q >= p1) break;
             const double et = e_r[i];
+            if constexpr (ST) {
+                if (a.sflag[q]) {                               // a new stratum: empty sums (the open tie group closed at q - 1)
+                    has_start = 1;
+                    M = -INFINITY; s0 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { s1[c].x = 0.0; s1[c].y = 0.0; }
+                }
+            }
             if (et > M) {                                       // wave-uniform: rescale the running sums to the new max
                 const double r = M == -INFINITY ? 0.0 : exp_neg(et - M);
                 s0 *= r;
@@ -201,7 +231,8 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
             for (int c = 0; c < NC; ++c) { s1[c].x = fma(e, x[i][c].x, s1[c].x); s1[c].y = fma(e, x[i][c].y, s1[c].y); }
             const int64_t r = a.order[q];
             const int ev = a.event[r] != 0.0;
-            const bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
+            bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
+            if constexpr (ST) end = end || a.sflag[q + 1];      // (equal times on the two sides of a boundary are not tied)
             tail += ev;
             if constexpr (EF) {
                 if (ev) {
@@ -229,6 +260,7 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
         a.segV[s] = s0;
         a.tie[s] = has_end; a.tie[a.ld + s] = head; a.tie[2 * a.ld + s] = tail; a.tie[3 * a.ld + s] = nend;
         if constexpr (EF) { a.tie2[s] = nend2; a.tailV[s] = t0; }
+        if constexpr (ST) a.sst[s] = has_start;
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -267,7 +299,17 @@ __device__ void seg_scan(int nseg, State ident, Load load, Comb comb, Store stor
 
 struct PreS { double M, v; };
 struct TieS { int f, c; };
-struct TcS { int f; double M, v; };     // (Efron) a scaled sum that a segment with a group end restarts
+struct TcS { int f; double M, v; };     // a scaled sum that a flagged segment restarts (Efron's T carry; strata: prefix and hazard suffix)
+// the restart operator: a flagged segment replaces the accumulator, any other combines with it (associative: a range of
+// segments is flagged when any of them is, and then holds the sum from its last flagged segment on)
+static __device__ __forceinline__ void tcs_restart_pre(TcS& x, const TcS& y) {
+    if (y.f) { x.M = y.M; x.v = y.v; x.f = 1; }
+    else pre_comb(x.M, x.v, y.M, y.v);
+}
+static __device__ __forceinline__ void tcs_restart_suf(TcS& x, const TcS& y) {
+    if (y.f) { x.M = y.M; x.v = y.v; x.f = 1; }
+    else suf_comb(x.M, x.v, y.M, y.v);
+}
 
 // ---- pass 2: blocks 0 .. p: prefix of column (S0, S1_c); block p + 1: tie groups and A-row indices; Efron: blocks
 // p + 2 .. 2 p + 2: column (T0, T1_c) of the tie group open at every segment's start -------------------------------------
@@ -275,25 +317,32 @@ __global__ __launch_bounds__(COX_THREADS) void cox_segscan_kernel(CoxArgs a) {
     __shared__ PreS shp[COX_THREADS];
     __shared__ TieS sht[COX_THREADS];
     __shared__ int64_t shg[COX_THREADS];
+    __shared__ TcS shc[COX_THREADS];
     const int c = blockIdx.x;
     if (c > a.p + 1) {
         // TieS's operator on scaled sums: a segment with an end restarts the sum at its tail, any other adds all its event rows
-        __shared__ TcS shc[COX_THREADS];
         const int cc = c - a.p - 2;
         const double* V = a.tailV + (int64_t)cc * a.ld;
         double* P = a.tcV + (int64_t)cc * a.ld;
         seg_scan<TcS>(a.nseg, TcS{0, -INFINITY, 0.0},
-                      [&](int s) { return TcS{a.tie[s], a.segM[s], V[s]}; },
-                      [](TcS& x, const TcS& y) {
-                          if (y.f) { x.M = y.M; x.v = y.v; x.f = 1; }
-                          else pre_comb(x.M, x.v, y.M, y.v);
-                      },
+                      // (strata: a segment that starts a stratum at its first position may hold no end, and restarts the group too)
+                      [&](int s) { return TcS{a.tie[s] | (a.sflag ? a.sst[s] : 0), a.segM[s], V[s]}; },
+                      [](TcS& x, const TcS& y) { tcs_restart_pre(x, y); },
                       [&](int s, const TcS& e) { P[s] = e.v; if (cc == 0) a.tcM[s] = e.M; }, shc, false);
         return;
     }
     if (c <= a.p) {
         const double* V = a.segV + (int64_t)c * a.ld;
         double* P = a.preV + (int64_t)c * a.ld;
+        if (a.sflag) {
+            // strata: a segment with a stratum start replaces the prefix (its sums run from its last start); the prefix of a
+            // segment whose first position starts a stratum may hold anything, the walk restarts there
+            seg_scan<TcS>(a.nseg, TcS{0, -INFINITY, 0.0},
+                          [&](int s) { return TcS{a.sst[s], a.segM[s], V[s]}; },
+                          [](TcS& x, const TcS& y) { tcs_restart_pre(x, y); },
+                          [&](int s, const TcS& e) { P[s] = e.v; if (c == 0) a.preM[s] = e.M; }, shc, false);
+            return;
+        }
         seg_scan<PreS>(a.nseg, PreS{-INFINITY, 0.0},
                        [&](int s) { return PreS{a.segM[s], V[s]}; },
                        [](PreS& x, const PreS& y) { pre_comb(x.M, x.v, y.M, y.v); },
@@ -350,7 +399,7 @@ static __device__ __forceinline__ EfronSums efron_sums(double s0, double t0, int
     return r;
 }
 
-template <int NC, bool VEC, bool EF>
+template <int NC, bool VEC, bool EF, bool ST>
 __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
     constexpr int RB = NC >= 8 ? 1 : COX_RB;
     const int lane = threadIdx.x & 63;
@@ -375,8 +424,8 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
     // (EF) T0 / T1 of the open tie group under the same running max, and the (Q, h2) of the segment's first end
     double t0 = 0.0, nq = 0.0, nv = 0.0;
     double2 t1[EF ? NC : 1];
-    bool seen_end = false;
-    (void)t0; (void)t1; (void)nq; (void)nv; (void)seen_end;
+    bool seen_end = false, seen_start = false;
+    (void)t0; (void)t1; (void)nq; (void)nv; (void)seen_end; (void)seen_start;
     if constexpr (EF) {
         const double cM = a.tcM[s];
         const double r = (cM == -INFINITY || M == -INFINITY) ? 0.0 : exp_neg(M - cM);     // (the prefix max covers the group's rows)
@@ -403,6 +452,19 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
             const int64_t q = q0 + i;
             if (q >= p1) break;
             const double et = a.eta[q];
+            if constexpr (ST) {
+                if (a.sflag[q]) {          // a new stratum: the prefix, the open group and its T sums start empty
+                    seen_start = true;
+                    M = -INFINITY; s0 = 0.0; open = 0;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) { s1[c].x = 0.0; s1[c].y = 0.0; }
+                    if constexpr (EF) {
+                        t0 = 0.0;
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
+                    }
+                }
+            }
             if (et > M) {
                 const double r = M == -INFINITY ? 0.0 : exp_neg(et - M);
                 s0 *= r;
@@ -421,7 +483,8 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
             for (int c = 0; c < NC; ++c) { s1[c].x = fma(e, x[i][c].x, s1[c].x); s1[c].y = fma(e, x[i][c].y, s1[c].y); }
             const int64_t r = a.order[q];
             const bool ev = a.event[r] != 0.0;
-            const bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
+            bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
+            if constexpr (ST) end = end || a.sflag[q + 1];
             if (ev) {
                 ++open;
                 if constexpr (EF) {
@@ -459,7 +522,7 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
                             u[c].y = fma(-h1, s1[c].y, fma(h2, t1[c].y, u[c].y));
                         }
                         hzv = h1;
-                        suf_comb(hq, hv, M, hzv);
+                        if (!ST || !seen_start) suf_comb(hq, hv, M, hzv);
                     }
                     if (g >= a.g0 && g < a.g0 + a.ca) {
                         double* Ar = a.A + (g - a.g0) * a.lda;
@@ -504,7 +567,7 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
 #pragma unroll
                     for (int c = 0; c < NC; ++c) { u[c].x = fma(-d * inv, s1[c].x, u[c].x); u[c].y = fma(-d * inv, s1[c].y, u[c].y); }
                     hzv = d * inv;
-                    suf_comb(hq, hv, M, hzv);      // (walked forward: the segment's total needs no order among its terms but a fixed one)
+                    if (!ST || !seen_start) suf_comb(hq, hv, M, hzv);      // (walked forward: the segment's total needs no order among its terms but a fixed one)
                 }
                 if (g >= a.g0 && g < a.g0 + a.ca) {
                     double* Ar = a.A + (g - a.g0) * a.lda;
@@ -540,13 +603,22 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
 __global__ __launch_bounds__(COX_THREADS) void cox_finish_kernel(CoxArgs a, double* g, double* loglik) {
     __shared__ PreS shp[COX_THREADS];
     __shared__ double red[COX_THREADS];
+    __shared__ TcS shc[COX_THREADS];
     if ((int)blockIdx.x == a.p + 2) {
-        __shared__ TcS shc[COX_THREADS];
         // walked from the last segment: the end met last is the nearest one
         seg_scan<TcS>(a.nseg, TcS{0, 0.0, 0.0},
                       [&](int s) { return TcS{a.tie[s], a.segNq[s], a.segNv[s]}; },
                       [](TcS& x, const TcS& y) { if (y.f) x = y; },
                       [&](int s, const TcS& e) { a.sufNq[s] = e.M; a.sufNv[s] = e.v; }, shc, true);
+        return;
+    }
+    if (blockIdx.x == 0 && a.sflag) {
+        // strata: segH is the total of the segment's ends before its first stratum start, which is all that the positions
+        // to its left may see of it and of everything after it
+        seg_scan<TcS>(a.nseg, TcS{0, 0.0, 0.0},
+                      [&](int s) { return TcS{a.sst[s], a.segHq[s], a.segHv[s]}; },
+                      [](TcS& x, const TcS& y) { tcs_restart_suf(x, y); },
+                      [&](int s, const TcS& e) { a.sufHq[s] = e.M; a.sufHv[s] = e.v; }, shc, true);
         return;
     }
     if (blockIdx.x == 0) {
@@ -576,7 +648,9 @@ __global__ __launch_bounds__(COX_THREADS) void cox_finish_kernel(CoxArgs a, doub
 // ---- pass 5: w per position from the suffix of d / S0: one wave per segment, 64 positions per step, walked backwards ---
 // Efron: an event row also subtracts the h2 of its own group, which sits at the group's end at or after the row: the
 // nearest end is copied backwards through the 64 positions, then taken from the steps done before or from sufN.
-template <bool EF>
+// Strata: the wave's 64 flags are one ballot; lane l's suffix stops below `bnd`, the first flagged lane above l (64 without
+// one), which is also the bound of every lane it absorbs from, and the carry counts only for the lanes with bnd = 64.
+template <bool EF, bool ST>
 __global__ __launch_bounds__(COX_THREADS) void cox_w_kernel(CoxArgs a) {
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * COX_WAVES + (threadIdx.x >> 6);
@@ -592,6 +666,15 @@ __global__ __launch_bounds__(COX_THREADS) void cox_w_kernel(CoxArgs a) {
         double hq = valid ? a.hzq[q] : 0.0, hv = valid ? a.hzv[q] : 0.0;
         double eq = hq, e2 = -1.0;
         (void)eq; (void)e2;
+        int bnd = 64;
+        bool start0 = false;       // the step's first position starts a stratum: nothing carries to the positions before it
+        (void)start0;
+        if constexpr (ST) {
+            const unsigned long long fm = __ballot(valid && a.sflag[q] != 0);
+            const unsigned long long above = (fm >> lane) >> 1;
+            if (above) bnd = lane + 1 + __builtin_ctzll(above);
+            start0 = fm & 1ull;
+        }
         if constexpr (EF) {
             if (valid) e2 = a.h2v[q];
             int have = e2 >= 0.0;
@@ -608,10 +691,10 @@ __global__ __launch_bounds__(COX_THREADS) void cox_w_kernel(CoxArgs a) {
 #pragma unroll
         for (int k = 1; k < 64; k <<= 1) {
             const double oq = __shfl_down(hq, k, 64), ov = __shfl_down(hv, k, 64);
-            if (lane + k < 64) suf_comb(hq, hv, oq, ov);
+            if (lane + k < bnd) suf_comb(hq, hv, oq, ov);
         }
         double tq = hq, tv = hv;
-        suf_comb(tq, tv, cq, cv);
+        if (bnd == 64) suf_comb(tq, tv, cq, cv);
         if (valid) {
             const double et = a.eta[q];
             double w = tv == 0.0 ? 0.0 : tv * exp_neg(tq - et);
@@ -623,6 +706,9 @@ __global__ __launch_bounds__(COX_THREADS) void cox_w_kernel(CoxArgs a) {
             if (rel >= 0 && rel % a.vstep == 0 && rel / a.vstep < a.vrows) a.wv[rel / a.vstep] = w;
         }
         cq = __shfl(tq, 0, 64); cv = __shfl(tv, 0, 64);
+        if constexpr (ST) {
+            if (start0) { cq = 0.0; cv = 0.0; }
+        }
     }
 }
 
@@ -647,6 +733,13 @@ __global__ __launch_bounds__(1024) void cox_layout_kernel(const int64_t* __restr
     if (threadIdx.x == 0) { out[0] = mn; out[1] = mx; out[2] = bad_sh ? 0 : step; }
 }
 
+// ---- strata: the flag byte of every position of a partition (once per partition, like the row layout) -------------------
+__global__ void cox_strata_flag_kernel(const int32_t* __restrict__ strata, const int64_t* __restrict__ order, int64_t n,
+                                       unsigned char* __restrict__ flag) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) flag[q] = q > 0 && strata[order[q]] != strata[order[q - 1]];
+}
+
 __global__ void cox_fill_kernel(double* __restrict__ v, int64_t n, double val) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) v[i] = val;
@@ -658,9 +751,10 @@ struct CoxLayout {
     size_t off_eta, off_hzv, off_hzq, off_segM, off_segV, off_preM, off_preV, off_tie, off_gidx, off_carry, off_segLL, off_segU,
         off_segH, off_suf, off_A, off_dA, off_wv, off_misc, off_gram, gram_bytes, total;
     size_t off_h2v, off_tailV, off_tcM, off_tcV, off_tie2, off_segN, off_sufN;      // Efron only, after the Breslow layout
+    size_t off_sflag, off_sst;                                                      // strata only, after both
 };
 
-static CoxLayout cox_layout(int64_t max_rows, int p, int ties) {
+static CoxLayout cox_layout(int64_t max_rows, int p, int ties, bool stratified = false) {
     CoxLayout l{};
     const int64_t n = std::max<int64_t>(max_rows, 1);
     l.L = std::max<int64_t>(64, (n + COX_MAX_SEGS - 1) / COX_MAX_SEGS);
@@ -700,6 +794,10 @@ static CoxLayout cox_layout(int64_t max_rows, int p, int ties) {
         l.off_segN = take(8 * 2 * S);
         l.off_sufN = take(8 * 2 * S);
     }
+    if (stratified) {
+        l.off_sflag = take((size_t)n);
+        l.off_sst = take(4 * S);
+    }
     l.total = o;
     return l;
 }
@@ -708,30 +806,36 @@ static bool cox_vec_ok(const double* X, int64_t ldx, int p) {
     return (p % 2 == 0) && (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0);
 }
 
-template <int NC, bool EF>
+template <int NC, bool EF, bool ST>
 static void launch_rows(bool scan, bool vec, const CoxArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES));
     if (scan) {
-        if (vec) hipLaunchKernelGGL((cox_scan_kernel<NC, true, EF>), grid, dim3(COX_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((cox_scan_kernel<NC, false, EF>), grid, dim3(COX_THREADS), 0, s, a);
+        if (vec) hipLaunchKernelGGL((cox_scan_kernel<NC, true, EF, ST>), grid, dim3(COX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((cox_scan_kernel<NC, false, EF, ST>), grid, dim3(COX_THREADS), 0, s, a);
     } else {
-        if (vec) hipLaunchKernelGGL((cox_eta_kernel<NC, true, EF>), grid, dim3(COX_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((cox_eta_kernel<NC, false, EF>), grid, dim3(COX_THREADS), 0, s, a);
+        if (vec) hipLaunchKernelGGL((cox_eta_kernel<NC, true, EF, ST>), grid, dim3(COX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((cox_eta_kernel<NC, false, EF, ST>), grid, dim3(COX_THREADS), 0, s, a);
     }
 }
-template <bool EF>
+template <bool EF, bool ST>
 static void launch_rows_nc(bool scan, bool vec, const CoxArgs& a, hipStream_t s) {
     const int nc = (a.p + 127) / 128;
-    if (nc <= 1) launch_rows<1, EF>(scan, vec, a, s);
-    else if (nc <= 2) launch_rows<2, EF>(scan, vec, a, s);
-    else if (nc <= 4) launch_rows<4, EF>(scan, vec, a, s);
-    else if (nc <= 8) launch_rows<8, EF>(scan, vec, a, s);
-    else launch_rows<16, EF>(scan, vec, a, s);
+    if (nc <= 1) launch_rows<1, EF, ST>(scan, vec, a, s);
+    else if (nc <= 2) launch_rows<2, EF, ST>(scan, vec, a, s);
+    else if (nc <= 4) launch_rows<4, EF, ST>(scan, vec, a, s);
+    else if (nc <= 8) launch_rows<8, EF, ST>(scan, vec, a, s);
+    else launch_rows<16, EF, ST>(scan, vec, a, s);
 }
 static int launch_row_pass(bool scan, const CoxArgs& a, hipStream_t s) {
     const bool vec = cox_vec_ok(a.X, a.ldx, a.p);
-    if (a.ties == DLSA_COX_TIES_EFRON) launch_rows_nc<true>(scan, vec, a, s);
-    else launch_rows_nc<false>(scan, vec, a, s);
+    const bool efron = a.ties == DLSA_COX_TIES_EFRON;
+    if (a.sflag) {
+        if (efron) launch_rows_nc<true, true>(scan, vec, a, s);
+        else launch_rows_nc<false, true>(scan, vec, a, s);
+    } else {
+        if (efron) launch_rows_nc<true, false>(scan, vec, a, s);
+        else launch_rows_nc<false, false>(scan, vec, a, s);
+    }
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
@@ -749,10 +853,19 @@ static int cox_rows(const int64_t* order, int64_t n, int64_t* misc_dev, CoxRows*
     return DLSA_OK;
 }
 
+// The stratum-start flags of a partition's positions (null strata: nothing to do, the pass runs unstratified).
+static int cox_strata_flags(const int32_t* strata, const int64_t* order, int64_t n, char* ws, const CoxLayout& l, hipStream_t s) {
+    if (!strata) return DLSA_OK;
+    hipLaunchKernelGGL(cox_strata_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, strata, order, n,
+                       (unsigned char*)(ws + l.off_sflag));
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
 // One partition at a fixed beta: H (and g, loglik, w_out) as described at the top.  *D_out: number of A rows (Breslow: the
 // event groups; Efron: one more for every group of two events or more; 0 = no event).
-static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
-                         int p, int ties, const CoxRows& rows, const double* beta, double* H, int64_t ldh, double* g, double* loglik,
+static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const double* event, bool stratified, const int64_t* order,
+                         int64_t n, int p, int ties, const CoxRows& rows, const double* beta, double* H, int64_t ldh, double* g, double* loglik,
                          double* w_out, char* ws, const CoxLayout& l, int64_t* D_out, hipStream_t s) {
     CoxArgs a{};
     a.X = X; a.ldx = ldx; a.time = time; a.event = event; a.order = order; a.n = n; a.p = p; a.beta = beta;
@@ -774,6 +887,7 @@ static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const
         a.segNq = (double*)(ws + l.off_segN); a.segNv = a.segNq + COX_MAX_SEGS;
         a.sufNq = (double*)(ws + l.off_sufN); a.sufNv = a.sufNq + COX_MAX_SEGS;
     }
+    if (stratified) { a.sflag = (const unsigned char*)(ws + l.off_sflag); a.sst = (int*)(ws + l.off_sst); }      // (flags: cox_strata_flags)
     void* gws = ws + l.off_gram;
     const size_t gws_bytes = l.gram_bytes;
     int rc;
@@ -812,8 +926,13 @@ static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const
         }
         if (v0 > 0) a.w_out = nullptr;
         const dim3 wgrid((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES));
-        if (efron) hipLaunchKernelGGL(cox_w_kernel<true>, wgrid, dim3(COX_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(cox_w_kernel<false>, wgrid, dim3(COX_THREADS), 0, s, a);
+        if (stratified) {
+            if (efron) hipLaunchKernelGGL((cox_w_kernel<true, true>), wgrid, dim3(COX_THREADS), 0, s, a);
+            else hipLaunchKernelGGL((cox_w_kernel<false, true>), wgrid, dim3(COX_THREADS), 0, s, a);
+        } else {
+            if (efron) hipLaunchKernelGGL((cox_w_kernel<true, false>), wgrid, dim3(COX_THREADS), 0, s, a);
+            else hipLaunchKernelGGL((cox_w_kernel<false, false>), wgrid, dim3(COX_THREADS), 0, s, a);
+        }
         DLSA_HIP_CHECK(hipGetLastError());
         rc = gram_impl_f64(X + a.vlo * ldx, ldx * vstep, a.wv, a.vrows, p, H, ldh, first ? 0 : 1, gws, gws_bytes, s);
         if (rc) return rc;
@@ -834,32 +953,44 @@ static int cox_check_ws(void* ws, size_t ws_bytes, const CoxLayout& l) {
 
 extern "C" {
 
-size_t dlsa_cox_ties_workspace_bytes(int64_t max_rows, int p, int ties) {
+size_t dlsa_cox_strata_workspace_bytes(int64_t max_rows, int p, int ties, int stratified) {
     if (p <= 0 || p > 2048 || max_rows < 0 || (ties != DLSA_COX_TIES_BRESLOW && ties != DLSA_COX_TIES_EFRON)) return 0;
+    if (stratified != 0 && stratified != 1) return 0;
     // Newton state after the pass scratch: beta, prev, delta, g (p each), stats, the Cholesky factor (p x p)
-    return dlsa::align_up(dlsa::cox_layout(max_rows, p, ties).total, 256) + dlsa::align_up(8 * (size_t)(4 * p + 8), 256) +
+    return dlsa::align_up(dlsa::cox_layout(max_rows, p, ties, stratified != 0).total, 256) + dlsa::align_up(8 * (size_t)(4 * p + 8), 256) +
            dlsa::align_up(8 * (size_t)p * p, 256);
 }
 
+size_t dlsa_cox_ties_workspace_bytes(int64_t max_rows, int p, int ties) { return dlsa_cox_strata_workspace_bytes(max_rows, p, ties, 0); }
+
 size_t dlsa_cox_workspace_bytes(int64_t max_rows, int p) { return dlsa_cox_ties_workspace_bytes(max_rows, p, DLSA_COX_TIES_BRESLOW); }
 
-int dlsa_cox_pass_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
-                           int p, int ties, const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
-                           void* ws, size_t ws_bytes, void* stream) {
+int dlsa_cox_pass_strata_f64(const double* X, int64_t ldx, const double* time, const double* event, const int32_t* strata,
+                             const int64_t* order, int64_t n, int p, int ties, const double* beta, double* H, int64_t ldh, double* g,
+                             double* loglik, double* w_out, void* ws, size_t ws_bytes, void* stream) {
     using namespace dlsa;
     DLSA_REQUIRE(X && time && event && order && beta && H, "cox_pass: null argument");
     DLSA_REQUIRE(n >= 1 && p > 0 && p <= 2048 && ldx >= p && ldh >= p, "cox_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
                  (long long)n, p, (long long)ldx, (long long)ldh);
     DLSA_REQUIRE(ties == DLSA_COX_TIES_BRESLOW || ties == DLSA_COX_TIES_EFRON, "cox_pass: unknown ties method %d", ties);
-    const CoxLayout l = cox_layout(n, p, ties);
+    const CoxLayout l = cox_layout(n, p, ties, strata != nullptr);
     int rc = cox_check_ws(ws, ws_bytes, l);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     CoxRows rows;
     rc = cox_rows(order, n, (int64_t*)((char*)ws + l.off_misc), &rows, s);
     if (rc) return rc;
+    rc = cox_strata_flags(strata, order, n, (char*)ws, l, s);
+    if (rc) return rc;
     int64_t D = 0;
-    return cox_pass_impl(X, ldx, time, event, order, n, p, ties, rows, beta, H, ldh, g, loglik, w_out, (char*)ws, l, &D, s);
+    return cox_pass_impl(X, ldx, time, event, strata != nullptr, order, n, p, ties, rows, beta, H, ldh, g, loglik, w_out, (char*)ws, l, &D,
+                         s);
+}
+
+int dlsa_cox_pass_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
+                           int p, int ties, const double* beta, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                           void* ws, size_t ws_bytes, void* stream) {
+    return dlsa_cox_pass_strata_f64(X, ldx, time, event, nullptr, order, n, p, ties, beta, H, ldh, g, loglik, w_out, ws, ws_bytes, stream);
 }
 
 int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n, int p,
@@ -869,10 +1000,10 @@ int dlsa_cox_pass_f64(const double* X, int64_t ldx, const double* time, const do
                                   stream);
 }
 
-int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
-                          const int64_t* part_offsets_host, int K, int p, int ties, double tol, int max_iter, double* coef,
-                          double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws,
-                          size_t ws_bytes, void* stream) {
+int dlsa_cox_fit_strata_f64(const double* X, int64_t ldx, const double* time, const double* event, const int32_t* strata,
+                            const int64_t* order, const int64_t* part_offsets_host, int K, int p, int ties, double tol, int max_iter,
+                            double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
+                            void* ws, size_t ws_bytes, void* stream) {
     using namespace dlsa;
     DLSA_REQUIRE(X && time && event && order && part_offsets_host && coef && Sig_inv && Sig_invMcoef, "cox_fit: null argument");
     DLSA_REQUIRE(K > 0 && p > 0 && p <= 2048 && ldx >= p, "cox_fit: bad shape K=%d p=%d ldx=%lld", K, p, (long long)ldx);
@@ -883,8 +1014,9 @@ int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, cons
         DLSA_REQUIRE(part_offsets_host[k] >= 0 && part_offsets_host[k + 1] >= part_offsets_host[k], "cox_fit: part_offsets must be non-decreasing from 0");
         max_rows = std::max(max_rows, part_offsets_host[k + 1] - part_offsets_host[k]);
     }
-    const CoxLayout l = cox_layout(max_rows, p, ties);
-    const size_t need = dlsa_cox_ties_workspace_bytes(max_rows, p, ties);
+    const bool stratified = strata != nullptr;
+    const CoxLayout l = cox_layout(max_rows, p, ties, stratified);
+    const size_t need = dlsa_cox_strata_workspace_bytes(max_rows, p, ties, stratified ? 1 : 0);
     if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
         set_error("cox_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
         return DLSA_ERR_WORKSPACE;
@@ -911,6 +1043,8 @@ int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, cons
             CoxRows rows;
             int rc = cox_rows(ok, nk, (int64_t*)(wsc + l.off_misc), &rows, s);
             if (rc) return rc;
+            rc = cox_strata_flags(strata, ok, nk, wsc, l, s);
+            if (rc) return rc;
             DLSA_HIP_CHECK(hipMemsetAsync(beta, 0, (size_t)p * sizeof(double), s));
             double ll_prev = -INFINITY;
             bool have_prev = false, done = false;
@@ -918,7 +1052,7 @@ int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, cons
             st_k = DLSA_PART_NOT_CONVERGED;
             for (int it = 0; it < max_iter + 1 && !done; ++it) {
                 int64_t D = 0;
-                rc = cox_pass_impl(X, ldx, time, event, ok, nk, p, ties, rows, beta, Hk, p, g, stats + 3, nullptr, wsc, l, &D, s);
+                rc = cox_pass_impl(X, ldx, time, event, stratified, ok, nk, p, ties, rows, beta, Hk, p, g, stats + 3, nullptr, wsc, l, &D, s);
                 if (rc) return rc;
                 if (D == 0) { st_k = DLSA_PART_EMPTY; break; }
                 rc = launch_chol_solve(Hk, p, 0, g, 0, beta, 0, p, 1, Lf, delta, 0, stats, 0, s, 0);
@@ -968,6 +1102,14 @@ int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, cons
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;
+}
+
+int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,
+                          const int64_t* part_offsets_host, int K, int p, int ties, double tol, int max_iter, double* coef,
+                          double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws,
+                          size_t ws_bytes, void* stream) {
+    return dlsa_cox_fit_strata_f64(X, ldx, time, event, nullptr, order, part_offsets_host, K, p, ties, tol, max_iter, coef, Sig_inv,
+                                   Sig_invMcoef, n_iter_host, status_host, loglik_host, ws, ws_bytes, stream);
 }
 
 int dlsa_cox_fit_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order,

@@ -692,13 +692,46 @@ def cox_ties(ties):
     return code
 
 
-def cox_pass(X, time, event, order, beta, want_w=False, ties="breslow"):
-    """One Cox partition at a fixed beta (dlsa_cox_pass_ties_f64): `order` [m] int64 holds the partition's absolute row
-    indices in DESCENDING time.  ties: "breslow" or "efron".  Returns (H [p,p] observed information, g [p] score, loglik [1]
-    log partial likelihood, w [m] or None -- the weights of the rows order[i] in H's X'diag(w)X term), all of the chosen method."""
+def cox_strata(strata, n):
+    """Argument check of the stratum codes, with no GPU work: None, or an integer tensor with one code per row of X.  TypeError
+    for anything but an integer tensor, ValueError for a wrong length.  Returns its argument."""
+    if strata is None:
+        return None
+    if not torch.is_tensor(strata) or strata.dtype.is_floating_point or strata.dtype.is_complex or strata.dtype == torch.bool:
+        raise TypeError("cox: strata must be an integer tensor of stratum codes, got %s"
+                        % (strata.dtype if torch.is_tensor(strata) else type(strata).__name__))
+    if strata.dim() != 1 or strata.numel() != n:
+        raise ValueError("cox: strata must have n = %d elements" % n)
+    return strata
+
+
+def cox_strata_codes(strata, device):
+    """The C ABI's form of checked stratum codes: contiguous int32 on X's device.  An int32 tensor passes as it is; any other
+    integer type is range-checked (one device reduction) and converted, so callers that loop convert once and pass the result."""
+    if strata is None:
+        return None
+    if strata.device != device:
+        raise RuntimeError("cox: strata must be on X's device %s, got %s" % (device, strata.device))
+    if strata.dtype != torch.int32:
+        # (only equality of codes is read; codes within int32 keep their value)
+        lo, hi = torch.aminmax(strata) if strata.numel() else (strata.new_zeros(()), strata.new_zeros(()))
+        if int(hi) > 2 ** 31 - 1 or int(lo) < -2 ** 31:
+            raise ValueError("cox: stratum codes must fit int32")
+        strata = strata.to(torch.int32)
+    return strata.contiguous()
+
+
+def cox_pass(X, time, event, order, beta, want_w=False, ties="breslow", strata=None):
+    """One Cox partition at a fixed beta (dlsa_cox_pass_strata_f64): `order` [m] int64 holds the partition's absolute row
+    indices in DESCENDING time.  ties: "breslow" or "efron".  strata: None, or an integer tensor with one stratum code per row
+    of X; `order` then lists the rows grouped by stratum, descending time inside each (models.cox_order), and every stratum
+    has its own baseline hazard.  Returns (H [p,p] observed information, g [p] score, loglik [1] log partial likelihood,
+    w [m] or None -- the weights of the rows order[i] in H's X'diag(w)X term), all of the chosen method."""
     code = cox_ties(ties)
+    cox_strata(strata, X.shape[0])
     lib = _lib.load()
     p = _cox_args(X, time, event, order)
+    strata = cox_strata_codes(strata, X.device)
     _f64(beta, "beta")
     m = order.numel()
     if m < 1 or beta.numel() != p:
@@ -708,19 +741,21 @@ def cox_pass(X, time, event, order, beta, want_w=False, ties="breslow"):
     g = torch.empty((p,), dtype=torch.float64, device=dev)
     ll = torch.empty((1,), dtype=torch.float64, device=dev)
     w = torch.empty((m,), dtype=torch.float64, device=dev) if want_w else None
-    ws = _workspace(lib.dlsa_cox_ties_workspace_bytes(m, p, code), dev)
-    check(lib.dlsa_cox_pass_ties_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), m, p, code, _ptr(beta), _ptr(H), p,
-                                     _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
+    ws = _workspace(lib.dlsa_cox_strata_workspace_bytes(m, p, code, 0 if strata is None else 1), dev)
+    check(lib.dlsa_cox_pass_strata_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(strata), _ptr(order), m, p, code, _ptr(beta),
+                                       _ptr(H), p, _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
     return H, g, ll, w
 
 
-def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100, ties="breslow"):
-    """Per-partition Cox fit (dlsa_cox_fit_ties_f64): partition k = rows order[off[k]:off[k+1]] (each segment in descending
-    time).  ties: "breslow" or "efron".  Same result dict as irls_fit; `loglik` holds the log partial likelihood of the chosen
-    method at coef."""
+def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100, ties="breslow", strata=None):
+    """Per-partition Cox fit (dlsa_cox_fit_strata_f64): partition k = rows order[off[k]:off[k+1]] (each segment in descending
+    time; with `strata`, as cox_pass: grouped by stratum, descending time inside each).  ties: "breslow" or "efron".  Same
+    result dict as irls_fit; `loglik` holds the log partial likelihood of the chosen method at coef."""
     code = cox_ties(ties)
+    cox_strata(strata, X.shape[0])
     lib = _lib.load()
     p = _cox_args(X, time, event, order)
+    strata = cox_strata_codes(strata, X.device)
     offs = [int(v) for v in part_offsets]
     K = len(offs) - 1
     if K < 1 or offs[0] != 0 or offs[-1] > order.numel() or any(offs[k + 1] < offs[k] for k in range(K)):
@@ -729,11 +764,12 @@ def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100, ties="
     coef = torch.empty((K, p), dtype=torch.float64, device=dev)
     smc = torch.empty((K, p), dtype=torch.float64, device=dev)
     sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_cox_ties_workspace_bytes(max(offs[k + 1] - offs[k] for k in range(K)), p, code), dev)
+    ws = _workspace(lib.dlsa_cox_strata_workspace_bytes(max(offs[k + 1] - offs[k] for k in range(K)), p, code, 0 if strata is None else 1),
+                    dev)
     c_offs = (ctypes.c_int64 * (K + 1))(*offs)
     n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    rc = lib.dlsa_cox_fit_ties_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(order), c_offs, K, p, code, tol, max_iter,
-                                   _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
+    rc = lib.dlsa_cox_fit_strata_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(strata), _ptr(order), c_offs, K, p, code, tol,
+                                     max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
     if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
         check(rc)
     return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),

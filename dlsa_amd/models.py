@@ -490,19 +490,29 @@ def linear_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_fa
 # common beta); the block is coef = the partition's MLE, Sig_inv = the observed information there, Sig_invMcoef = Sig_inv coef,
 # so dlsa_mapred / dlsa apply unchanged.  No intercept (the partial likelihood does not identify one).
 # ---------------------------------------------------------------------------------------------
-def simulate_cox(sample_size, p, partition_num, seed=20260101, censor_rate=0.3, tie_levels=None):
+def simulate_cox(sample_size, p, partition_num, seed=20260101, censor_rate=0.3, tie_levels=None, strata=None):
     """Seeded survival rows: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), hazard exp(x beta*) with beta* as
     in simulate_logistic (first int(0.4p) coefficients 1), event times T = E / exp(x beta*) with E ~ Exp(1), censoring times
     C ~ Exp(rate) with the rate that censors about `censor_rate` of the rows; time = min(T, C), event = T <= C.  tie_levels
     rounds the times onto that many quantile levels (heavy ties).  partition_id = i % partition_num.
-    Returns the frame partition_id, time, event, x0 .. x{p-1}."""
+    strata: an int S gives every row the stratum i // partition_num % S (every partition holds all S strata in equal shares)
+    and multiplies the event times of stratum s by 2 ** (s - (S - 1) / 2): a baseline hazard of its own per stratum, the same
+    beta*.  The column `stratum` then follows `event`.
+    Returns the frame partition_id, time, event, [stratum,] x0 .. x{p-1}."""
     n, p = int(sample_size), int(p)
+    if strata is not None and int(strata) < 1:
+        raise ValueError("simulate_cox: strata must be a positive number of strata, got %r" % (strata,))
     X, _ = engine.synth(seed, 0, n, p, labels=False)
     X = X.cpu().numpy()
     beta = np.zeros(p)
     beta[:int(0.4 * p)] = 1.0
     rng = np.random.default_rng(seed)
     T = rng.exponential(1.0, n) / np.exp(X @ beta)
+    stratum = None
+    if strata is not None:
+        S = int(strata)
+        stratum = np.arange(n) // int(partition_num) % S
+        T = T * 2.0 ** (stratum - (S - 1) / 2.0)
     if censor_rate > 0:
         # E[P(C < T)] = rate / (rate + h) for a hazard h; one scalar rate from the median hazard is close enough for a simulator
         h = float(np.median(np.exp(X @ beta))) if n else 1.0
@@ -516,26 +526,38 @@ def simulate_cox(sample_size, p, partition_num, seed=20260101, censor_rate=0.3, 
         q = np.quantile(time, np.linspace(0, 1, int(tie_levels) + 1)[1:])
         time = q[np.minimum(np.searchsorted(q, time), len(q) - 1)]
     pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    if stratum is not None:
+        data = np.concatenate((pid[:, None], time[:, None], event[:, None], stratum.astype(np.float64)[:, None], X), 1)
+        return pd.DataFrame(data, columns=["partition_id", "time", "event", "stratum"] + ["x" + str(i) for i in range(p)])
     data = np.concatenate((pid[:, None], time[:, None], event[:, None], X), 1)
     return pd.DataFrame(data, columns=["partition_id", "time", "event"] + ["x" + str(i) for i in range(p)])
 
 
-def cox_order(time, part_id):
-    """The row permutation the Cox kernels read: one stable device sort keyed on (partition, -time).  Returns (order int64,
-    rows per partition).  part_id: int64 tensor of partition indices 0 .. K-1."""
+def cox_order(time, part_id, strata=None):
+    """The row permutation the Cox kernels read: one stable device sort keyed on (partition, -time), or with `strata` (an
+    integer tensor of stratum codes per row) on (partition, stratum, -time).  Returns order int64.  part_id: int64 tensor of
+    partition indices 0 .. K-1."""
     # stable sort by -time first, then a stable sort by partition keeps the time order inside every partition
     o1 = torch.sort(-time, stable=True).indices
+    if strata is not None:
+        o1 = o1[torch.sort(strata[o1], stable=True).indices]
     o2 = torch.sort(part_id[o1], stable=True).indices
     return o1[o2].contiguous()
 
 
-def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, names=None, tol=1e-13, max_iter=100, ties="breslow"):
+def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, names=None, tol=1e-13, max_iter=100, ties="breslow",
+                       strata=None):
     """Cox map step for the partitions of one device-resident shard: X [n, p] fp64 row-major, time [n], event [n] (nonzero =
     event) on the GPU.  Partitions as fit_logistic_partitions: `part_offsets` (K+1 ints, contiguous row ranges) or
     `partition_num` (partition_id = i % K).  The rows are read through a permutation (one stable device sort keyed on
     (partition, -time)); nothing is copied.  ties: "breslow" (the default) or "efron" (the default of R's coxph, lifelines and
-    scikit-survival), any letter case.  Returns MappedBlocks with `loglik` = log partial likelihood of that method per partition."""
+    scikit-survival), any letter case.  strata: None, or an integer tensor [n] of stratum codes on X's device: one common
+    beta per partition and one baseline hazard per stratum (risk sets, tie groups and the cumulative hazard stop at stratum
+    boundaries).  The codes are global: a stratum that spans partitions forms a risk set of its own in each of them.  With one
+    event per stratum this is conditional logistic regression on matched sets.
+    Returns MappedBlocks with `loglik` = log partial likelihood of that method per partition."""
     engine.cox_ties(ties)          # (a wrong name fails before any GPU work)
+    engine.cox_strata(strata, X.shape[0])
     if not X.is_cuda:
         raise RuntimeError("fit_cox_partitions runs on the GPU only (no CPU fallback)")
     if X.dtype != torch.float64:
@@ -554,29 +576,41 @@ def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, na
             raise ValueError("fit_cox_partitions: part_offsets must run from 0 to n = %d" % n)
         pid = torch.repeat_interleave(torch.arange(K, device=X.device, dtype=torch.int64),
                                       torch.tensor([offs[k + 1] - offs[k] for k in range(K)], device=X.device))
-    order = cox_order(time, pid)
+    strata = engine.cox_strata_codes(strata, X.device)          # (once: cox_fit gets int32)
+    order = cox_order(time, pid, strata)
     counts = torch.bincount(pid, minlength=K).cpu().tolist()
     offs = [0]
     for c in counts:
         offs.append(offs[-1] + int(c))
     if names is None:
         names = ["x" + str(i) for i in range(p)]
-    r = engine.cox_fit(X, time, event, order, offs, tol=tol, max_iter=max_iter, ties=ties)
+    r = engine.cox_fit(X, time, event, order, offs, tol=tol, max_iter=max_iter, ties=ties, strata=strata)
     return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
 
 
-def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_baseline=[], data_info=[], ties="breslow"):
+def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_baseline=[], data_info=[], ties="breslow", strata=None):
     """Frame-level sibling of logistic_model / linear_model for survival data: one partition (a pandas frame) with a time
     and an event column.  Returns the p x (3+p) frame `par_id, coef, Sig_invMcoef, <features>`; a chunk that lacks an
-    expected dummy level returns the all-zero block with a warning, as logistic_model does.  ties: as fit_cox_partitions."""
+    expected dummy level returns the all-zero block with a warning, as logistic_model does.  ties: as fit_cox_partitions.
+    strata: a column name or a list of names; the distinct combinations of their values are the strata, and the columns are
+    no features (KeyError for a name the frame lacks)."""
     engine.cox_ties(ties)
+    codes = None
+    if strata is not None:
+        cols = [strata] if isinstance(strata, str) else list(strata)
+        missing = [c for c in cols if c not in sample_df.columns]
+        if missing or not cols:
+            raise KeyError("cox_model: strata column(s) %r not in the frame" % (missing,))
+        codes = sample_df.groupby(cols, sort=True, dropna=False).ngroup().to_numpy(dtype=np.int32)
+        sample_df = sample_df.drop(columns=cols)
     features_df = sample_df.drop(columns=[event_name])
     Xd, names = _device_design(features_df, time_name, False, dummy_info, dummy_factors_baseline, data_info)
     if Xd is None:
         return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
     td = torch.from_numpy(np.ascontiguousarray(sample_df[time_name].to_numpy(dtype=np.float64))).cuda()
     ed = torch.from_numpy(np.ascontiguousarray(sample_df[event_name].to_numpy(dtype=np.float64))).cuda()
-    mb = fit_cox_partitions(Xd, td, ed, names=names, ties=ties)
+    sd = torch.from_numpy(np.ascontiguousarray(codes)).cuda() if codes is not None else None
+    mb = fit_cox_partitions(Xd, td, ed, names=names, ties=ties, strata=sd)
     st = mb.status[0]
     if st == 1:
         warnings.warn("cox_model: Newton iterations did not converge (max_iter reached: monotone likelihood?)")

@@ -266,7 +266,18 @@ int dlsa_irls_fit_ex_f64(const double* X, int64_t ldx, const double* y, const in
  * R's coxph: group i of d_i tied events contributes sum_l log(S0_i - (l / d_i) T0_i), l = 0 .. d_i - 1, with T0_i the sum
  * over the group's event rows; H = X'diag(w)X minus at most two rank-one terms per group; loglik, g and w_out are those of
  * the chosen method).  Any other value is DLSA_ERR_INVALID.      Workspace: dlsa_cox_ties_workspace_bytes(max rows, p, ties),
- * which is dlsa_cox_workspace_bytes for Breslow, larger for Efron, 0 for an unknown method, and non-decreasing in max rows. */
+ * which is dlsa_cox_workspace_bytes for Breslow, larger for Efron, 0 for an unknown method, and non-decreasing in max rows.
+ * Strata: the *_strata entries are the *_ties entries with `strata` after event: one int32 code per row (device, indexed by
+ * absolute row like time and event; nullable).  One common beta, one baseline hazard per stratum: risk sets, tie groups and
+ * the cumulative hazard stop at stratum boundaries, and loglik, g and H are the sums over the strata.  Adjacency contract:
+ * `order` lists each partition's rows GROUPED BY STRATUM, in descending time inside each stratum, and the kernels compare the
+ * codes of neighbouring positions only (position q starts a stratum when strata[order[q]] != strata[order[q-1]]), as they do
+ * with time; only equality of codes matters (negative and non-dense codes are fine), and a code that reappears after another
+ * one is a new stratum.  A stratum without events contributes nothing; a partition with no event in any stratum is
+ * DLSA_PART_EMPTY.  strata = NULL is the unstratified model (the *_ties entries forward with it; same results bit for bit).
+ * Workspace: dlsa_cox_strata_workspace_bytes(max rows, p, ties, stratified), stratified = 1 when strata is passed: equal to
+ * dlsa_cox_ties_workspace_bytes for stratified = 0, never smaller for 1, 0 for any other value or an unknown method, and
+ * non-decreasing in max rows. */
 #define DLSA_COX_TIES_BRESLOW 0
 #define DLSA_COX_TIES_EFRON 1
 size_t dlsa_cox_workspace_bytes(int64_t max_rows, int p);
@@ -285,6 +296,14 @@ int dlsa_cox_fit_ties_f64(const double* X, int64_t ldx, const double* time, cons
                           const int64_t* part_offsets_host, int K, int p, int ties, double tol, int max_iter,
                           double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                           double* loglik_host, void* ws, size_t ws_bytes, void* stream);
+size_t dlsa_cox_strata_workspace_bytes(int64_t max_rows, int p, int ties, int stratified);
+int dlsa_cox_pass_strata_f64(const double* X, int64_t ldx, const double* time, const double* event, const int32_t* strata,
+                             const int64_t* order, int64_t n, int p, int ties, const double* beta, double* H, int64_t ldh, double* g,
+                             double* loglik, double* w_out, void* ws, size_t ws_bytes, void* stream);
+int dlsa_cox_fit_strata_f64(const double* X, int64_t ldx, const double* time, const double* event, const int32_t* strata,
+                            const int64_t* order, const int64_t* part_offsets_host, int K, int p, int ties, double tol, int max_iter,
+                            double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                            double* loglik_host, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Poisson regression map step (log link; the count-data family of the DLSA method) -------------------------------
  * y_i ~ Poisson(mu_i), log mu_i = eta_i = [1 | x_i]' beta + o_i.  intercept != 0: the implicit intercept is column 0 of a
