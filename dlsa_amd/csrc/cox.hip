@@ -28,8 +28,9 @@
 //   2 cox_segscan_kernel  exclusive prefix over segments, one workgroup per column (a block total is rescaled by its
 //                         max when combined), plus the open tie group entering every segment and the index of its
 //                         first event row of A;
-//   3 cox_scan_kernel     the segment re-walked from its prefix: A rows (a chunk of them per launch), the segment's
-//                         partials of loglik and U, and d_i / S0_i (Efron: h1_i, and h2_i beside it) at every group end;
+//   3 cox_scan_kernel     the segment re-walked from its prefix, with the recurrence of pass 1 (CoxRun, the one copy of it):
+//                         A rows (a chunk of them per launch), the segment's partials of loglik and U, and d_i / S0_i
+//                         (Efron: h1_i, and h2_i beside it) at every group end;
 //   4 cox_finish_kernel + cox_w_kernel: the suffix sum of d_i / S0_i (over segments, then inside each segment by wave
 //                         scans) and w; the column sums of the loglik and U partials;
 //   5 the two Grams: dlsa_gram_f64(A, -d) per chunk and dlsa_gram_f64(X, w) accumulated into H.
@@ -46,8 +47,9 @@
 // quantity restarts at a flagged position:
 //   1 eta pass   a tie group also ends where the next position starts a stratum; (M, s0, s1) restart from empty before the
 //                row is added, so the segment emits the sums since its last stratum start, and the flag "holds a start";
-//   2 segscan    a flagged segment replaces the (M, v) accumulator instead of combining with it (TcS's operator); the open
-//                tie group's T carry restarts at a segment with an end or a start;
+//   2 segscan    a flagged segment replaces the (M, v) accumulator instead of combining with it (TcS's operator; every
+//                caller runs this scan, without strata no segment is flagged); the open tie group's T carry restarts at a
+//                segment with an end or a start;
 //   3 scan pass  the same restart inside the walk; the segment emits the (Q, v) total of its ends BEFORE its first start;
 //   4 finish     walking from the right, a flagged segment replaces the hazard accumulator with that head total;
 //   5 w pass     the 64-lane suffix is segmented (lane l absorbs lanes below the first flagged lane above l) and the carry
@@ -58,7 +60,7 @@
 #include "common.h"
 #include <math.h>
 #include <algorithm>
-#include <vector>
+#include <type_traits>
 
 typedef double dlsa_cox_d2v __attribute__((ext_vector_type(2)));
 
@@ -115,35 +117,107 @@ static __device__ __forceinline__ void suf_comb(double& Q, double& v, double Qb,
     Q = Qn;
 }
 
+// One evaluation's kernel arguments, grouped by the pass that writes each array ((EF) / (ST): only allocated and touched under
+// Efron ties / with strata; cox_workspace below is the one list of the arrays, their sizes and their order in the workspace).
 struct CoxArgs {
+    // the problem
     const double* X; int64_t ldx;
     const double* time; const double* event; const int64_t* order;
-    int64_t n; int p; int64_t L; int nseg; int ld;      // ld: columns of the column-major segment arrays = nseg
+    int64_t n; int p; int ties;
     const double* beta;
-    double* eta;          // [n] per position
-    double* hzv; double* hzq;        // [n] d / S0 at event-group ends as (Q, v), v = 0 elsewhere
+    int64_t L; int nseg; int ld;     // segments of L positions; ld: columns of the column-major segment arrays = nseg
+    const unsigned char* sflag;      // (ST) [n] per position: 1 = the position starts a stratum (position 0: 0); null = unstratified
+    // pass 1 (eta)
+    double* eta;                     // [n] per position
     double* segM; double* segV;      // [nseg], [(p + 1) x nseg]: segment totals (col 0 = S0, 1 + c = S1_c)
-    double* preM; double* preV;      // exclusive prefixes, same layout
     int* tie;                        // [4 x nseg]: has_end, head events (up to the first end), tail events (after the last end), event ends
-    int64_t* gidx;                   // [nseg + 1]: first A-row index of each segment; gidx[nseg] = D
+    int* tie2;                       // (EF) [nseg]: ends of the segment whose own run holds two events or more
+    double* tailV;                   // (EF) [(p + 1) x nseg]: sums over the segment's event rows after its last end (all of them without one), scaled by segM
+    int* sst;                        // (ST) [nseg]: the segment holds a stratum start
+    // pass 2 (segment scan)
+    double* preM; double* preV;      // exclusive prefixes of segM / segV, same layout
+    double* tcM; double* tcV;        // (EF) [nseg], [(p + 1) x nseg]: T0 / T1 of the tie group open at the segment's start
     int* carry;                      // [nseg]: events of the tie group open at the segment's start
-    double* segLL; double* segU;     // [nseg], [p x nseg]
-    double* segHq; double* segHv;    // [nseg] segment totals of d / S0 as (Q, v)
-    double* sufHq; double* sufHv;    // [nseg] their exclusive suffix over the later segments
+    int64_t* gidx;                   // [nseg + 1]: first A-row index of each segment; gidx[nseg] = D
+    // pass 3 (scan), one launch per chunk of A rows
     double* A; int64_t lda; double* dA; int64_t g0; int64_t ca; int chunk; int nchunks;
+    double* hzv; double* hzq;        // [n] d / S0 (EF: h1) at event-group ends as (Q, v), v = 0 elsewhere
+    double* h2v;                     // (EF) [n] h2 at group ends as (hzq, v); -1 at every other position
+    double* segLL; double* segU;     // [nseg], [p x nseg]
+    double* segHq; double* segHv;    // [nseg] segment totals of d / S0 as (Q, v); (ST) of the segment's ends before its first stratum start
+    double* segNq; double* segNv;    // (EF) [nseg] (Q, h2) of the segment's first end
+    // pass 4 (finish, w)
+    double* sufHq; double* sufHv;    // [nseg] exclusive suffix of segH over the later segments
+    double* sufNq; double* sufNv;    // (EF) [nseg] (Q, h2) of the first end after the segment
     double* wv; int64_t vlo; int64_t vstep; int64_t vrows;      // Gram weights of the view rows [vlo + r vstep, r < vrows]
     double* w_out;                   // [n] per position, nullable
-    // Efron only (appended: the fields above keep their kernel-argument offsets)
-    int ties;
-    double* tailV;                   // [(p + 1) x nseg]: sums over the segment's event rows after its last end (all of them without one), scaled by segM
-    double* tcM; double* tcV;        // [nseg], [(p + 1) x nseg]: T0 / T1 of the tie group open at the segment's start
-    int* tie2;                       // [nseg]: ends of the segment whose own run holds two events or more
-    double* h2v;                     // [n] h2 at group ends as (hzq, v); -1 at every other position
-    double* segNq; double* segNv;    // [nseg] (Q, h2) of the segment's first end
-    double* sufNq; double* sufNv;    // [nseg] (Q, h2) of the first end after the segment
-    // strata only (appended); with them segHq / segHv hold the total of the segment's ends before its first stratum start
-    const unsigned char* sflag;      // [n] per position: 1 = the position starts a stratum (position 0: 0); null = unstratified
-    int* sst;                        // [nseg]: the segment holds a stratum start
+};
+
+// The lane's pair (col, col + 1) of segment s in a column-major segment array whose column `col` is row `row0 + col` (1 under
+// the S0 / T0 row of segV, preV, tailV, tcV; 0 in segU): a column at or beyond p loads as 0 and is not stored.
+static __device__ __forceinline__ double2 seg_ld2(const CoxArgs& a, const double* V, int row0, int col, int s) {
+    double2 r;
+    r.x = col < a.p ? V[(int64_t)(row0 + col) * a.ld + s] : 0.0;
+    r.y = col + 1 < a.p ? V[(int64_t)(row0 + col + 1) * a.ld + s] : 0.0;
+    return r;
+}
+static __device__ __forceinline__ void seg_st2(const CoxArgs& a, double* V, int row0, int col, int s, double2 v) {
+    if (col < a.p) V[(int64_t)(row0 + col) * a.ld + s] = v.x;
+    if (col + 1 < a.p) V[(int64_t)(row0 + col + 1) * a.ld + s] = v.y;
+}
+
+// ---- the forward recurrence of the two walks (passes 1 and 3) -------------------------------------------------------------
+// The running max M of eta and the sums of exp(eta - M) [1, x] since the last stratum start (s0, s1); under EF the same sums
+// over the event rows of the open tie group (t0, t1), scaled by the same M.  Lane l holds columns c * 128 + 2 l, + 1 of pair c.
+// The scan pass is the eta pass's segment re-walked from its prefix, so both walk with these operations and nothing else.
+template <int NC, bool EF>
+struct CoxRun {
+    double M, s0, t0;
+    double2 s1[NC], t1[EF ? NC : 1];
+
+    __device__ __forceinline__ void clear_group() {
+        if constexpr (EF) {
+            t0 = 0.0;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
+        }
+    }
+    // empty sums: the eta pass's segment before its first row, and every stratum start (the open tie group is not touched:
+    // it closed at the position in front of the start)
+    __device__ __forceinline__ void restart() {
+        M = -INFINITY; s0 = 0.0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { s1[c].x = 0.0; s1[c].y = 0.0; }
+    }
+    __device__ __forceinline__ void rescale(double Mn) {
+        const double r = M == -INFINITY ? 0.0 : exp_neg(Mn - M);
+        s0 *= r;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { s1[c].x *= r; s1[c].y *= r; }
+        if constexpr (EF) {
+            t0 *= r;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) { t1[c].x *= r; t1[c].y *= r; }
+        }
+        M = Mn;
+    }
+    // the row (eta, x) joins the sums; returns its term e = exp(eta - M)
+    __device__ __forceinline__ double add_row(double et, const double2 (&x)[NC]) {
+        if (et > M) rescale(et);                            // wave-uniform: rescale the running sums to the new max
+        const double e = exp_neg(M - et);
+        s0 += e;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { s1[c].x = fma(e, x[c].x, s1[c].x); s1[c].y = fma(e, x[c].y, s1[c].y); }
+        return e;
+    }
+    // an event row also joins the open tie group
+    __device__ __forceinline__ void add_to_group(double e, const double2 (&x)[NC]) {
+        if constexpr (EF) {
+            t0 += e;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) { t1[c].x = fma(e, x[c].x, t1[c].x); t1[c].y = fma(e, x[c].y, t1[c].y); }
+        }
+    }
 };
 
 // ---- pass 1 ----------------------------------------------------------------------------------------------------------
@@ -161,24 +235,19 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * COX_WAVES + (threadIdx.x >> 6);
     if (s >= a.nseg) return;
-    double2 b[NC], s1[NC];
+    double2 b[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int col = c * 128 + 2 * lane;
         b[c].x = col < a.p ? a.beta[col] : 0.0;
         b[c].y = col + 1 < a.p ? a.beta[col + 1] : 0.0;
-        s1[c].x = 0.0; s1[c].y = 0.0;
     }
-    double M = -INFINITY, s0 = 0.0;
+    CoxRun<NC, EF> run;
+    run.restart();
+    run.clear_group();
     int has_end = 0, head = 0, tail = 0, nend = 0;
-    double t0 = 0.0;                                // (EF) the sums over the event rows of the open tie group
-    double2 t1[EF ? NC : 1];
-    int nend2 = 0, has_start = 0;
-    (void)t0; (void)t1; (void)nend2; (void)has_start;
-    if constexpr (EF) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
-    }
+    int nend2 = 0, has_start = 0;                   // (EF) ends with two own events or more, (ST) the segment holds a stratum start
+    (void)nend2; (void)has_start;
     const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
     const int myrow = row_of_lane<RB>(lane);
     for (int64_t q0 = p0; q0 < p1; q0 += RB) {
@@ -206,71 +275,37 @@ __global__ __launch_bounds__(COX_THREADS) void cox_eta_kernel(CoxArgs a) {
             if (q >= p1) break;
             const double et = e_r[i];
             if constexpr (ST) {
-                if (a.sflag[q]) {                               // a new stratum: empty sums (the open tie group closed at q - 1)
-                    has_start = 1;
-                    M = -INFINITY; s0 = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { s1[c].x = 0.0; s1[c].y = 0.0; }
-                }
+                if (a.sflag[q]) { has_start = 1; run.restart(); }       // a new stratum: the segment emits the sums since its last start
             }
-            if (et > M) {                                       // wave-uniform: rescale the running sums to the new max
-                const double r = M == -INFINITY ? 0.0 : exp_neg(et - M);
-                s0 *= r;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) { s1[c].x *= r; s1[c].y *= r; }
-                if constexpr (EF) {
-                    t0 *= r;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { t1[c].x *= r; t1[c].y *= r; }
-                }
-                M = et;
-            }
-            const double e = exp_neg(M - et);
-            s0 += e;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) { s1[c].x = fma(e, x[i][c].x, s1[c].x); s1[c].y = fma(e, x[i][c].y, s1[c].y); }
+            const double e = run.add_row(et, x[i]);
             const int64_t r = a.order[q];
             const int ev = a.event[r] != 0.0;
             bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
             if constexpr (ST) end = end || a.sflag[q + 1];      // (equal times on the two sides of a boundary are not tied)
             tail += ev;
-            if constexpr (EF) {
-                if (ev) {
-                    t0 += e;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { t1[c].x = fma(e, x[i][c].x, t1[c].x); t1[c].y = fma(e, x[i][c].y, t1[c].y); }
-                }
-            }
+            if (ev) run.add_to_group(e, x[i]);
             if (end) {
                 if (!has_end) head = tail;
                 nend += tail > 0;
-                if constexpr (EF) {
-                    nend2 += tail > 1;
-                    t0 = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
-                }
+                if constexpr (EF) nend2 += tail > 1;
+                run.clear_group();
                 has_end = 1;
                 tail = 0;
             }
         }
     }
     if (lane == 0) {
-        a.segM[s] = M;
-        a.segV[s] = s0;
+        a.segM[s] = run.M;
+        a.segV[s] = run.s0;
         a.tie[s] = has_end; a.tie[a.ld + s] = head; a.tie[2 * a.ld + s] = tail; a.tie[3 * a.ld + s] = nend;
-        if constexpr (EF) { a.tie2[s] = nend2; a.tailV[s] = t0; }
+        if constexpr (EF) { a.tie2[s] = nend2; a.tailV[s] = run.t0; }
         if constexpr (ST) a.sst[s] = has_start;
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int col = c * 128 + 2 * lane;
-        if (col < a.p) a.segV[(int64_t)(1 + col) * a.ld + s] = s1[c].x;
-        if (col + 1 < a.p) a.segV[(int64_t)(2 + col) * a.ld + s] = s1[c].y;
-        if constexpr (EF) {
-            if (col < a.p) a.tailV[(int64_t)(1 + col) * a.ld + s] = t1[c].x;
-            if (col + 1 < a.p) a.tailV[(int64_t)(2 + col) * a.ld + s] = t1[c].y;
-        }
+        seg_st2(a, a.segV, 1, col, s, run.s1[c]);
+        if constexpr (EF) seg_st2(a, a.tailV, 1, col, s, run.t1[c]);
     }
 }
 
@@ -297,11 +332,11 @@ __device__ void seg_scan(int nseg, State ident, Load load, Comb comb, Store stor
     __syncthreads();
 }
 
-struct PreS { double M, v; };
 struct TieS { int f, c; };
 struct TcS { int f; double M, v; };     // a scaled sum that a flagged segment restarts (Efron's T carry; strata: prefix and hazard suffix)
 // the restart operator: a flagged segment replaces the accumulator, any other combines with it (associative: a range of
-// segments is flagged when any of them is, and then holds the sum from its last flagged segment on)
+// segments is flagged when any of them is, and then holds the sum from its last flagged segment on).  Without strata no
+// segment of the prefix and of the hazard suffix is flagged, and the operator is pre_comb / suf_comb.
 static __device__ __forceinline__ void tcs_restart_pre(TcS& x, const TcS& y) {
     if (y.f) { x.M = y.M; x.v = y.v; x.f = 1; }
     else pre_comb(x.M, x.v, y.M, y.v);
@@ -314,39 +349,26 @@ static __device__ __forceinline__ void tcs_restart_suf(TcS& x, const TcS& y) {
 // ---- pass 2: blocks 0 .. p: prefix of column (S0, S1_c); block p + 1: tie groups and A-row indices; Efron: blocks
 // p + 2 .. 2 p + 2: column (T0, T1_c) of the tie group open at every segment's start -------------------------------------
 __global__ __launch_bounds__(COX_THREADS) void cox_segscan_kernel(CoxArgs a) {
-    __shared__ PreS shp[COX_THREADS];
     __shared__ TieS sht[COX_THREADS];
     __shared__ int64_t shg[COX_THREADS];
     __shared__ TcS shc[COX_THREADS];
     const int c = blockIdx.x;
-    if (c > a.p + 1) {
-        // TieS's operator on scaled sums: a segment with an end restarts the sum at its tail, any other adds all its event rows
-        const int cc = c - a.p - 2;
-        const double* V = a.tailV + (int64_t)cc * a.ld;
-        double* P = a.tcV + (int64_t)cc * a.ld;
+    if (c != a.p + 1) {
+        // one scaled-sum scan for both: column cc of the prefix (segV -> preV, preM) or of the T carry (tailV -> tcV, tcM)
+        const bool tc = c > a.p + 1;
+        const int cc = tc ? c - a.p - 2 : c;
+        const double* V = (tc ? a.tailV : a.segV) + (int64_t)cc * a.ld;
+        double* P = (tc ? a.tcV : a.preV) + (int64_t)cc * a.ld;
+        double* PM = tc ? a.tcM : a.preM;
         seg_scan<TcS>(a.nseg, TcS{0, -INFINITY, 0.0},
-                      // (strata: a segment that starts a stratum at its first position may hold no end, and restarts the group too)
-                      [&](int s) { return TcS{a.tie[s] | (a.sflag ? a.sst[s] : 0), a.segM[s], V[s]}; },
+                      // strata: a segment with a stratum start replaces the prefix (its sums run from its last start); the prefix of a
+                      // segment whose first position starts a stratum may hold anything, the walk restarts there.
+                      // T carry (TieS's operator on scaled sums): a segment with an end restarts the sum at its tail, any other adds
+                      // all its event rows; a segment that starts a stratum at its first position may hold no end, and restarts the
+                      // group too.
+                      [&](int s) { return TcS{(tc ? a.tie[s] : 0) | (a.sflag ? a.sst[s] : 0), a.segM[s], V[s]}; },
                       [](TcS& x, const TcS& y) { tcs_restart_pre(x, y); },
-                      [&](int s, const TcS& e) { P[s] = e.v; if (cc == 0) a.tcM[s] = e.M; }, shc, false);
-        return;
-    }
-    if (c <= a.p) {
-        const double* V = a.segV + (int64_t)c * a.ld;
-        double* P = a.preV + (int64_t)c * a.ld;
-        if (a.sflag) {
-            // strata: a segment with a stratum start replaces the prefix (its sums run from its last start); the prefix of a
-            // segment whose first position starts a stratum may hold anything, the walk restarts there
-            seg_scan<TcS>(a.nseg, TcS{0, -INFINITY, 0.0},
-                          [&](int s) { return TcS{a.sst[s], a.segM[s], V[s]}; },
-                          [](TcS& x, const TcS& y) { tcs_restart_pre(x, y); },
-                          [&](int s, const TcS& e) { P[s] = e.v; if (c == 0) a.preM[s] = e.M; }, shc, false);
-            return;
-        }
-        seg_scan<PreS>(a.nseg, PreS{-INFINITY, 0.0},
-                       [&](int s) { return PreS{a.segM[s], V[s]}; },
-                       [](PreS& x, const PreS& y) { pre_comb(x.M, x.v, y.M, y.v); },
-                       [&](int s, const PreS& e) { P[s] = e.v; if (c == 0) a.preM[s] = e.M; }, shp, false);
+                      [&](int s, const TcS& e) { P[s] = e.v; if (cc == 0) PM[s] = e.M; }, shc, false);
         return;
     }
     // the open tie group entering segment s: (f, c) = (segment has an end, events after its last end / all its events)
@@ -409,34 +431,44 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
     const int owner = (int)min<int64_t>(gs / a.ca, a.nchunks - 1);       // the chunk that also writes the segment's partials
     const bool own = owner == a.chunk;
     if (!own && (ge <= a.g0 || gs >= a.g0 + a.ca)) return;               // no A row of this chunk ends here
-    double M = a.preM[s], s0 = a.preV[s];
-    double2 s1[NC], u[NC];
+    CoxRun<NC, EF> run;                                                  // the segment's exclusive prefix
+    run.M = a.preM[s]; run.s0 = a.preV[s];
+    double2 u[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const int col = c * 128 + 2 * lane;
-        s1[c].x = col < a.p ? a.preV[(int64_t)(1 + col) * a.ld + s] : 0.0;
-        s1[c].y = col + 1 < a.p ? a.preV[(int64_t)(2 + col) * a.ld + s] : 0.0;
+        run.s1[c] = seg_ld2(a, a.preV, 1, c * 128 + 2 * lane, s);
         u[c].x = 0.0; u[c].y = 0.0;
     }
     int open = a.carry[s];
     int64_t g = gs;
     double ll = 0.0, hq = 0.0, hv = 0.0;
-    // (EF) T0 / T1 of the open tie group under the same running max, and the (Q, h2) of the segment's first end
-    double t0 = 0.0, nq = 0.0, nv = 0.0;
-    double2 t1[EF ? NC : 1];
+    double nq = 0.0, nv = 0.0;                                           // (EF) the (Q, h2) of the segment's first end
     bool seen_end = false, seen_start = false;
-    (void)t0; (void)t1; (void)nq; (void)nv; (void)seen_end; (void)seen_start;
+    (void)nq; (void)nv; (void)seen_end; (void)seen_start;
     if constexpr (EF) {
+        // T0 / T1 of the open tie group, brought under the prefix max (which covers the group's rows)
         const double cM = a.tcM[s];
-        const double r = (cM == -INFINITY || M == -INFINITY) ? 0.0 : exp_neg(M - cM);     // (the prefix max covers the group's rows)
-        t0 = a.tcV[s] * r;
+        const double r = (cM == -INFINITY || run.M == -INFINITY) ? 0.0 : exp_neg(run.M - cM);
+        run.t0 = a.tcV[s] * r;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const double2 t = seg_ld2(a, a.tcV, 1, c * 128 + 2 * lane, s);
+            run.t1[c].x = t.x * r; run.t1[c].y = t.y * r;
+        }
+    }
+    // A row g (if the chunk holds it): the lane's pair c of it is val(c), its Gram weight wgt
+    auto store_row = [&](int64_t gr, double wgt, auto val) {
+        if (gr < a.g0 || gr >= a.g0 + a.ca) return;
+        double* Ar = a.A + (gr - a.g0) * a.lda;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int col = c * 128 + 2 * lane;
-            t1[c].x = col < a.p ? a.tcV[(int64_t)(1 + col) * a.ld + s] * r : 0.0;
-            t1[c].y = col + 1 < a.p ? a.tcV[(int64_t)(2 + col) * a.ld + s] * r : 0.0;
+            const double2 v = val(c);
+            if (col < a.p) Ar[col] = v.x;
+            if (col + 1 < a.p) Ar[col + 1] = v.y;
         }
-    }
+        if (lane == 0) a.dA[gr - a.g0] = wgt;
+    };
     const int64_t p0 = (int64_t)s * a.L, p1 = min(p0 + a.L, a.n);
     for (int64_t q0 = p0; q0 < p1; q0 += RB) {
         double2 x[RB][NC];
@@ -453,136 +485,80 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
             if (q >= p1) break;
             const double et = a.eta[q];
             if constexpr (ST) {
-                if (a.sflag[q]) {          // a new stratum: the prefix, the open group and its T sums start empty
-                    seen_start = true;
-                    M = -INFINITY; s0 = 0.0; open = 0;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { s1[c].x = 0.0; s1[c].y = 0.0; }
-                    if constexpr (EF) {
-                        t0 = 0.0;
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
-                    }
-                }
+                if (a.sflag[q]) { seen_start = true; open = 0; run.restart(); run.clear_group(); }     // a new stratum: the prefix and the open group start empty
             }
-            if (et > M) {
-                const double r = M == -INFINITY ? 0.0 : exp_neg(et - M);
-                s0 *= r;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) { s1[c].x *= r; s1[c].y *= r; }
-                if constexpr (EF) {
-                    t0 *= r;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { t1[c].x *= r; t1[c].y *= r; }
-                }
-                M = et;
-            }
-            const double e = exp_neg(M - et);
-            s0 += e;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) { s1[c].x = fma(e, x[i][c].x, s1[c].x); s1[c].y = fma(e, x[i][c].y, s1[c].y); }
+            const double e = run.add_row(et, x[i]);
             const int64_t r = a.order[q];
             const bool ev = a.event[r] != 0.0;
             bool end = q + 1 == a.n || a.time[a.order[q + 1]] != a.time[r];
             if constexpr (ST) end = end || a.sflag[q + 1];
             if (ev) {
                 ++open;
-                if constexpr (EF) {
-                    t0 += e;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { t1[c].x = fma(e, x[i][c].x, t1[c].x); t1[c].y = fma(e, x[i][c].y, t1[c].y); }
-                }
+                run.add_to_group(e, x[i]);
                 if (own) {
                     ll += et;
 #pragma unroll
                     for (int c = 0; c < NC; ++c) { u[c].x += x[i][c].x; u[c].y += x[i][c].y; }
                 }
             }
-            double hzv = 0.0;
-            if constexpr (EF) {
-                double h2 = 0.0;
-                if (end && open > 0) {
-                    const double inv = 1.0 / s0;
+            // a group end with events: its terms of loglik and U, its A rows and its hazard increment (EF: h1, and h2 beside it)
+            double hzv = 0.0, h2 = 0.0;
+            (void)h2;
+            if (end && open > 0) {
+                const double d = (double)open;
+                const double inv = 1.0 / run.s0;
+                if constexpr (EF) {
                     // d = 1: Breslow's terms; otherwise the sums over l and the Cholesky factor of K
                     double h1 = inv, slog = 0.0, L11 = inv, L21 = 0.0, L22 = 0.0;
                     if (open > 1) {
-                        const EfronSums es = efron_sums(s0, t0, open, lane);
+                        const EfronSums es = efron_sums(run.s0, run.t0, open, lane);
                         h1 = es.h1; h2 = es.h2; slog = es.slog;
                         L11 = sqrt(es.k0);
                         L21 = -es.k1 / L11;
                         L22 = sqrt(fmax(es.k2 - L21 * L21, 0.0));
                     } else if (own) {
-                        slog = log(s0);
+                        slog = log(run.s0);
                     }
                     if (own) {
-                        ll -= (double)open * M + slog;
+                        ll -= d * run.M + slog;
 #pragma unroll
                         for (int c = 0; c < NC; ++c) {
-                            u[c].x = fma(-h1, s1[c].x, fma(h2, t1[c].x, u[c].x));
-                            u[c].y = fma(-h1, s1[c].y, fma(h2, t1[c].y, u[c].y));
+                            u[c].x = fma(-h1, run.s1[c].x, fma(h2, run.t1[c].x, u[c].x));
+                            u[c].y = fma(-h1, run.s1[c].y, fma(h2, run.t1[c].y, u[c].y));
                         }
                         hzv = h1;
-                        if (!ST || !seen_start) suf_comb(hq, hv, M, hzv);
                     }
-                    if (g >= a.g0 && g < a.g0 + a.ca) {
-                        double* Ar = a.A + (g - a.g0) * a.lda;
+                    store_row(g++, -1.0, [&](int c) {
+                        return make_double2(fma(L11, run.s1[c].x, L21 * run.t1[c].x), fma(L11, run.s1[c].y, L21 * run.t1[c].y));
+                    });
+                    // (the group's two rows may lie in different chunks)
+                    if (open > 1) store_row(g++, -1.0, [&](int c) { return make_double2(L22 * run.t1[c].x, L22 * run.t1[c].y); });
+                } else {
+                    if (own) {
+                        ll -= d * (run.M + log(run.s0));
 #pragma unroll
                         for (int c = 0; c < NC; ++c) {
-                            const int col = c * 128 + 2 * lane;
-                            if (col < a.p) Ar[col] = fma(L11, s1[c].x, L21 * t1[c].x);
-                            if (col + 1 < a.p) Ar[col + 1] = fma(L11, s1[c].y, L21 * t1[c].y);
+                            u[c].x = fma(-d * inv, run.s1[c].x, u[c].x);
+                            u[c].y = fma(-d * inv, run.s1[c].y, u[c].y);
                         }
-                        if (lane == 0) a.dA[g - a.g0] = -1.0;
+                        hzv = d * inv;
                     }
-                    ++g;
-                    if (open > 1) {          // (the group's two rows may lie in different chunks)
-                        if (g >= a.g0 && g < a.g0 + a.ca) {
-                            double* Ar = a.A + (g - a.g0) * a.lda;
-#pragma unroll
-                            for (int c = 0; c < NC; ++c) {
-                                const int col = c * 128 + 2 * lane;
-                                if (col < a.p) Ar[col] = L22 * t1[c].x;
-                                if (col + 1 < a.p) Ar[col + 1] = L22 * t1[c].y;
-                            }
-                            if (lane == 0) a.dA[g - a.g0] = -1.0;
-                        }
-                        ++g;
-                    }
+                    store_row(g++, -d, [&](int c) { return make_double2(run.s1[c].x * inv, run.s1[c].y * inv); });
                 }
-                if (end) {
-                    open = 0;
-                    if (!seen_end) { seen_end = true; nq = M; nv = h2; }
-                    t0 = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { t1[c].x = 0.0; t1[c].y = 0.0; }
-                }
-                if (own && lane == 0) { a.hzv[q] = hzv; a.hzq[q] = M; a.h2v[q] = end ? h2 : -1.0; }
-                continue;
+                // (walked forward: the segment's total needs no order among its terms but a fixed one)
+                if (own && (!ST || !seen_start)) suf_comb(hq, hv, run.M, hzv);
             }
-            if (end && open > 0) {
-                const double d = (double)open;
-                const double inv = 1.0 / s0;
-                if (own) {
-                    ll -= d * (M + log(s0));
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) { u[c].x = fma(-d * inv, s1[c].x, u[c].x); u[c].y = fma(-d * inv, s1[c].y, u[c].y); }
-                    hzv = d * inv;
-                    if (!ST || !seen_start) suf_comb(hq, hv, M, hzv);      // (walked forward: the segment's total needs no order among its terms but a fixed one)
+            if (end) {
+                open = 0;
+                run.clear_group();
+                if constexpr (EF) {
+                    if (!seen_end) { seen_end = true; nq = run.M; nv = h2; }
                 }
-                if (g >= a.g0 && g < a.g0 + a.ca) {
-                    double* Ar = a.A + (g - a.g0) * a.lda;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        const int col = c * 128 + 2 * lane;
-                        if (col < a.p) Ar[col] = s1[c].x * inv;
-                        if (col + 1 < a.p) Ar[col + 1] = s1[c].y * inv;
-                    }
-                    if (lane == 0) a.dA[g - a.g0] = -d;
-                }
-                ++g;
             }
-            if (end) open = 0;
-            if (own && lane == 0) { a.hzv[q] = hzv; a.hzq[q] = M; }
+            if (own && lane == 0) {
+                a.hzv[q] = hzv; a.hzq[q] = run.M;
+                if constexpr (EF) a.h2v[q] = end ? h2 : -1.0;
+            }
         }
     }
     if (!own) return;
@@ -591,17 +567,12 @@ __global__ __launch_bounds__(COX_THREADS) void cox_scan_kernel(CoxArgs a) {
         if (lane == 0) { a.segNq[s] = nq; a.segNv[s] = nv; }
     }
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int col = c * 128 + 2 * lane;
-        if (col < a.p) a.segU[(int64_t)col * a.ld + s] = u[c].x;
-        if (col + 1 < a.p) a.segU[(int64_t)(col + 1) * a.ld + s] = u[c].y;
-    }
+    for (int c = 0; c < NC; ++c) seg_st2(a, a.segU, 0, c * 128 + 2 * lane, s, u[c]);
 }
 
 // ---- pass 4: suffix of d / S0 over segments (block 0) and the column sums of loglik / U (blocks 1 ..) ------------------
 // Efron: block p + 2: the (Q, h2) of the first group end after every segment.
 __global__ __launch_bounds__(COX_THREADS) void cox_finish_kernel(CoxArgs a, double* g, double* loglik) {
-    __shared__ PreS shp[COX_THREADS];
     __shared__ double red[COX_THREADS];
     __shared__ TcS shc[COX_THREADS];
     if ((int)blockIdx.x == a.p + 2) {
@@ -612,20 +583,13 @@ __global__ __launch_bounds__(COX_THREADS) void cox_finish_kernel(CoxArgs a, doub
                       [&](int s, const TcS& e) { a.sufNq[s] = e.M; a.sufNv[s] = e.v; }, shc, true);
         return;
     }
-    if (blockIdx.x == 0 && a.sflag) {
+    if (blockIdx.x == 0) {
         // strata: segH is the total of the segment's ends before its first stratum start, which is all that the positions
         // to its left may see of it and of everything after it
         seg_scan<TcS>(a.nseg, TcS{0, 0.0, 0.0},
-                      [&](int s) { return TcS{a.sst[s], a.segHq[s], a.segHv[s]}; },
+                      [&](int s) { return TcS{a.sflag ? a.sst[s] : 0, a.segHq[s], a.segHv[s]}; },
                       [](TcS& x, const TcS& y) { tcs_restart_suf(x, y); },
                       [&](int s, const TcS& e) { a.sufHq[s] = e.M; a.sufHv[s] = e.v; }, shc, true);
-        return;
-    }
-    if (blockIdx.x == 0) {
-        seg_scan<PreS>(a.nseg, PreS{0.0, 0.0},
-                       [&](int s) { return PreS{a.segHq[s], a.segHv[s]}; },
-                       [](PreS& x, const PreS& y) { suf_comb(x.M, x.v, y.M, y.v); },
-                       [&](int s, const PreS& e) { a.sufHq[s] = e.M; a.sufHv[s] = e.v; }, shp, true);
         return;
     }
     // column c = blockIdx.x - 1 (c == p: loglik): thread t sums segments t, t + 256, ... in order, then a fixed tree
@@ -746,64 +710,81 @@ __global__ void cox_fill_kernel(double* __restrict__ v, int64_t n, double val) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-struct CoxLayout {
-    int64_t L, nseg, ca, lda;
-    size_t off_eta, off_hzv, off_hzq, off_segM, off_segV, off_preM, off_preV, off_tie, off_gidx, off_carry, off_segLL, off_segU,
-        off_segH, off_suf, off_A, off_dA, off_wv, off_misc, off_gram, gram_bytes, total;
-    size_t off_h2v, off_tailV, off_tcM, off_tcV, off_tie2, off_segN, off_sufN;      // Efron only, after the Breslow layout
-    size_t off_sflag, off_sst;                                                      // strata only, after both
+// The one list of the workspace: every array of a pass in its order, each 256-byte aligned, with the geometry that sizes them
+// (segments of L positions, A chunks of ca rows of lda doubles).  With a null base only the sizes are walked, so the byte
+// queries and the passes cannot disagree.  The Efron arrays follow the Breslow layout and the strata arrays follow both.
+struct CoxWs {
+    CoxArgs a;              // L, ca, lda and every array pointer; the entries fill in the problem
+    int64_t* misc;          // cox_rows' read-back
+    void* gram; size_t gram_bytes;
+    size_t total;
 };
-
-static CoxLayout cox_layout(int64_t max_rows, int p, int ties, bool stratified = false) {
-    CoxLayout l{};
-    const int64_t n = std::max<int64_t>(max_rows, 1);
-    l.L = std::max<int64_t>(64, (n + COX_MAX_SEGS - 1) / COX_MAX_SEGS);
-    l.L = (l.L + COX_RB - 1) / COX_RB * COX_RB;
-    l.nseg = (n + l.L - 1) / l.L;
-    l.lda = (p + 1) / 2 * 2;
-    l.ca = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(COX_A_BYTES / (8 * (size_t)l.lda))));
-    const int64_t S = COX_MAX_SEGS;     // segment arrays sized for the largest count any n gives (the query stays monotone)
+static CoxWs cox_workspace(char* base, int64_t max_rows, int p, int ties, bool stratified) {
+    CoxWs w{};
+    CoxArgs& a = w.a;
+    const size_t n = (size_t)std::max<int64_t>(max_rows, 1);
+    a.L = std::max<int64_t>(64, ((int64_t)n + COX_MAX_SEGS - 1) / COX_MAX_SEGS);
+    a.L = (a.L + COX_RB - 1) / COX_RB * COX_RB;
+    a.lda = (p + 1) / 2 * 2;
+    a.ca = std::max<int64_t>(1, std::min<int64_t>((int64_t)n, (int64_t)(COX_A_BYTES / (8 * (size_t)a.lda))));
+    const size_t S = COX_MAX_SEGS;      // segment arrays sized for the largest count any n gives (the query stays monotone)
+    const size_t P1 = (size_t)p + 1;
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
-    l.off_eta = take(8 * (size_t)n);
-    l.off_hzv = take(8 * (size_t)n);
-    l.off_hzq = take(8 * (size_t)n);
-    l.off_wv = take(8 * (size_t)n);
-    l.off_segM = take(8 * S);
-    l.off_segV = take(8 * S * (size_t)(p + 1));
-    l.off_preM = take(8 * S);
-    l.off_preV = take(8 * S * (size_t)(p + 1));
-    l.off_tie = take(4 * 4 * S);
-    l.off_gidx = take(8 * (S + 1));
-    l.off_carry = take(4 * S);
-    l.off_segLL = take(8 * S);
-    l.off_segU = take(8 * S * (size_t)p);
-    l.off_segH = take(8 * 2 * S);
-    l.off_suf = take(8 * 2 * S);
-    l.off_A = take(8 * (size_t)l.ca * l.lda);
-    l.off_dA = take(8 * (size_t)l.ca);
-    l.off_misc = take(256);
-    l.off_gram = take(gram_workspace_bytes_impl(std::max<int64_t>(n, l.ca), p, 8));
-    l.gram_bytes = o - l.off_gram;
+    auto take = [&](auto*& ptr, size_t bytes) {
+        if (base) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + o);
+        o = align_up(o + bytes, 256);
+    };
+    take(a.eta, 8 * n); take(a.hzv, 8 * n); take(a.hzq, 8 * n); take(a.wv, 8 * n);
+    take(a.segM, 8 * S); take(a.segV, 8 * S * P1);
+    take(a.preM, 8 * S); take(a.preV, 8 * S * P1);
+    take(a.tie, 4 * 4 * S); take(a.gidx, 8 * (S + 1)); take(a.carry, 4 * S);
+    take(a.segLL, 8 * S); take(a.segU, 8 * S * (size_t)p);
+    take(a.segHq, 8 * S); take(a.segHv, 8 * S);
+    take(a.sufHq, 8 * S); take(a.sufHv, 8 * S);
+    take(a.A, 8 * (size_t)a.ca * a.lda); take(a.dA, 8 * (size_t)a.ca);
+    take(w.misc, 256);
+    const size_t gram0 = o;
+    take(w.gram, gram_workspace_bytes_impl(std::max<int64_t>((int64_t)n, a.ca), p, 8));
+    w.gram_bytes = o - gram0;
     if (ties == DLSA_COX_TIES_EFRON) {
-        l.off_h2v = take(8 * (size_t)n);
-        l.off_tailV = take(8 * S * (size_t)(p + 1));
-        l.off_tcM = take(8 * S);
-        l.off_tcV = take(8 * S * (size_t)(p + 1));
-        l.off_tie2 = take(4 * S);
-        l.off_segN = take(8 * 2 * S);
-        l.off_sufN = take(8 * 2 * S);
+        take(a.h2v, 8 * n);
+        take(a.tailV, 8 * S * P1);
+        take(a.tcM, 8 * S); take(a.tcV, 8 * S * P1);
+        take(a.tie2, 4 * S);
+        take(a.segNq, 8 * S); take(a.segNv, 8 * S);
+        take(a.sufNq, 8 * S); take(a.sufNv, 8 * S);
     }
-    if (stratified) {
-        l.off_sflag = take((size_t)n);
-        l.off_sst = take(4 * S);
+    if (stratified) {                   // (the flags themselves: cox_strata_flags, once per partition)
+        take(a.sflag, n);
+        take(a.sst, 4 * S);
     }
-    l.total = o;
-    return l;
+    w.total = o;
+    return w;
+}
+
+static int cox_check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
+        set_error("%s: workspace %zu bytes needed (256-aligned), got %zu", who, need, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    return DLSA_OK;
 }
 
 static bool cox_vec_ok(const double* X, int64_t ldx, int p) {
     return (p % 2 == 0) && (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0);
+}
+
+// The runtime (Efron, stratified) pair as the template arguments <EF, ST>: f(std::bool_constant<EF>, std::bool_constant<ST>).
+template <class F>
+static void cox_dispatch(const CoxArgs& a, F f) {
+    const bool efron = a.ties == DLSA_COX_TIES_EFRON;
+    if (a.sflag) {
+        if (efron) f(std::true_type{}, std::true_type{});
+        else f(std::false_type{}, std::true_type{});
+    } else {
+        if (efron) f(std::true_type{}, std::false_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
 }
 
 template <int NC, bool EF, bool ST>
@@ -817,25 +798,17 @@ static void launch_rows(bool scan, bool vec, const CoxArgs& a, hipStream_t s) {
         else hipLaunchKernelGGL((cox_eta_kernel<NC, false, EF, ST>), grid, dim3(COX_THREADS), 0, s, a);
     }
 }
-template <bool EF, bool ST>
-static void launch_rows_nc(bool scan, bool vec, const CoxArgs& a, hipStream_t s) {
-    const int nc = (a.p + 127) / 128;
-    if (nc <= 1) launch_rows<1, EF, ST>(scan, vec, a, s);
-    else if (nc <= 2) launch_rows<2, EF, ST>(scan, vec, a, s);
-    else if (nc <= 4) launch_rows<4, EF, ST>(scan, vec, a, s);
-    else if (nc <= 8) launch_rows<8, EF, ST>(scan, vec, a, s);
-    else launch_rows<16, EF, ST>(scan, vec, a, s);
-}
 static int launch_row_pass(bool scan, const CoxArgs& a, hipStream_t s) {
     const bool vec = cox_vec_ok(a.X, a.ldx, a.p);
-    const bool efron = a.ties == DLSA_COX_TIES_EFRON;
-    if (a.sflag) {
-        if (efron) launch_rows_nc<true, true>(scan, vec, a, s);
-        else launch_rows_nc<false, true>(scan, vec, a, s);
-    } else {
-        if (efron) launch_rows_nc<true, false>(scan, vec, a, s);
-        else launch_rows_nc<false, false>(scan, vec, a, s);
-    }
+    const int nc = (a.p + 127) / 128;
+    cox_dispatch(a, [&](auto ef, auto st) {
+        constexpr bool EF = decltype(ef)::value, ST = decltype(st)::value;
+        if (nc <= 1) launch_rows<1, EF, ST>(scan, vec, a, s);
+        else if (nc <= 2) launch_rows<2, EF, ST>(scan, vec, a, s);
+        else if (nc <= 4) launch_rows<4, EF, ST>(scan, vec, a, s);
+        else if (nc <= 8) launch_rows<8, EF, ST>(scan, vec, a, s);
+        else launch_rows<16, EF, ST>(scan, vec, a, s);
+    });
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
@@ -854,42 +827,24 @@ static int cox_rows(const int64_t* order, int64_t n, int64_t* misc_dev, CoxRows*
 }
 
 // The stratum-start flags of a partition's positions (null strata: nothing to do, the pass runs unstratified).
-static int cox_strata_flags(const int32_t* strata, const int64_t* order, int64_t n, char* ws, const CoxLayout& l, hipStream_t s) {
+static int cox_strata_flags(const int32_t* strata, const int64_t* order, int64_t n, const CoxWs& w, hipStream_t s) {
     if (!strata) return DLSA_OK;
     hipLaunchKernelGGL(cox_strata_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, strata, order, n,
-                       (unsigned char*)(ws + l.off_sflag));
+                       const_cast<unsigned char*>(w.a.sflag));
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
 
 // One partition at a fixed beta: H (and g, loglik, w_out) as described at the top.  *D_out: number of A rows (Breslow: the
 // event groups; Efron: one more for every group of two events or more; 0 = no event).
-static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const double* event, bool stratified, const int64_t* order,
-                         int64_t n, int p, int ties, const CoxRows& rows, const double* beta, double* H, int64_t ldh, double* g, double* loglik,
-                         double* w_out, char* ws, const CoxLayout& l, int64_t* D_out, hipStream_t s) {
-    CoxArgs a{};
-    a.X = X; a.ldx = ldx; a.time = time; a.event = event; a.order = order; a.n = n; a.p = p; a.beta = beta;
-    a.L = l.L; a.nseg = (int)((n + l.L - 1) / l.L); a.ld = a.nseg;
-    a.eta = (double*)(ws + l.off_eta); a.hzv = (double*)(ws + l.off_hzv); a.hzq = (double*)(ws + l.off_hzq);
-    a.segM = (double*)(ws + l.off_segM); a.segV = (double*)(ws + l.off_segV);
-    a.preM = (double*)(ws + l.off_preM); a.preV = (double*)(ws + l.off_preV);
-    a.tie = (int*)(ws + l.off_tie); a.gidx = (int64_t*)(ws + l.off_gidx); a.carry = (int*)(ws + l.off_carry);
-    a.segLL = (double*)(ws + l.off_segLL); a.segU = (double*)(ws + l.off_segU);
-    a.segHq = (double*)(ws + l.off_segH); a.segHv = a.segHq + COX_MAX_SEGS;
-    a.sufHq = (double*)(ws + l.off_suf); a.sufHv = a.sufHq + COX_MAX_SEGS;
-    a.A = (double*)(ws + l.off_A); a.lda = l.lda; a.dA = (double*)(ws + l.off_dA); a.ca = l.ca;
-    a.wv = (double*)(ws + l.off_wv); a.w_out = w_out;
-    a.ties = ties;
+static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n, int p,
+                         int ties, const CoxRows& rows, const double* beta, double* H, int64_t ldh, double* g, double* loglik,
+                         double* w_out, const CoxWs& w, int64_t* D_out, hipStream_t s) {
+    CoxArgs a = w.a;
+    a.X = X; a.ldx = ldx; a.time = time; a.event = event; a.order = order; a.n = n; a.p = p; a.ties = ties; a.beta = beta;
+    a.nseg = (int)((n + a.L - 1) / a.L); a.ld = a.nseg;
+    a.w_out = w_out;
     const bool efron = ties == DLSA_COX_TIES_EFRON;
-    if (efron) {
-        a.h2v = (double*)(ws + l.off_h2v); a.tailV = (double*)(ws + l.off_tailV);
-        a.tcM = (double*)(ws + l.off_tcM); a.tcV = (double*)(ws + l.off_tcV); a.tie2 = (int*)(ws + l.off_tie2);
-        a.segNq = (double*)(ws + l.off_segN); a.segNv = a.segNq + COX_MAX_SEGS;
-        a.sufNq = (double*)(ws + l.off_sufN); a.sufNv = a.sufNq + COX_MAX_SEGS;
-    }
-    if (stratified) { a.sflag = (const unsigned char*)(ws + l.off_sflag); a.sst = (int*)(ws + l.off_sst); }      // (flags: cox_strata_flags)
-    void* gws = ws + l.off_gram;
-    const size_t gws_bytes = l.gram_bytes;
     int rc;
 
     rc = launch_row_pass(false, a, s);
@@ -900,15 +855,15 @@ static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const
     DLSA_HIP_CHECK(hipMemcpyAsync(&D, a.gidx + a.nseg, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     *D_out = D;
-    a.nchunks = (int)std::max<int64_t>(1, (D + l.ca - 1) / l.ca);
+    a.nchunks = (int)std::max<int64_t>(1, (D + a.ca - 1) / a.ca);
     bool first = true;
     for (int k = 0; k < a.nchunks; ++k) {
-        a.chunk = k; a.g0 = (int64_t)k * l.ca;
+        a.chunk = k; a.g0 = (int64_t)k * a.ca;
         rc = launch_row_pass(true, a, s);
         if (rc) return rc;
-        const int64_t rowsA = std::min<int64_t>(l.ca, D - a.g0);
+        const int64_t rowsA = std::min<int64_t>(a.ca, D - a.g0);
         if (rowsA > 0) {
-            rc = gram_impl_f64(a.A, a.lda, a.dA, rowsA, p, H, ldh, first ? 0 : 1, gws, gws_bytes, s);
+            rc = gram_impl_f64(a.A, a.lda, a.dA, rowsA, p, H, ldh, first ? 0 : 1, w.gram, w.gram_bytes, s);
             if (rc) return rc;
             first = false;
         }
@@ -926,25 +881,13 @@ static int cox_pass_impl(const double* X, int64_t ldx, const double* time, const
         }
         if (v0 > 0) a.w_out = nullptr;
         const dim3 wgrid((unsigned)((a.nseg + COX_WAVES - 1) / COX_WAVES));
-        if (stratified) {
-            if (efron) hipLaunchKernelGGL((cox_w_kernel<true, true>), wgrid, dim3(COX_THREADS), 0, s, a);
-            else hipLaunchKernelGGL((cox_w_kernel<false, true>), wgrid, dim3(COX_THREADS), 0, s, a);
-        } else {
-            if (efron) hipLaunchKernelGGL((cox_w_kernel<true, false>), wgrid, dim3(COX_THREADS), 0, s, a);
-            else hipLaunchKernelGGL((cox_w_kernel<false, false>), wgrid, dim3(COX_THREADS), 0, s, a);
-        }
+        cox_dispatch(a, [&](auto ef, auto st) {
+            hipLaunchKernelGGL((cox_w_kernel<decltype(ef)::value, decltype(st)::value>), wgrid, dim3(COX_THREADS), 0, s, a);
+        });
         DLSA_HIP_CHECK(hipGetLastError());
-        rc = gram_impl_f64(X + a.vlo * ldx, ldx * vstep, a.wv, a.vrows, p, H, ldh, first ? 0 : 1, gws, gws_bytes, s);
+        rc = gram_impl_f64(X + a.vlo * ldx, ldx * vstep, a.wv, a.vrows, p, H, ldh, first ? 0 : 1, w.gram, w.gram_bytes, s);
         if (rc) return rc;
         first = false;
-    }
-    return DLSA_OK;
-}
-
-static int cox_check_ws(void* ws, size_t ws_bytes, const CoxLayout& l) {
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
-        set_error("cox: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
     }
     return DLSA_OK;
 }
@@ -957,8 +900,8 @@ size_t dlsa_cox_strata_workspace_bytes(int64_t max_rows, int p, int ties, int st
     if (p <= 0 || p > 2048 || max_rows < 0 || (ties != DLSA_COX_TIES_BRESLOW && ties != DLSA_COX_TIES_EFRON)) return 0;
     if (stratified != 0 && stratified != 1) return 0;
     // Newton state after the pass scratch: beta, prev, delta, g (p each), stats, the Cholesky factor (p x p)
-    return dlsa::align_up(dlsa::cox_layout(max_rows, p, ties, stratified != 0).total, 256) + dlsa::align_up(8 * (size_t)(4 * p + 8), 256) +
-           dlsa::align_up(8 * (size_t)p * p, 256);
+    return dlsa::align_up(dlsa::cox_workspace(nullptr, max_rows, p, ties, stratified != 0).total, 256) +
+           dlsa::align_up(8 * (size_t)(4 * p + 8), 256) + dlsa::align_up(8 * (size_t)p * p, 256);
 }
 
 size_t dlsa_cox_ties_workspace_bytes(int64_t max_rows, int p, int ties) { return dlsa_cox_strata_workspace_bytes(max_rows, p, ties, 0); }
@@ -973,18 +916,17 @@ int dlsa_cox_pass_strata_f64(const double* X, int64_t ldx, const double* time, c
     DLSA_REQUIRE(n >= 1 && p > 0 && p <= 2048 && ldx >= p && ldh >= p, "cox_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
                  (long long)n, p, (long long)ldx, (long long)ldh);
     DLSA_REQUIRE(ties == DLSA_COX_TIES_BRESLOW || ties == DLSA_COX_TIES_EFRON, "cox_pass: unknown ties method %d", ties);
-    const CoxLayout l = cox_layout(n, p, ties, strata != nullptr);
-    int rc = cox_check_ws(ws, ws_bytes, l);
+    const CoxWs w = cox_workspace((char*)ws, n, p, ties, strata != nullptr);
+    int rc = cox_check_ws("cox", ws, ws_bytes, w.total);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     CoxRows rows;
-    rc = cox_rows(order, n, (int64_t*)((char*)ws + l.off_misc), &rows, s);
+    rc = cox_rows(order, n, w.misc, &rows, s);
     if (rc) return rc;
-    rc = cox_strata_flags(strata, order, n, (char*)ws, l, s);
+    rc = cox_strata_flags(strata, order, n, w, s);
     if (rc) return rc;
     int64_t D = 0;
-    return cox_pass_impl(X, ldx, time, event, strata != nullptr, order, n, p, ties, rows, beta, H, ldh, g, loglik, w_out, (char*)ws, l, &D,
-                         s);
+    return cox_pass_impl(X, ldx, time, event, order, n, p, ties, rows, beta, H, ldh, g, loglik, w_out, w, &D, s);
 }
 
 int dlsa_cox_pass_ties_f64(const double* X, int64_t ldx, const double* time, const double* event, const int64_t* order, int64_t n,
@@ -1015,21 +957,18 @@ int dlsa_cox_fit_strata_f64(const double* X, int64_t ldx, const double* time, co
         max_rows = std::max(max_rows, part_offsets_host[k + 1] - part_offsets_host[k]);
     }
     const bool stratified = strata != nullptr;
-    const CoxLayout l = cox_layout(max_rows, p, ties, stratified);
-    const size_t need = dlsa_cox_strata_workspace_bytes(max_rows, p, ties, stratified ? 1 : 0);
-    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
-        set_error("cox_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
-    double* st = (double*)(wsc + align_up(l.total, 256));
+    const CoxWs w = cox_workspace(wsc, max_rows, p, ties, stratified);
+    int rcw = cox_check_ws("cox_fit", ws, ws_bytes, dlsa_cox_strata_workspace_bytes(max_rows, p, ties, stratified ? 1 : 0));
+    if (rcw) return rcw;
+    hipStream_t s = (hipStream_t)stream;
+    double* st = (double*)(wsc + align_up(w.total, 256));
     double* stats = st;                 // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] loglik
     double* beta = st + 8;
     double* prev = beta + p;
     double* delta = prev + p;
     double* g = delta + p;
-    double* Lf = (double*)(wsc + align_up(l.total, 256) + align_up(8 * (size_t)(4 * p + 8), 256));
+    double* Lf = (double*)(wsc + align_up(w.total, 256) + align_up(8 * (size_t)(4 * p + 8), 256));
     int overall = DLSA_OK;
     for (int k = 0; k < K; ++k) {
         const int64_t nk = part_offsets_host[k + 1] - part_offsets_host[k];
@@ -1041,9 +980,9 @@ int dlsa_cox_fit_strata_f64(const double* X, int64_t ldx, const double* time, co
         double ll = 0.0;
         if (nk > 0) {
             CoxRows rows;
-            int rc = cox_rows(ok, nk, (int64_t*)(wsc + l.off_misc), &rows, s);
+            int rc = cox_rows(ok, nk, w.misc, &rows, s);
             if (rc) return rc;
-            rc = cox_strata_flags(strata, ok, nk, wsc, l, s);
+            rc = cox_strata_flags(strata, ok, nk, w, s);
             if (rc) return rc;
             DLSA_HIP_CHECK(hipMemsetAsync(beta, 0, (size_t)p * sizeof(double), s));
             double ll_prev = -INFINITY;
@@ -1052,7 +991,7 @@ int dlsa_cox_fit_strata_f64(const double* X, int64_t ldx, const double* time, co
             st_k = DLSA_PART_NOT_CONVERGED;
             for (int it = 0; it < max_iter + 1 && !done; ++it) {
                 int64_t D = 0;
-                rc = cox_pass_impl(X, ldx, time, event, stratified, ok, nk, p, ties, rows, beta, Hk, p, g, stats + 3, nullptr, wsc, l, &D, s);
+                rc = cox_pass_impl(X, ldx, time, event, ok, nk, p, ties, rows, beta, Hk, p, g, stats + 3, nullptr, w, &D, s);
                 if (rc) return rc;
                 if (D == 0) { st_k = DLSA_PART_EMPTY; break; }
                 rc = launch_chol_solve(Hk, p, 0, g, 0, beta, 0, p, 1, Lf, delta, 0, stats, 0, s, 0);

@@ -162,6 +162,41 @@ def test_strata_workspace_query(lib):
         assert lib.dlsa_cox_strata_workspace_bytes(*bad) == 0, bad
 
 
+# dlsa_cox_strata_workspace_bytes as the library of d1e44ca (the commit before the workspace became one list) returns it:
+# (max_rows, p): (Breslow, Breslow stratified, Efron, Efron stratified)
+WORKSPACE_BYTES = {
+    (0, 1): (772608, 789248, 1084160, 1100800),
+    (0, 5): (1165824, 1182464, 1739520, 1756160),
+    (0, 500): (68360960, 68377600, 101374976, 101391616),
+    (0, 2048): (503810048, 503826688, 638273792, 638290432),
+    (1, 1): (772608, 789248, 1084160, 1100800),
+    (1, 5): (1165824, 1182464, 1739520, 1756160),
+    (1, 500): (68360960, 68377600, 101374976, 101391616),
+    (1, 2048): (503810048, 503826688, 638273792, 638290432),
+    (65, 1): (776192, 792832, 1088256, 1104896),
+    (65, 5): (1171456, 1188096, 1745664, 1762304),
+    (65, 500): (68619520, 68636160, 101634048, 101650688),
+    (65, 2048): (504861184, 504877824, 639325440, 639342080),
+    (4096 * 64 + 1, 1): (31967744, 32246528, 34376448, 34655232),
+    (4096 * 64 + 1, 5): (40749568, 41028352, 43420416, 43699200),
+    (4096 * 64 + 1, 500): (463156480, 463435264, 498267648, 498546432),
+    (4096 * 64 + 1, 2048): (780748544, 781027328, 917309440, 917588224),
+    (10 ** 7, 1): (577286144, 587302656, 657597440, 667613952),
+    (10 ** 7, 5): (650854144, 660870656, 731427584, 741444096),
+    (10 ** 7, 500): (1244527360, 1254543872, 1357541120, 1367557632),
+    (10 ** 7, 2048): (11292906240, 11302922752, 11507369728, 11517386240),
+}
+
+
+def test_strata_workspace_bytes_are_pinned(lib):
+    """the byte queries and the passes walk one list of the workspace arrays: its sizes, order and alignment are those of the
+    three lists it replaced"""
+    assert len(WORKSPACE_BYTES) == 5 * 4
+    for (n, p), want in WORKSPACE_BYTES.items():
+        got = tuple(lib.dlsa_cox_strata_workspace_bytes(n, p, ties, stratified) for ties in (0, 1) for stratified in (0, 1))
+        assert got == want, (n, p, got, want)
+
+
 def test_abi_validates_before_any_hip_call(lib):
     from dlsa_amd import _lib
     fake = ctypes.c_void_p(256)

@@ -74,6 +74,18 @@ def test_pass_matches_reference(eng, n, p, name, ties):
 
 
 @pytest.mark.parametrize("ties", TIES)
+@pytest.mark.parametrize("name", ["random7", None])
+def test_pass_widest_rows(eng, name, ties):
+    """p = 1025: the widest row kernels (nine column chunks run as sixteen, one row per step) with scalar loads (odd p), which
+    PASS_P does not reach; at n = 300 alone, where the loop form is cheap, with strata and without"""
+    X, t, ev, beta, strata = cases.pass_case(1025, 300, name or "random7")
+    if name is None:
+        _check("%s widest pass" % ties, X, _pass(eng, X, t, ev, beta, None, ties), LOOP[ties](X, t, ev, beta))
+    else:
+        _check_pass(eng, X, t, ev, beta, strata, ties)
+
+
+@pytest.mark.parametrize("ties", TIES)
 @pytest.mark.parametrize("case", cases.EDGE_CASES)
 def test_pass_edge_cases(eng, case, ties):
     X, t, ev, beta, strata = cases.edge_case(case)
