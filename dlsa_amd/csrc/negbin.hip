@@ -15,9 +15,9 @@
 // - (y+theta)/(mu+theta)^2 rewritten in alpha, so every term is O(alpha) as theta grows and nothing is formed at theta itself).
 //
 // Launches per evaluation at (beta, alpha) (every partial combines in a fixed order: no float atomics):
-//   1 negbin_kernel         poisson_kernel's skeleton (rowdot.h, RB rows per wave, non-temporal 16-byte loads, any row pitch) with
-//                           the NB terms: w = mu q (-> the Gram's weights), mu (-> the theta step), per-block partials of g,
-//                           sum (y - mu) q, sum y eta - (y + theta) L and, with the intercept and H wanted, X'w and sum w;
+//   1 count_pass_kernel     (count_pass.h, shared with poisson.hip: rowdot.h, RB rows per wave, non-temporal 16-byte loads, any row
+//                           pitch) with the terms of NbRow: w = mu q (-> the Gram's weights), mu (-> the theta step), per-block partials
+//                           of g, sum (y - mu) q, sum y eta - (y + theta) L and, with the intercept and H wanted, X'w and sum w;
 //   2 logit_finish_launch   the fixed-order column sums (shared with logit.hip / poisson.hip);
 //   3 the Gram              dlsa_gram_f64's dispatch on (X, w).
 // The theta step reads y and mu only (16 bytes per row): negbin_theta_kernel + its finish, once per Newton iteration on log theta.
@@ -30,207 +30,36 @@
 #include <math.h>
 #include <algorithm>
 
-typedef double dlsa_nb_d2v __attribute__((ext_vector_type(2)));
-
 namespace dlsa {
 
 #include "rowdot.h"          // merged_reduce, row_of_lane, rep_mask, rank1_update
 #include "poisson_exp.h"     // exp_full
 #include "negbin_special.h"  // nb_gamma_parts, nb_diffs
+#include "count_pass.h"      // count_pass_kernel, count_pass, CountScratch
 
-int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
-                  int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
-size_t gram_workspace_bytes_impl(int64_t n, int p, int elem_bytes);
-int gram_icpt_impl(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
-                   void* ws, size_t ws_bytes, hipStream_t s, const double* border);
-void logit_finish_launch(const double* gpart, const double* llpart, int nblocks, int pitch, int p, double* g,
-                         double* loglik, hipStream_t stream, const double* s0part, double* s0);
-int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
-                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
-                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);
-int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s);
-int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
-int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
-
-constexpr int NB_THREADS = 256;
-constexpr int NB_WAVES = NB_THREADS / 64;
-constexpr int NB_MAX_BLOCKS = 2048;
 constexpr int NB_THETA_BLOCKS = 2048;
 // theta-step sums: c (without lgamma(y+1)), s, i, Pearson, sum (y-mu)^2 - y, bad rows, sum (y-mu)^2 - mu, sum mu^2, sum lgamma(y+1),
 // sum (y + theta) L (the alpha-dependent part of the row log-likelihood: lets the driver move it from one alpha to the next)
 constexpr int NB_NQ = 10;
 enum { NB_C = 0, NB_S = 1, NB_I = 2, NB_PEARSON = 3, NB_D0 = 4, NB_BAD = 5, NB_M1 = 6, NB_M2 = 7, NB_LG = 8, NB_YL = 9 };
 
-struct NegbinArgs {
-    const double* X;
-    const double* y;
-    const double* off;     // nullable (OFF = false)
-    const double* beta;    // the p coefficients of X's columns
-    const double* beta0;   // the intercept's coefficient (nullable: no intercept)
-    double* w_out;         // mu q per row (nullable)
-    double* mu_out;        // mu per row (nullable)
-    double* gpart;         // [nblocks][NC*128]
-    double* llpart;        // [nblocks]: sum y eta - (y + theta) L
-    double* s0part;        // [nblocks]: sum (y - mu) q (the intercept's entry of g)
-    double* hpart;         // BORDER: [nblocks][NC*128] X'w
-    double* swpart;        // BORDER: [nblocks] sum w
-    int64_t ldx;
-    int64_t n;
-    int p;
+// the NB2 row at theta = 1 / alpha: weight mu q, residual (y - mu) q, term y eta - (y + theta) L
+struct NbRow {
+    static constexpr bool STORES_MU = true;
     double alpha;          // >= 0 (0: the Poisson limit, used by the fit at its start)
     double theta;          // 1 / alpha
     double log_alpha;
-};
-
-static __device__ __forceinline__ double2 nb_ld2(const double* ptr) {
-    const dlsa_nb_d2v t = __builtin_nontemporal_load(reinterpret_cast<const dlsa_nb_d2v*>(ptr));
-    double2 r; r.x = t.x; r.y = t.y; return r;
-}
-
-// poisson_kernel's skeleton with the NB terms: branch-free clamped loads, the lane's own row's count and offset travel with the
-// batch, a second register set prefetches the next batch at NC = 1.
-template <int NC, int RB, bool VEC, bool OFF, bool BORDER>
-__global__ __launch_bounds__(NB_THREADS) void negbin_kernel(NegbinArgs a) {
-    __shared__ double red[NC * 128 + 2];
-    __shared__ double redh[BORDER ? NC * 128 + 1 : 1];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const double b0 = a.beta0 ? *a.beta0 : 0.0;
-    const double alpha = a.alpha, theta = a.theta, log_alpha = a.log_alpha;
-    double s0 = 0.0, sw = 0.0, ll = 0.0;
-    double2 b[NC], g[NC], h[BORDER ? NC : 1];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int col = c * 128 + 2 * lane;
-        b[c].x = col < a.p ? a.beta[col] : 0.0;
-        b[c].y = col + 1 < a.p ? a.beta[col + 1] : 0.0;
-        g[c].x = 0.0; g[c].y = 0.0;
-        if constexpr (BORDER) { h[c].x = 0.0; h[c].y = 0.0; }
-    }
-    const int myrow = row_of_lane<RB>(lane);
-    const bool rep = (lane & rep_mask<RB>()) == 0;
-    const int64_t nbatch = (a.n + RB - 1) / RB;
-    const int64_t stride = (int64_t)gridDim.x * NB_WAVES;
-
-    auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], double& yv, double& ov) {
-        const int64_t row0 = bt * RB;
-        const int64_t ry = min(row0 + myrow, a.n - 1);
-        const double ytmp = a.y[ry];
-        const double otmp = OFF ? a.off[ry] : 0.0;
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            const int64_t r = min(row0 + i, a.n - 1);
-            const double* rowp = a.X + r * a.ldx;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int col = c * 128 + 2 * lane;
-                const int c0 = col < a.p ? col : 0;                   // clamped columns meet beta = 0
-                if (VEC) {                                            // VEC implies p even: a pair never straddles p
-                    x[i][c] = nb_ld2(rowp + c0);
-                } else {
-                    x[i][c].x = __builtin_nontemporal_load(rowp + c0);
-                    x[i][c].y = __builtin_nontemporal_load(rowp + (col + 1 < a.p ? col + 1 : 0));
-                }
-            }
-        }
-        yv = ytmp;
-        ov = otmp;
-    };
-    auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const double yraw, const double oraw) {
-        const int64_t row0 = bt * RB;
-        double dot[RB];
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) s = fma(x[i][c].x, b[c].x, fma(x[i][c].y, b[c].y, s));
-            dot[i] = s;
-        }
-        const int64_t r = row0 + myrow;
-        const bool valid = r < a.n;
-        const double yv = valid ? yraw : 0.0;
-        const double eta = merged_reduce<RB>(dot, lane) + b0 + (OFF ? oraw : 0.0);
-        const double mu = exp_full(eta);
+    __device__ __forceinline__ void terms(double yv, double eta, double mu, double& wgt, double& rs, double& llt) const {
         const double amu = alpha * mu;
         // one reciprocal: q = 1 / (1 + alpha mu), w = mu q; where alpha mu overflowed (or is NaN) the limits w = 1 / alpha, q = 0
         const bool big = !(amu <= 1e300);
         const double q = big ? 0.0 : 1.0 / (1.0 + amu);
-        const double wgt = big ? theta : mu * q;
+        wgt = big ? theta : mu * q;
         const double L = amu < 9007199254740992.0 ? log1p(amu) : (mu < INFINITY ? eta + log_alpha : INFINITY);
-        const double rs = big ? -theta : (yv - mu) * q;
-        const double resid = valid ? rs : 0.0;
-        if (valid && rep) {
-            if (a.w_out) a.w_out[r] = wgt;
-            if (a.mu_out) a.mu_out[r] = mu;
-            ll += yv * eta - (alpha > 0.0 ? (yv + theta) * L : mu);      // (y + theta) L -> mu as alpha -> 0
-            s0 += resid;
-        }
-        rank1_update<RB, NC, 0>(resid, x, g);
-        if constexpr (BORDER) {                 // X'w and sum w of the same rows (a clamped row past n weighs nothing)
-            const double wv = valid ? wgt : 0.0;
-            if (rep) sw += wv;
-            rank1_update<RB, NC, 0>(wv, x, h);
-        }
-    };
-
-    int64_t bt = (int64_t)blockIdx.x * NB_WAVES + wave;
-    if constexpr (NC == 1) {
-        double2 xa[RB][NC], xb[RB][NC];
-        double ya = 0.0, yb = 0.0, oa = 0.0, ob = 0.0;
-        if (a.n > 0) {
-            load_batch(bt, xa, ya, oa);
-            for (; bt < nbatch; bt += 2 * stride) {
-                const int64_t b1 = bt + stride, b2 = bt + 2 * stride;
-                load_batch(b1, xb, yb, ob);
-                process(bt, xa, ya, oa);
-                load_batch(b2, xa, ya, oa);
-                if (b1 < nbatch) process(b1, xb, yb, ob);
-            }
-        }
-    } else {
-        for (; bt < nbatch; bt += stride) {
-            double2 x[RB][NC];
-            double yv, ov;
-            load_batch(bt, x, yv, ov);
-            process(bt, x, yv, ov);
-        }
+        rs = big ? -theta : (yv - mu) * q;
+        llt = yv * eta - (alpha > 0.0 ? (yv + theta) * L : mu);      // (y + theta) L -> mu as alpha -> 0
     }
-
-    // block reduction: waves add into LDS one after another (fixed order)
-    ll = wave_allreduce_sum(ll);
-    s0 = wave_allreduce_sum(s0);
-    if constexpr (BORDER) sw = wave_allreduce_sum(sw);
-    for (int wv = 0; wv < NB_WAVES; ++wv) {
-        if (wave == wv) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                double* dst = red + c * 128 + 2 * lane;
-                if (wv == 0) { dst[0] = g[c].x; dst[1] = g[c].y; }
-                else { dst[0] += g[c].x; dst[1] += g[c].y; }
-                if constexpr (BORDER) {
-                    double* dh = redh + c * 128 + 2 * lane;
-                    if (wv == 0) { dh[0] = h[c].x; dh[1] = h[c].y; }
-                    else { dh[0] += h[c].x; dh[1] += h[c].y; }
-                }
-            }
-            if (lane == 0) {
-                if (wv == 0) { red[NC * 128] = ll; red[NC * 128 + 1] = s0; }
-                else { red[NC * 128] += ll; red[NC * 128 + 1] += s0; }
-                if constexpr (BORDER) { if (wv == 0) redh[NC * 128] = sw; else redh[NC * 128] += sw; }
-            }
-        }
-        __syncthreads();
-    }
-    double* gp = a.gpart + (int64_t)blockIdx.x * (NC * 128);
-    for (int col = tid; col < NC * 128; col += NB_THREADS) gp[col] = red[col];
-    if (tid == 0) { a.llpart[blockIdx.x] = red[NC * 128]; a.s0part[blockIdx.x] = red[NC * 128 + 1]; }
-    if constexpr (BORDER) {
-        double* hp = a.hpart + (int64_t)blockIdx.x * (NC * 128);
-        for (int col = tid; col < NC * 128; col += NB_THREADS) hp[col] = redh[col];
-        if (tid == 0) a.swpart[blockIdx.x] = redh[NC * 128];
-    }
-}
+};
 
 // ---- the dispersion step: the NB_NQ sums over (y, mu) at one theta -----------------------------------------------------
 // alpha = 0 (the fit's look at the Poisson MLE) skips the special functions: only Pearson, the two moment sums and the check.
@@ -295,12 +124,6 @@ __global__ void negbin_ll_fix_kernel(double* __restrict__ ll, const double* __re
     if (threadIdx.x == 0) ll[0] = tst[NB_BAD] > 0.0 ? NAN : ll[0] + (tst[NB_C] - tst[NB_LG]);
 }
 
-// out[j] = v[first + j * step]
-__global__ void negbin_gather_kernel(const double* __restrict__ v, int64_t first, int64_t step, int64_t n, double* __restrict__ out) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) out[j] = v[first + j * step];
-}
-
 // test entry: out[4 i ..] = psi(theta_i), psi'(theta_i), psi(y_i + theta_i) - psi(theta_i), lgamma(y_i + theta_i) - lgamma(theta_i) - y_i log theta_i
 __global__ void negbin_special_kernel(const double* __restrict__ theta, const double* __restrict__ y, int64_t n, double* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -314,24 +137,9 @@ __global__ void negbin_special_kernel(const double* __restrict__ theta, const do
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static int nb_nc(int p) {
-    const int chunks = (p + 127) / 128;
-    int nc = 1;
-    while (nc < chunks) nc *= 2;
-    return nc;
-}
-
-static int nb_rb(int nc) { return nc <= 2 ? 8 : nc == 4 ? 4 : nc == 8 ? 2 : 1; }
-
-static int nb_blocks(int64_t n, int rb) {
-    const int64_t nbatch = (n + rb - 1) / rb;
-    int64_t blocks = (nbatch + NB_WAVES * 4 - 1) / (NB_WAVES * 4);   // >= 4 batches per wave
-    return (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), NB_MAX_BLOCKS);
-}
-
 struct NbLayout {
-    size_t off_y, off_o, off_pois, off_gpart, off_llpart, off_s0part, off_hpart, off_swpart, off_border, off_tpart, off_tst, off_w,
-        off_mu, off_gram, off_state, total;
+    CountScratchOff sc;
+    size_t off_y, off_o, off_pois, off_tpart, off_tst, off_w, off_mu, off_gram, off_state, total;
 };
 
 // [gathered counts | gathered offsets] of a strided partition, then the Poisson start's workspace (pois_bytes; 0 for the pass)
@@ -340,18 +148,12 @@ static NbLayout nb_layout(int64_t max_rows, int p, int intercept, int64_t row_st
     NbLayout l{};
     const int64_t n = std::max<int64_t>(max_rows, 1);
     const int pe = p + (intercept ? 1 : 0);
-    const size_t gp = (size_t)NB_MAX_BLOCKS * nb_nc(p) * 128 * sizeof(double);
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
     l.off_y = take(row_step > 1 ? 8 * (size_t)n : 0);
     l.off_o = take(row_step > 1 ? 8 * (size_t)n : 0);
     l.off_pois = o;
-    l.off_gpart = take(gp);
-    l.off_llpart = take(8 * (size_t)NB_MAX_BLOCKS);
-    l.off_s0part = take(8 * (size_t)NB_MAX_BLOCKS);
-    l.off_hpart = take(gp);
-    l.off_swpart = take(8 * (size_t)NB_MAX_BLOCKS);
-    l.off_border = take(8 * (size_t)(p + 1));
+    l.sc = count_scratch_take(take, p);
     l.off_tpart = take(8 * (size_t)NB_NQ * NB_THETA_BLOCKS);
     l.off_tst = take(8 * 16);
     l.off_w = take(8 * (size_t)n);
@@ -362,58 +164,13 @@ static NbLayout nb_layout(int64_t max_rows, int p, int intercept, int64_t row_st
     return l;
 }
 
-template <int NC, int RB, bool VEC, bool OFF>
-static void launch_nb_b(const NegbinArgs& a, bool border, int blocks, hipStream_t s) {
-    if (border) hipLaunchKernelGGL((negbin_kernel<NC, RB, VEC, OFF, true>), dim3(blocks), dim3(NB_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((negbin_kernel<NC, RB, VEC, OFF, false>), dim3(blocks), dim3(NB_THREADS), 0, s, a);
-}
-template <int NC, int RB>
-static void launch_nb(const NegbinArgs& a, bool vec, bool border, int blocks, hipStream_t s) {
-    if (vec) {
-        if (a.off) launch_nb_b<NC, RB, true, true>(a, border, blocks, s);
-        else launch_nb_b<NC, RB, true, false>(a, border, blocks, s);
-    } else {
-        if (a.off) launch_nb_b<NC, RB, false, true>(a, border, blocks, s);
-        else launch_nb_b<NC, RB, false, false>(a, border, blocks, s);
-    }
-}
-
-// One partition at a fixed (beta, alpha) (pe = p + intercept entries, intercept first).  H (nullable) needs w (the Gram's
-// weights); g, loglik (the row sum of y eta - (y + theta) L, without c(theta)), w, mu nullable otherwise.
+// One partition at a fixed (beta, alpha) (count_pass with the NB2 row): w is mu q per row, loglik the row sum of
+// y eta - (y + theta) L, without c(theta).
 static int nb_pass_impl(const double* X, int64_t ldx, const double* y, const double* off, const double* beta, double alpha, int64_t n,
                         int p, int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w, double* mu, char* ws,
                         const NbLayout& l, hipStream_t s) {
-    const int nc = nb_nc(p), rb = nb_rb(nc);
-    const bool border = H && intercept;
-    NegbinArgs a{};
-    a.X = X; a.y = y; a.off = off; a.beta = intercept ? beta + 1 : beta; a.beta0 = intercept ? beta : nullptr;
-    a.w_out = w; a.mu_out = mu; a.ldx = ldx; a.n = n; a.p = p;
-    a.alpha = alpha; a.theta = 1.0 / alpha; a.log_alpha = log(alpha);
-    a.gpart = (double*)(ws + l.off_gpart); a.llpart = (double*)(ws + l.off_llpart); a.s0part = (double*)(ws + l.off_s0part);
-    a.hpart = (double*)(ws + l.off_hpart); a.swpart = (double*)(ws + l.off_swpart);
-    const bool vec = (ldx % 2 == 0) && (p % 2 == 0) && (((uintptr_t)X & 15) == 0);
-    const int blocks = nb_blocks(n, rb);
-    switch (nc) {
-        case 1: launch_nb<1, 8>(a, vec, border, blocks, s); break;
-        case 2: launch_nb<2, 8>(a, vec, border, blocks, s); break;
-        case 4: launch_nb<4, 4>(a, vec, border, blocks, s); break;
-        case 8: launch_nb<8, 2>(a, vec, border, blocks, s); break;
-        default: launch_nb<16, 1>(a, vec, border, blocks, s); break;
-    }
-    DLSA_HIP_CHECK(hipGetLastError());
-    if (g || loglik) {
-        logit_finish_launch(a.gpart, a.llpart, blocks, nc * 128, p, (g && intercept) ? g + 1 : g, loglik, s,
-                            (g && intercept) ? a.s0part : nullptr, (g && intercept) ? g : nullptr);
-        DLSA_HIP_CHECK(hipGetLastError());
-    }
-    if (!H) return DLSA_OK;
-    void* gws = ws + l.off_gram;
-    const size_t gws_bytes = l.total - l.off_gram;
-    if (!intercept) return gram_impl_f64(X, ldx, w, n, p, H, ldh, 0, gws, gws_bytes, s);
-    double* bd = (double*)(ws + l.off_border);          // [sum w | X'w]: row 0 of [1 | X]' diag(w) [1 | X]
-    logit_finish_launch(a.hpart, a.swpart, blocks, nc * 128, p, bd + 1, bd, s, nullptr, nullptr);
-    DLSA_HIP_CHECK(hipGetLastError());
-    return gram_icpt_impl(X, ldx, w, n, p, H, ldh, gws, gws_bytes, s, bd);
+    return count_pass(NbRow{alpha, 1.0 / alpha, log(alpha)}, X, ldx, y, off, beta, n, p, intercept, H, ldh, g, loglik, w, mu,
+                      count_scratch_at(ws, l.sc), ws + l.off_gram, l.total - l.off_gram, s);
 }
 
 // the NB_NQ sums at theta = 1 / alpha (alpha = 0: no special functions) into tst (device)
@@ -429,11 +186,11 @@ static int nb_theta_launch(const double* y, const double* mu, const double* off,
 constexpr double NB_ALPHA_START_MIN = 1e-3;     // floor of the moment start
 constexpr double NB_ALPHA_POISSON = 1e-8;       // the theta iteration below this alpha: the partition is Poisson (alpha = 0)
 
-struct NbFitCtx {
+struct NbFitCtx : PoisState {                  // (stats, beta, prev, delta, g, Lf: the Newton state)
     const double* Xk; int64_t pitch; const double* yk; const double* ok; int64_t nk;
     int p, intercept, pe;
     double tol;
-    double* Hk; double* stats; double* beta; double* prev; double* delta; double* g; double* Lf;
+    double* Hk;
     double* w; double* mu; double* tpart; double* tst;
     char* ws; const NbLayout* l; hipStream_t s;
 };
@@ -598,9 +355,8 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
     char* wsc = (char*)ws;
     NbFitCtx c{};
     c.pitch = ldx * row_step; c.p = p; c.intercept = intercept; c.pe = pe; c.tol = tol;
-    c.stats = (double*)(wsc + l.off_state);        // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] the row log-likelihood
-    c.beta = c.stats + 8; c.prev = c.beta + pe; c.delta = c.prev + pe; c.g = c.delta + pe;
-    c.Lf = (double*)(wsc + l.off_state + align_up(8 * (size_t)(4 * pe + 8), 256));
+    // (NbFitCtx derives from PoisState so that the Newton loops keep reading c.beta, c.g, ... while the carving has one copy)
+    static_cast<PoisState&>(c) = pois_state_at(wsc + l.off_state, pe);
     c.w = (double*)(wsc + l.off_w); c.mu = (double*)(wsc + l.off_mu);
     c.tpart = (double*)(wsc + l.off_tpart); c.tst = (double*)(wsc + l.off_tst);
     c.ws = wsc; c.l = &l; c.s = s;
@@ -625,16 +381,16 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
             c.yk = y + part_first_host[k];
             c.ok = offset ? offset + part_first_host[k] : nullptr;
             if (row_step > 1) {                               // the partition's counts and offsets, gathered once
-                const dim3 grid((unsigned)((nk + 255) / 256));
                 double* yb = (double*)(wsc + l.off_y);
-                hipLaunchKernelGGL(negbin_gather_kernel, grid, dim3(256), 0, s, y, part_first_host[k], row_step, nk, yb);
+                rc = pois_gather(y, part_first_host[k], row_step, nk, yb, s);
+                if (rc) return rc;
                 c.yk = yb;
                 if (offset) {
                     double* ob = (double*)(wsc + l.off_o);
-                    hipLaunchKernelGGL(negbin_gather_kernel, grid, dim3(256), 0, s, offset, part_first_host[k], row_step, nk, ob);
+                    rc = pois_gather(offset, part_first_host[k], row_step, nk, ob, s);
+                    if (rc) return rc;
                     c.ok = ob;
                 }
-                DLSA_HIP_CHECK(hipGetLastError());
             }
             DLSA_HIP_CHECK(hipMemcpyAsync(c.beta, ck, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
             // mu at the Poisson MLE (alpha = 0: the kernel's Poisson limit; no H, no g), then the moment sums
@@ -690,9 +446,7 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
         if (alpha_host) alpha_host[k] = alpha;
         if (alpha_info_host) alpha_info_host[k] = info;
         if (pearson_host) pearson_host[k] = pearson;
-        if (st_k == DLSA_PART_NOT_CONVERGED && overall == DLSA_OK) overall = DLSA_ERR_NOT_CONVERGED;
-        if (st_k == DLSA_PART_NOT_SPD && overall == DLSA_OK) overall = DLSA_ERR_NOT_SPD;
-        if (st_k == DLSA_PART_NAN && overall == DLSA_OK) overall = DLSA_ERR_NAN;
+        pois_fold_status(st_k, overall);
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;

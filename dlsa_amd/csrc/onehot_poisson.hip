@@ -28,8 +28,6 @@ size_t onehot_workspace_bytes_impl(const dlsa_onehot_plan* pl, int64_t n);
 int onehot_plan_p(const dlsa_onehot_plan* pl);
 int onehot_gram_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
                      const double* w, int64_t n, double* H, int64_t ldh, void* ws, size_t ws_bytes, hipStream_t s, bool irls_weights);
-void logit_finish_launch(const double* gpart, const double* llpart, int nblocks, int pitch, int p, double* g,
-                         double* loglik, hipStream_t stream, const double* s0part, double* s0);
 
 // The skeleton of oh_logit_kernel with the Poisson terms.  Every thread runs the same number of rounds (the ordered mode has
 // barriers inside): rows past n are clamped to row n - 1 and masked.  OFF = false reads no offsets.
@@ -259,8 +257,7 @@ int dlsa_onehot_poisson_fit_f64(const dlsa_onehot_plan* plan, const double* num,
     PoisFitBufs b{};
     b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
     b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
-    b.state = (double*)(wsc + l.off_state);
-    b.Lf = (double*)(wsc + l.off_state + align_up(8 * (size_t)(4 * p + 8), 256));
+    b.st = pois_state_at(wsc + l.off_state, p);
     double* wv = (double*)(wsc + l.off_w);
     void* ws_oh = wsc + l.off_oh;
     const size_t oh_bytes = l.oh_bytes;

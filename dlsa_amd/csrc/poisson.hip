@@ -7,203 +7,36 @@
 //   loglik = sum y eta - mu - lgamma(y + 1),  g = X'(y - mu),  H = X' diag(mu) X.
 //
 // Launches per evaluation (every partial combines in a fixed order: no float atomics, no waits between workgroups):
-//   1 poisson_kernel        one read of the rows in the logit pass's layout (rowdot.h: RB rows per wave, one merged butterfly
-//                           for their dot products, non-temporal 16-byte loads): mu (-> w), per-block partials of g,
-//                           sum (y - mu), sum (y eta - mu) and, with the intercept and H wanted, of X'mu and sum mu (the
-//                           Hessian's border, so no extra pass);
+//   1 count_pass_kernel     (count_pass.h, shared with negbin.hip, here with the terms of PoisRow) one read of the rows in the
+//                           logit pass's layout (rowdot.h: RB rows per wave, one merged butterfly for their dot products,
+//                           non-temporal 16-byte loads): mu (-> w), per-block partials of g, sum (y - mu), sum (y eta - mu)
+//                           and, with the intercept and H wanted, of X'mu and sum mu (the Hessian's border, so no extra pass);
 //   2 logit_finish_launch   the fixed-order column sums of those partials (the finish step of logit.hip, shared);
 //   3 the Gram              dlsa_gram_f64's dispatch on (X, mu) into the p x p block (gram_icpt_impl with the border).
 // The constant sum lgamma(y + 1) is a small reduction of its own, once per partition (poisson_const_kernel), which also
 // counts the rows with a negative or non-finite count or offset and sums y and e^o for the intercept's start value.
 // The Newton loop (pois_fit_core) takes the evaluation at beta as a callable and is shared with the structured one-hot fit
-// (onehot_poisson.hip) through poisson_internal.h, as are the constant-term and log-likelihood-fix launchers.
+// (onehot_poisson.hip) through poisson_internal.h, as are the constant-term, log-likelihood-fix and gather launchers.
 #include "common.h"
 #include "poisson_internal.h"
 #include <math.h>
 #include <algorithm>
 
-typedef double dlsa_pois_d2v __attribute__((ext_vector_type(2)));
-
 namespace dlsa {
 
 #include "rowdot.h"       // merged_reduce, row_of_lane, rep_mask, rank1_update
 #include "poisson_exp.h"  // exp_full
+#include "count_pass.h"   // count_pass_kernel, count_pass, CountScratch
 
-int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
-                  int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
-size_t gram_workspace_bytes_impl(int64_t n, int p, int elem_bytes);
-int gram_icpt_impl(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
-                   void* ws, size_t ws_bytes, hipStream_t s, const double* border);
-void logit_finish_launch(const double* gpart, const double* llpart, int nblocks, int pitch, int p, double* g,
-                         double* loglik, hipStream_t stream, const double* s0part, double* s0);
-int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
-                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
-                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);
-int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s);
-int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
-int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
-
-constexpr int POIS_THREADS = 256;
-constexpr int POIS_WAVES = POIS_THREADS / 64;
-constexpr int POIS_MAX_BLOCKS = 2048;
-
-struct PoissonArgs {
-    const double* X;
-    const double* y;
-    const double* off;     // nullable (OFF = false)
-    const double* beta;    // the p coefficients of X's columns
-    const double* beta0;   // the intercept's coefficient (nullable: no intercept)
-    double* w_out;         // mu per row (nullable)
-    double* gpart;         // [nblocks][NC*128]
-    double* llpart;        // [nblocks]: sum y eta - mu
-    double* s0part;        // [nblocks]: sum y - mu (the intercept's entry of g)
-    double* hpart;         // BORDER: [nblocks][NC*128] X'mu
-    double* swpart;        // BORDER: [nblocks] sum mu
-    int64_t ldx;
-    int64_t n;
-    int p;
+// the Poisson row: weight mu, residual y - mu, term y eta - mu
+struct PoisRow {
+    static constexpr bool STORES_MU = false;
+    __device__ __forceinline__ void terms(double yv, double eta, double mu, double& wgt, double& rs, double& llt) const {
+        wgt = mu;
+        rs = yv - mu;
+        llt = yv * eta - mu;
+    }
 };
-
-static __device__ __forceinline__ double2 pois_ld2(const double* ptr) {
-    const dlsa_pois_d2v t = __builtin_nontemporal_load(reinterpret_cast<const dlsa_pois_d2v*>(ptr));
-    double2 r; r.x = t.x; r.y = t.y; return r;
-}
-
-// The logit pass's skeleton (logit.hip logit_kernel) with the Poisson terms: branch-free clamped loads, the lane's own row's
-// count and offset travel with the batch, a second register set prefetches the next batch at NC = 1.
-template <int NC, int RB, bool VEC, bool OFF, bool BORDER>
-__global__ __launch_bounds__(POIS_THREADS) void poisson_kernel(PoissonArgs a) {
-    __shared__ double red[NC * 128 + 2];
-    __shared__ double redh[BORDER ? NC * 128 + 1 : 1];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const double b0 = a.beta0 ? *a.beta0 : 0.0;
-    double s0 = 0.0, sw = 0.0, ll = 0.0;
-    double2 b[NC], g[NC], h[BORDER ? NC : 1];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int col = c * 128 + 2 * lane;
-        b[c].x = col < a.p ? a.beta[col] : 0.0;
-        b[c].y = col + 1 < a.p ? a.beta[col + 1] : 0.0;
-        g[c].x = 0.0; g[c].y = 0.0;
-        if constexpr (BORDER) { h[c].x = 0.0; h[c].y = 0.0; }
-    }
-    const int myrow = row_of_lane<RB>(lane);
-    const bool rep = (lane & rep_mask<RB>()) == 0;
-    const int64_t nbatch = (a.n + RB - 1) / RB;
-    const int64_t stride = (int64_t)gridDim.x * POIS_WAVES;
-
-    auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], double& yv, double& ov) {
-        const int64_t row0 = bt * RB;
-        const int64_t ry = min(row0 + myrow, a.n - 1);
-        const double ytmp = a.y[ry];
-        const double otmp = OFF ? a.off[ry] : 0.0;
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            const int64_t r = min(row0 + i, a.n - 1);
-            const double* rowp = a.X + r * a.ldx;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int col = c * 128 + 2 * lane;
-                const int c0 = col < a.p ? col : 0;                   // clamped columns meet beta = 0
-                if (VEC) {                                            // VEC implies p even: a pair never straddles p
-                    x[i][c] = pois_ld2(rowp + c0);
-                } else {
-                    x[i][c].x = __builtin_nontemporal_load(rowp + c0);
-                    x[i][c].y = __builtin_nontemporal_load(rowp + (col + 1 < a.p ? col + 1 : 0));
-                }
-            }
-        }
-        yv = ytmp;
-        ov = otmp;
-    };
-    auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const double yraw, const double oraw) {
-        const int64_t row0 = bt * RB;
-        double dot[RB];
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) s = fma(x[i][c].x, b[c].x, fma(x[i][c].y, b[c].y, s));
-            dot[i] = s;
-        }
-        const int64_t r = row0 + myrow;
-        const bool valid = r < a.n;
-        const double yv = valid ? yraw : 0.0;
-        const double eta = merged_reduce<RB>(dot, lane) + b0 + (OFF ? oraw : 0.0);
-        const double mu = exp_full(eta);
-        const double resid = valid ? (yv - mu) : 0.0;
-        if (valid && rep) {
-            if (a.w_out) a.w_out[r] = mu;
-            ll += yv * eta - mu;
-            s0 += resid;
-        }
-        rank1_update<RB, NC, 0>(resid, x, g);
-        if constexpr (BORDER) {                 // X'mu and sum mu of the same rows (a clamped row past n weighs nothing)
-            const double wv = valid ? mu : 0.0;
-            if (rep) sw += wv;
-            rank1_update<RB, NC, 0>(wv, x, h);
-        }
-    };
-
-    int64_t bt = (int64_t)blockIdx.x * POIS_WAVES + wave;
-    if constexpr (NC == 1) {
-        double2 xa[RB][NC], xb[RB][NC];
-        double ya = 0.0, yb = 0.0, oa = 0.0, ob = 0.0;
-        if (a.n > 0) {
-            load_batch(bt, xa, ya, oa);
-            for (; bt < nbatch; bt += 2 * stride) {
-                const int64_t b1 = bt + stride, b2 = bt + 2 * stride;
-                load_batch(b1, xb, yb, ob);
-                process(bt, xa, ya, oa);
-                load_batch(b2, xa, ya, oa);
-                if (b1 < nbatch) process(b1, xb, yb, ob);
-            }
-        }
-    } else {
-        for (; bt < nbatch; bt += stride) {
-            double2 x[RB][NC];
-            double yv, ov;
-            load_batch(bt, x, yv, ov);
-            process(bt, x, yv, ov);
-        }
-    }
-
-    // block reduction: waves add into LDS one after another (fixed order)
-    ll = wave_allreduce_sum(ll);
-    s0 = wave_allreduce_sum(s0);
-    if constexpr (BORDER) sw = wave_allreduce_sum(sw);
-    for (int wv = 0; wv < POIS_WAVES; ++wv) {
-        if (wave == wv) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                double* dst = red + c * 128 + 2 * lane;
-                if (wv == 0) { dst[0] = g[c].x; dst[1] = g[c].y; }
-                else { dst[0] += g[c].x; dst[1] += g[c].y; }
-                if constexpr (BORDER) {
-                    double* dh = redh + c * 128 + 2 * lane;
-                    if (wv == 0) { dh[0] = h[c].x; dh[1] = h[c].y; }
-                    else { dh[0] += h[c].x; dh[1] += h[c].y; }
-                }
-            }
-            if (lane == 0) {
-                if (wv == 0) { red[NC * 128] = ll; red[NC * 128 + 1] = s0; }
-                else { red[NC * 128] += ll; red[NC * 128 + 1] += s0; }
-                if constexpr (BORDER) { if (wv == 0) redh[NC * 128] = sw; else redh[NC * 128] += sw; }
-            }
-        }
-        __syncthreads();
-    }
-    double* gp = a.gpart + (int64_t)blockIdx.x * (NC * 128);
-    for (int col = tid; col < NC * 128; col += POIS_THREADS) gp[col] = red[col];
-    if (tid == 0) { a.llpart[blockIdx.x] = red[NC * 128]; a.s0part[blockIdx.x] = red[NC * 128 + 1]; }
-    if constexpr (BORDER) {
-        double* hp = a.hpart + (int64_t)blockIdx.x * (NC * 128);
-        for (int col = tid; col < NC * 128; col += POIS_THREADS) hp[col] = redh[col];
-        if (tid == 0) a.swpart[blockIdx.x] = redh[NC * 128];
-    }
-}
 
 // ---- once per partition: [sum lgamma(y + 1), sum y, sum e^o, rows with y < 0 or a non-finite y / o] --------------------
 __global__ __launch_bounds__(256) void poisson_const_kernel(const double* __restrict__ y, const double* __restrict__ off,
@@ -258,39 +91,18 @@ __global__ void poisson_start_kernel(double* __restrict__ beta, int pe, int icpt
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static int pois_nc(int p) {
-    const int chunks = (p + 127) / 128;
-    int nc = 1;
-    while (nc < chunks) nc *= 2;
-    return nc;
-}
-
-static int pois_rb(int nc) { return nc <= 2 ? 8 : nc == 4 ? 4 : nc == 8 ? 2 : 1; }
-
-static int pois_blocks(int64_t n, int rb) {
-    const int64_t nbatch = (n + rb - 1) / rb;
-    int64_t blocks = (nbatch + POIS_WAVES * 4 - 1) / (POIS_WAVES * 4);   // >= 4 batches per wave
-    return (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), POIS_MAX_BLOCKS);
-}
-
 struct PoisLayout {
-    size_t off_gpart, off_llpart, off_s0part, off_hpart, off_swpart, off_border, off_cpart, off_cst, off_w, off_y, off_o, off_gram,
-        total;
+    CountScratchOff sc;
+    size_t off_cpart, off_cst, off_w, off_y, off_o, off_gram, total;
 };
 
 // pass scratch; row_step > 1: room for the gathered counts and offsets of a strided partition
 static PoisLayout pois_layout(int64_t max_rows, int p, int64_t row_step) {
     PoisLayout l{};
     const int64_t n = std::max<int64_t>(max_rows, 1);
-    const size_t gp = (size_t)POIS_MAX_BLOCKS * pois_nc(p) * 128 * sizeof(double);
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
-    l.off_gpart = take(gp);
-    l.off_llpart = take(8 * (size_t)POIS_MAX_BLOCKS);
-    l.off_s0part = take(8 * (size_t)POIS_MAX_BLOCKS);
-    l.off_hpart = take(gp);
-    l.off_swpart = take(8 * (size_t)POIS_MAX_BLOCKS);
-    l.off_border = take(8 * (size_t)(p + 1));
+    l.sc = count_scratch_take(take, p);
     l.off_cpart = take(8 * 4 * (size_t)POIS_CONST_BLOCKS);
     l.off_cst = take(8 * 4);
     l.off_w = take(8 * (size_t)n);
@@ -315,57 +127,19 @@ int pois_ll_fix(double* ll, const double* cst, hipStream_t s) {
     return DLSA_OK;
 }
 
-template <int NC, int RB, bool VEC, bool OFF>
-static void launch_pois_b(const PoissonArgs& a, bool border, int blocks, hipStream_t s) {
-    if (border) hipLaunchKernelGGL((poisson_kernel<NC, RB, VEC, OFF, true>), dim3(blocks), dim3(POIS_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((poisson_kernel<NC, RB, VEC, OFF, false>), dim3(blocks), dim3(POIS_THREADS), 0, s, a);
-}
-template <int NC, int RB>
-static void launch_pois(const PoissonArgs& a, bool vec, bool border, int blocks, hipStream_t s) {
-    if (vec) {
-        if (a.off) launch_pois_b<NC, RB, true, true>(a, border, blocks, s);
-        else launch_pois_b<NC, RB, true, false>(a, border, blocks, s);
-    } else {
-        if (a.off) launch_pois_b<NC, RB, false, true>(a, border, blocks, s);
-        else launch_pois_b<NC, RB, false, false>(a, border, blocks, s);
-    }
+int pois_gather(const double* v, int64_t first, int64_t step, int64_t n, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(poisson_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, first, step, n, out);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
 }
 
-// One partition at a fixed beta (pe = p + intercept entries, intercept first).  H (nullable) needs w (mu per row: the
-// Gram's weights); g, loglik (the sum of y eta - mu, without the constant), w nullable otherwise.
+// One partition at a fixed beta (count_pass with the Poisson row): w is mu per row, loglik the sum of y eta - mu, without the
+// constant.
 static int pois_pass_impl(const double* X, int64_t ldx, const double* y, const double* off, const double* beta, int64_t n, int p,
                           int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w, char* ws, const PoisLayout& l,
                           hipStream_t s) {
-    const int nc = pois_nc(p), rb = pois_rb(nc);
-    const bool border = H && intercept;
-    PoissonArgs a{};
-    a.X = X; a.y = y; a.off = off; a.beta = intercept ? beta + 1 : beta; a.beta0 = intercept ? beta : nullptr;
-    a.w_out = w; a.ldx = ldx; a.n = n; a.p = p;
-    a.gpart = (double*)(ws + l.off_gpart); a.llpart = (double*)(ws + l.off_llpart); a.s0part = (double*)(ws + l.off_s0part);
-    a.hpart = (double*)(ws + l.off_hpart); a.swpart = (double*)(ws + l.off_swpart);
-    const bool vec = (ldx % 2 == 0) && (p % 2 == 0) && (((uintptr_t)X & 15) == 0);
-    const int blocks = pois_blocks(n, rb);
-    switch (nc) {
-        case 1: launch_pois<1, 8>(a, vec, border, blocks, s); break;
-        case 2: launch_pois<2, 8>(a, vec, border, blocks, s); break;
-        case 4: launch_pois<4, 4>(a, vec, border, blocks, s); break;
-        case 8: launch_pois<8, 2>(a, vec, border, blocks, s); break;
-        default: launch_pois<16, 1>(a, vec, border, blocks, s); break;
-    }
-    DLSA_HIP_CHECK(hipGetLastError());
-    if (g || loglik) {
-        logit_finish_launch(a.gpart, a.llpart, blocks, nc * 128, p, (g && intercept) ? g + 1 : g, loglik, s,
-                            (g && intercept) ? a.s0part : nullptr, (g && intercept) ? g : nullptr);
-        DLSA_HIP_CHECK(hipGetLastError());
-    }
-    if (!H) return DLSA_OK;
-    void* gws = ws + l.off_gram;
-    const size_t gws_bytes = l.total - l.off_gram;
-    if (!intercept) return gram_impl_f64(X, ldx, w, n, p, H, ldh, 0, gws, gws_bytes, s);
-    double* bd = (double*)(ws + l.off_border);          // [sum mu | X'mu]: row 0 of [1 | X]' diag(mu) [1 | X]
-    logit_finish_launch(a.hpart, a.swpart, blocks, nc * 128, p, bd + 1, bd, s, nullptr, nullptr);
-    DLSA_HIP_CHECK(hipGetLastError());
-    return gram_icpt_impl(X, ldx, w, n, p, H, ldh, gws, gws_bytes, s, bd);
+    return count_pass(PoisRow{}, X, ldx, y, off, beta, n, p, intercept, H, ldh, g, loglik, w, nullptr, count_scratch_at(ws, l.sc),
+                      ws + l.off_gram, l.total - l.off_gram, s);
 }
 
 // The Newton loop of the Poisson fits (dense rows here, raw one-hot rows in onehot_poisson.hip): `eval` is the only part that
@@ -374,12 +148,7 @@ int pois_fit_core(const char* who, const double* y, const double* offset, const 
                   const int64_t* part_rows_host, int64_t row_step, int K, int pe, int icpt_col, double tol, int max_iter,
                   double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
                   const PoisFitBufs& b, const PoisEval& eval, hipStream_t s) {
-    double* stats = b.state;            // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] sum y eta - mu
-    double* beta = b.state + 8;
-    double* prev = beta + pe;
-    double* delta = prev + pe;
-    double* g = delta + pe;
-    double* Lf = b.Lf;
+    double *stats = b.st.stats, *beta = b.st.beta, *prev = b.st.prev, *delta = b.st.delta, *g = b.st.g, *Lf = b.st.Lf;
     int overall = DLSA_OK;
     for (int k = 0; k < K; ++k) {
         const int64_t nk = part_rows_host[k];
@@ -391,17 +160,18 @@ int pois_fit_core(const char* who, const double* y, const double* offset, const 
         int st_k = DLSA_PART_EMPTY, iters = 0;
         double ll = 0.0, cst[4] = {0.0, 0.0, 0.0, 0.0};
         if (nk > 0) {
+            int rc = DLSA_OK;
             if (row_step > 1) {                               // the partition's counts and offsets, gathered once (8 bytes per row each)
-                const dim3 grid((unsigned)((nk + 255) / 256));
-                hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, y, part_first_host[k], row_step, nk, b.ybuf);
+                rc = pois_gather(y, part_first_host[k], row_step, nk, b.ybuf, s);
+                if (rc) return rc;
                 yk = b.ybuf;
                 if (offset) {
-                    hipLaunchKernelGGL(poisson_gather_kernel, grid, dim3(256), 0, s, offset, part_first_host[k], row_step, nk, b.obuf);
+                    rc = pois_gather(offset, part_first_host[k], row_step, nk, b.obuf, s);
+                    if (rc) return rc;
                     ok = b.obuf;
                 }
-                DLSA_HIP_CHECK(hipGetLastError());
             }
-            int rc = pois_const(yk, ok, nk, b.cpart, b.cst, s);
+            rc = pois_const(yk, ok, nk, b.cpart, b.cst, s);
             if (rc) return rc;
             DLSA_HIP_CHECK(hipMemcpyAsync(cst, b.cst, sizeof(cst), hipMemcpyDeviceToHost, s));
             DLSA_HIP_CHECK(hipStreamSynchronize(s));
@@ -466,9 +236,7 @@ int pois_fit_core(const char* who, const double* y, const double* offset, const 
         if (n_iter_host) n_iter_host[k] = iters;
         if (status_host) status_host[k] = st_k;
         if (loglik_host) loglik_host[k] = ll;
-        if (st_k == DLSA_PART_NOT_CONVERGED && overall == DLSA_OK) overall = DLSA_ERR_NOT_CONVERGED;
-        if (st_k == DLSA_PART_NOT_SPD && overall == DLSA_OK) overall = DLSA_ERR_NOT_SPD;
-        if (st_k == DLSA_PART_NAN && overall == DLSA_OK) overall = DLSA_ERR_NAN;
+        pois_fold_status(st_k, overall);
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;
@@ -532,8 +300,7 @@ int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const do
     PoisFitBufs b{};
     b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
     b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
-    b.state = (double*)(wsc + align_up(l.total, 256));
-    b.Lf = (double*)(wsc + align_up(l.total, 256) + align_up(8 * (size_t)(4 * pe + 8), 256));
+    b.st = pois_state_at(wsc + align_up(l.total, 256), pe);
     double* wv = (double*)(wsc + l.off_w);
     const int64_t pitch = ldx * row_step;                     // rows first, first + step, ...: a strided view, no copy of X
     const PoisEval eval = [=](int k, const double* yk, const double* ok, int64_t nk, const double* beta, double* Hk, double* g,

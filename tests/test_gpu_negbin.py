@@ -50,9 +50,11 @@ def _theta_terms_mp(y, mu, alpha):
     return s, i, pe
 
 
-def _check_pass(eng, X, y, o, beta, alpha, intercept, tol=1e-12, theta=True):
-    Xd, yd, od, bd = _dev(X, y, o, beta)
-    H, g, ll, w, mu, tt = eng.negbin_pass(Xd, yd, bd, alpha, offset=od, fit_intercept=intercept, want_w=True, want_theta=True)
+def _check_pass(eng, X, y, o, beta, alpha, intercept, tol=1e-12, theta=True, Xd=None):
+    """Xd: the device tensor to pass for X (a view with its own pitch / alignment); default a contiguous copy"""
+    Xc, yd, od, bd = _dev(X, y, o, beta)
+    H, g, ll, w, mu, tt = eng.negbin_pass(Xc if Xd is None else Xd, yd, bd, alpha, offset=od, fit_intercept=intercept, want_w=True,
+                                          want_theta=True)
     llr, gr, Hr, mur, sr, ir, per = nr.terms(X, y, beta, alpha, o, intercept)
     assert abs(float(ll.item()) - llr) <= tol * abs(llr), (float(ll.item()), llr)
     assert rel(g.cpu().numpy(), gr) <= tol, rel(g.cpu().numpy(), gr)
@@ -80,15 +82,47 @@ def _check_pass(eng, X, y, o, beta, alpha, intercept, tol=1e-12, theta=True):
         assert e_k <= 10 * max(e_ref, floor), (name, e_k, e_ref, floor)
 
 
+def _away_from_optimum(pe):
+    return np.linspace(-0.8, 0.6, pe) / max(1.0, math.sqrt(pe / 10))
+
+
 @pytest.mark.parametrize("p", WIDTHS)
 @pytest.mark.parametrize("alpha", [0.05, 0.5, 5.0])
 @pytest.mark.parametrize("intercept,offset", [(False, False), (True, False), (False, True), (True, True)])
 def test_pass_matches_reference(eng, p, alpha, intercept, offset):
     n = 3001
     X, y, o = nr.data(10 + p, n, p, intercept, offset, alpha)
-    pe = p + intercept
-    beta = np.linspace(-0.8, 0.6, pe) / max(1.0, math.sqrt(pe / 10))       # away from the optimum
-    _check_pass(eng, X, y, o, beta, alpha, intercept)
+    _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), alpha, intercept)
+
+
+# Shapes of the row pass no 3001-row case reaches (as tests/test_gpu_poisson.py: NC = 16 with one row per wave; fewer rows than one
+# batch, where every prefetch at NC = 1 is a clamped re-read of row n - 1; one full and one partial batch at NC = 2).  theta=False:
+# the theta kernel is not the pass's, and at n = 1 its sums can be exactly 0.
+SHORT_AND_WIDE = [(67, 1025), (67, 1030), (1, 1), (1, 2), (5, 7), (7, 8), (9, 130), (13, 128)]
+
+
+@pytest.mark.parametrize("n,p", SHORT_AND_WIDE)
+@pytest.mark.parametrize("intercept,offset", [(False, False), (True, True)])
+def test_pass_short_and_wide_shapes(eng, n, p, intercept, offset):
+    X, y, o = nr.data(900 + p + n, n, p, intercept, offset, 0.5)
+    _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), 0.5, intercept, theta=False)
+
+
+@pytest.mark.parametrize("p", [8, 130, 1030])
+@pytest.mark.parametrize("pad", [3, 2])
+@pytest.mark.parametrize("intercept,offset", [(False, False), (True, True)])
+def test_pass_even_width_on_the_scalar_loads(eng, p, pad, intercept, offset):
+    """an even p takes the scalar loads only through the rows' pitch or base: columns 1 .. p of a buffer with p + 3 columns (an odd
+    pitch) and of one with p + 2 (an even pitch, the base 8 bytes off a 16-byte boundary), passed as views, without a copy"""
+    n = 67
+    X, y, o = nr.data(900 + p + n, n, p, intercept, offset, 0.5)
+    big = torch.zeros((n, p + pad), dtype=torch.float64, device="cuda")
+    Xd = big[:, 1:1 + p]
+    Xd.copy_(torch.from_numpy(X))
+    assert Xd.stride(0) == p + pad and Xd.stride(1) == 1
+    if pad == 2:
+        assert Xd.data_ptr() % 16 == 8
+    _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), 0.5, intercept, theta=False, Xd=Xd)
 
 
 def test_special_functions(eng):

@@ -41,9 +41,10 @@ def _data(seed, n, p, intercept, offset, b0=0.3, scale=1.0):
     return X, y, o
 
 
-def _check_pass(eng, X, y, o, beta, intercept, tol=1e-12):
-    Xd, yd, od, bd = _dev(X, y, o, beta)
-    H, g, ll, w = eng.poisson_pass(Xd, yd, bd, offset=od, fit_intercept=intercept, want_w=True)
+def _check_pass(eng, X, y, o, beta, intercept, tol=1e-12, Xd=None):
+    """Xd: the device tensor to pass for X (a view with its own pitch / alignment); default a contiguous copy"""
+    Xc, yd, od, bd = _dev(X, y, o, beta)
+    H, g, ll, w = eng.poisson_pass(Xc if Xd is None else Xd, yd, bd, offset=od, fit_intercept=intercept, want_w=True)
     llr, gr, Hr, mur = pr.terms(X, y, beta, o, intercept)
     assert abs(float(ll.item()) - llr) <= tol * abs(llr), (float(ll.item()), llr)
     assert rel(g.cpu().numpy(), gr) <= tol, rel(g.cpu().numpy(), gr)
@@ -53,14 +54,46 @@ def _check_pass(eng, X, y, o, beta, intercept, tol=1e-12):
     assert np.array_equal(Hn, Hn.T)
 
 
+def _away_from_optimum(pe):
+    return np.linspace(-0.8, 0.6, pe) / max(1.0, math.sqrt(pe / 10))
+
+
 @pytest.mark.parametrize("p", WIDTHS)
 @pytest.mark.parametrize("intercept,offset", [(False, False), (True, False), (False, True), (True, True)])
 def test_pass_matches_reference(eng, p, intercept, offset):
     n = 3001
     X, y, o = _data(10 + p, n, p, intercept, offset)
-    pe = p + intercept
-    beta = np.linspace(-0.8, 0.6, pe) / max(1.0, math.sqrt(pe / 10))       # away from the optimum
-    _check_pass(eng, X, y, o, beta, intercept)
+    _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), intercept)
+
+
+# Shapes of the row pass no 3001-row case reaches.  p > 1024 is NC = 16 with one row per wave (1025: the scalar loads, 1030: the
+# 16-byte ones); the short ones have fewer rows than one batch of 8 (or a single row), so at NC = 1 every prefetch of the second
+# register set is a clamped re-read of row n - 1 and most waves process nothing, and at NC = 2 there is one full and one partial batch.
+SHORT_AND_WIDE = [(67, 1025), (67, 1030), (1, 1), (1, 2), (5, 7), (7, 8), (9, 130), (13, 128)]
+
+
+@pytest.mark.parametrize("n,p", SHORT_AND_WIDE)
+@pytest.mark.parametrize("intercept,offset", [(False, False), (True, True)])
+def test_pass_short_and_wide_shapes(eng, n, p, intercept, offset):
+    X, y, o = _data(900 + p + n, n, p, intercept, offset)
+    _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), intercept)
+
+
+@pytest.mark.parametrize("p", [8, 130, 1030])
+@pytest.mark.parametrize("pad", [3, 2])
+@pytest.mark.parametrize("intercept,offset", [(False, False), (True, True)])
+def test_pass_even_width_on_the_scalar_loads(eng, p, pad, intercept, offset):
+    """an even p takes the scalar loads only through the rows' pitch or base: columns 1 .. p of a buffer with p + 3 columns (an odd
+    pitch) and of one with p + 2 (an even pitch, the base 8 bytes off a 16-byte boundary), passed as views, without a copy"""
+    n = 67
+    X, y, o = _data(900 + p + n, n, p, intercept, offset)
+    big = torch.zeros((n, p + pad), dtype=torch.float64, device="cuda")
+    Xd = big[:, 1:1 + p]
+    Xd.copy_(torch.from_numpy(X))
+    assert Xd.stride(0) == p + pad and Xd.stride(1) == 1
+    if pad == 2:
+        assert Xd.data_ptr() % 16 == 8
+    _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), intercept, Xd=Xd)
 
 
 def test_pass_exp_is_exact_to_two_ulp_over_the_range(eng):

@@ -139,6 +139,45 @@ def test_negbin_entries_validate_arguments_without_a_gpu():
     assert rc == 1 and "null" in _lib.last_error()
 
 
+# (max_rows, p) -> dlsa_negbin_workspace_bytes for (intercept, row_step) = (0, 1), (0, 25), (1, 1), (1, 25): the values of the library
+# before the pass scratch went through count_pass.h's one take list
+WORKSPACE_BYTES = {
+    (0, 1): (4670976, 4671488, 4670976, 4671488),
+    (0, 100): (5541120, 5541632, 5542656, 5543168),
+    (0, 130): (11102720, 11103232, 11104768, 11105280),
+    (0, 600): (62886912, 62887424, 62896640, 62897152),
+    (0, 1025): (151528960, 151529472, 151545344, 151545856),
+    (1, 1): (4670976, 4671488, 4670976, 4671488),
+    (1, 100): (5541120, 5541632, 5542656, 5543168),
+    (1, 130): (11102720, 11103232, 11104768, 11105280),
+    (1, 600): (62886912, 62887424, 62896640, 62897152),
+    (1, 1025): (151528960, 151529472, 151545344, 151545856),
+    (3001, 1): (4980736, 5028864, 4980736, 5028864),
+    (3001, 100): (6637312, 6685440, 6638848, 6686976),
+    (3001, 130): (13509632, 13557760, 13511680, 13559808),
+    (3001, 600): (89148928, 89197056, 89158656, 89206784),
+    (3001, 1025): (227336192, 227384320, 227352576, 227400704),
+    (10 ** 6, 1): (37185536, 61038080, 37185536, 61038080),
+    (10 ** 6, 100): (87601152, 111453696, 87602688, 111455232),
+    (10 ** 6, 130): (175737856, 199590400, 175739904, 199592448),
+    (10 ** 6, 600): (183744000, 207596544, 183753728, 207606272),
+    (10 ** 6, 1025): (319047680, 342900224, 319064064, 342916608),
+}
+
+
+def test_workspace_bytes_are_pinned():
+    """the layout takes the pass's six scratch arrays through the helper it shares with poisson.hip: sizes, order and alignment are
+    those of the list it replaced"""
+    import __graft_entry__ as g
+    g.build()
+    from dlsa_amd import _lib
+    lib = _lib.load()
+    assert len(WORKSPACE_BYTES) == 4 * 5
+    for (n, p), want in WORKSPACE_BYTES.items():
+        got = tuple(lib.dlsa_negbin_workspace_bytes(n, p, icpt, step) for icpt in (0, 1) for step in (1, 25))
+        assert got == want, (n, p, got, want)
+
+
 def test_package_exports_the_negbin_interface():
     import inspect
     import dlsa_amd

@@ -126,3 +126,38 @@ def test_workspace_query_is_monotone(lib):
                     prev = b
                 # the strided form gathers counts and offsets: never less than the contiguous one
                 assert lib.dlsa_poisson_workspace_bytes(10 ** 6, p, icpt, step) >= lib.dlsa_poisson_workspace_bytes(10 ** 6, p, icpt, 1)
+
+
+# (max_rows, p) -> dlsa_poisson_workspace_bytes for (intercept, row_step) = (0, 1), (0, 25), (1, 1), (1, 25): the values of the library
+# before the pass scratch went through count_pass.h's one take list
+WORKSPACE_BYTES = {
+    (0, 1): (4523264, 4523776, 4523264, 4523776),
+    (0, 100): (5393408, 5393920, 5394944, 5395456),
+    (0, 130): (10955008, 10955520, 10957056, 10957568),
+    (0, 600): (62739200, 62739712, 62748928, 62749440),
+    (0, 1025): (151381248, 151381760, 151397632, 151398144),
+    (1, 1): (4523264, 4523776, 4523264, 4523776),
+    (1, 100): (5393408, 5393920, 5394944, 5395456),
+    (1, 130): (10955008, 10955520, 10957056, 10957568),
+    (1, 600): (62739200, 62739712, 62748928, 62749440),
+    (1, 1025): (151381248, 151381760, 151397632, 151398144),
+    (3001, 1): (4809216, 4857344, 4809216, 4857344),
+    (3001, 100): (6465792, 6513920, 6467328, 6515456),
+    (3001, 130): (13338112, 13386240, 13340160, 13388288),
+    (3001, 600): (88977408, 89025536, 88987136, 89035264),
+    (3001, 1025): (227164672, 227212800, 227181056, 227229184),
+    (10 ** 6, 1): (29038080, 45038080, 29038080, 45038080),
+    (10 ** 6, 100): (79453696, 95453696, 79455232, 95455232),
+    (10 ** 6, 130): (167590400, 183590400, 167592448, 183592448),
+    (10 ** 6, 600): (175596544, 191596544, 175606272, 191606272),
+    (10 ** 6, 1025): (310900224, 326900224, 310916608, 326916608),
+}
+
+
+def test_workspace_bytes_are_pinned(lib):
+    """the layout takes the pass's six scratch arrays through the helper it shares with negbin.hip: sizes, order and alignment are
+    those of the list it replaced"""
+    assert len(WORKSPACE_BYTES) == 4 * 5
+    for (n, p), want in WORKSPACE_BYTES.items():
+        got = tuple(lib.dlsa_poisson_workspace_bytes(n, p, icpt, step) for icpt in (0, 1) for step in (1, 25))
+        assert got == want, (n, p, got, want)
