@@ -17,6 +17,7 @@ import glob
 import hashlib
 import json
 import os
+import signal
 import subprocess
 import sys
 
@@ -46,7 +47,7 @@ KERNELS = {
     "logit_img_p500": dict(cmd=["bench/wide_syrk_probe.py", "1000000", "500"], pat="logit_kernel<4, 4, true, false, true>",
                            src=["logit.hip", "rowdot.h", "logistic.h", "common.h"], rows=1_000_000, p=500, elem=8, kind="logit"),
     "onehot_c4": dict(cmd=["bench/onehot_one.py", "14000000", "14"], pat="oh_gram_kernel",
-                      src=["onehot.hip", "common.h"], rows=1_000_000, p=260, elem=8, kind="onehot"),
+                      src=["onehot.hip", "onehot_plan.h", "onehot_pass.h", "logistic.h", "common.h"], rows=1_000_000, p=260, elem=8, kind="onehot"),
 }
 
 PASSES = {
@@ -83,8 +84,21 @@ def latest_evidence_path(tag):
     return evidence_path(ROUNDS[0], tag)
 
 
+START_UP_S = 120.0        # interpreter + torch + the profiler + generating the driver's rows (a pass of onehot_c4 ends within 5 s)
+
+
+def pass_time_limit(tag):
+    """Seconds one rocprofv3 child may take: the driver's start-up plus a hundred times what the kernel's launches took under the
+    counters in the committed evidence (onehot_c4: 46 launches of 0.158 ms -> 120.7 s)."""
+    path = latest_evidence_path(tag)
+    kk = next(iter(json.load(open(path))["kernels"].values()), {}) if os.path.exists(path) else {}
+    return START_UP_S + 100.0 * kk.get("launches", 0) * kk.get("duration_ms_under_pmc", 0.0) / 1e3
+
+
 def collect(round_tag, tag):
+    """0, or non-zero when a pass failed or ran out of time: no further pass is started then and no evidence is written."""
     k = KERNELS[tag]
+    limit = pass_time_limit(tag)
     out = os.path.join(ROOT, "gpurun_out", "pmc_ev_%s" % tag)
     os.makedirs(out, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
@@ -92,9 +106,17 @@ def collect(round_tag, tag):
         cmd = ["rocprofv3", "--kernel-trace", "--pmc"] + ctrs + ["-d", os.path.join(out, name), "-o", name, "--output-format", "csv", "--",
                                                                  "python3", os.path.join(ROOT, k["cmd"][0])] + k["cmd"][1:]
         with open(os.path.join(out, name + ".log"), "w") as log:
-            rc = subprocess.call(cmd, cwd=ROOT, env=env, stdout=log, stderr=subprocess.STDOUT)
+            child = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=log, stderr=subprocess.STDOUT, start_new_session=True)
+            try:
+                rc = child.wait(timeout=limit)
+            except subprocess.TimeoutExpired:
+                os.killpg(child.pid, signal.SIGKILL)            # the profiler and the driver under it
+                child.wait()
+                rc = 124
         if rc:
-            print("[pmc_evidence] %s pass %s: rocprofv3 exit code %d (see %s)" % (tag, name, rc, os.path.join(out, name + ".log")), file=sys.stderr)
+            print("[pmc_evidence] %s pass %s: %s (see %s); stopping" % (tag, name, "no end within %.0f s" % limit if rc == 124 else
+                  "rocprofv3 exit code %d" % rc, os.path.join(out, name + ".log")), file=sys.stderr)
+            return rc
     res = {}
     for f in sorted(glob.glob(os.path.join(out, "*", "*_counter_collection.csv"))):
         agg = collections.defaultdict(lambda: collections.defaultdict(float))
@@ -134,14 +156,18 @@ def collect(round_tag, tag):
             "%.4g" % d["hbm_bytes"] if "hbm_bytes" in d else "-", "%.2f" % d["valu_per_mfma"] if "valu_per_mfma" in d else "-"), flush=True)
     if not res:
         print("[pmc_evidence] %s: no kernel matched %r" % (tag, k["pat"]), file=sys.stderr)
+    return 0
 
 
 def main():
     round_tag = sys.argv[1] if len(sys.argv) > 1 else ROUNDS[0]
     tags = sys.argv[2:] or list(KERNELS)
     for t in tags:
-        collect(round_tag, t)
+        rc = collect(round_tag, t)
+        if rc:
+            return rc
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

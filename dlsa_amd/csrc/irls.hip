@@ -19,6 +19,7 @@
 // (models.py:114,130); Sig_invMcoef = Sig_inv . coef (models.py:131).  One D2H copy of 4 doubles
 // per iteration is the only host synchronisation.
 #include "common.h"
+#include "onehot_plan.h"    // the structured passes of onehot.hip
 #include "options.h"
 #include <math.h>
 #include <algorithm>
@@ -68,16 +69,6 @@ bool chol_small_ok(int p);
 int launch_chol_small(const double* A, int64_t lda, int p, const double* rhs, const double* ref, double* Hinv, double* xout,
                       double* stats, hipStream_t s);
 int launch_inv_apply(const double* Linv, int p, const double* rhs, const double* ref, double* xout, double* stats, hipStream_t s);
-}  // namespace dlsa
-struct dlsa_onehot_plan;
-namespace dlsa {
-size_t onehot_workspace_bytes_impl(const dlsa_onehot_plan* pl, int64_t n);
-int onehot_plan_p(const dlsa_onehot_plan* pl);
-int onehot_logit_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
-                           const double* y, const double* beta, int64_t n, double* w_out, double* g, double* loglik,
-                           void* ws, size_t ws_bytes, hipStream_t s);
-int onehot_gram_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
-                     const double* w, int64_t n, double* H, int64_t ldh, void* ws, size_t ws_bytes, hipStream_t s, bool irls_weights);
 int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
 int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
 int launch_matvec_axpy(const double* A, int64_t lda, const double* x, int p, double alpha, const double* z, double beta, double* y, hipStream_t s);
@@ -1130,6 +1121,49 @@ __global__ void gather_strided_kernel(const double* __restrict__ y, int64_t firs
     if (j < n) out[j] = y[first + j * step];
 }
 
+// One-hot designs: the same fit on raw numerics + level codes (onehot.hip), never materialising the dense matrix.  Partitions
+// are (first row, rows, common row step): partition_id = i % K (models.py:33) is first = 0..K-1, step = K -- strided VIEWS of
+// the raw numerics and the level codes (row pitches ldn * step, ldc * step), nothing gathered but the partition's labels
+// (8 bytes per row, step > 1 only); contiguous offsets are the step = 1 case.
+static int onehot_irls_fit_rows(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                const double* y, const int64_t* first, const int64_t* rows, int64_t row_step, int K, double tol,
+                                int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                                double* loglik_host, void* ws, size_t ws_bytes, void* stream) {
+    const int p = onehot_plan_p(plan);
+    int64_t max_rows = 0;
+    std::vector<int64_t> offs((size_t)K + 1, 0);
+    for (int k = 0; k < K; ++k) {
+        max_rows = std::max(max_rows, rows[k]);
+        offs[(size_t)k + 1] = offs[(size_t)k] + rows[k];
+    }
+    const size_t ybytes = row_step > 1 ? align_up((size_t)std::max<int64_t>(max_rows, 1) * sizeof(double), 256) : 0;
+    const int64_t pn = ldn * row_step, pc = ldc * row_step;
+    auto make_data = [=](int k, int64_t, char* extra, hipStream_t st) {
+        const double* numk = num ? num + first[k] * ldn : nullptr;
+        const int32_t* codesk = codes ? codes + first[k] * ldc : nullptr;
+        const double* yk = y + first[k];
+        const int64_t nk = rows[k];
+        if (row_step > 1 && nk > 0) {
+            double* ybuf = (double*)extra;
+            hipLaunchKernelGGL(gather_strided_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, y, first[k], row_step, nk, ybuf);
+            yk = ybuf;
+        }
+        IrlsData d;
+        d.logit = [=](const double* beta, int64_t nrows, double* w, double* g, double* ll, const IrlsBuffers& b, hipStream_t s) {
+            return onehot_logit_pass_impl(plan, numk, pn, codesk, pc, yk, beta, nrows, w, g, ll, b.ws_pass, b.ws_pass_bytes, s);
+        };
+        d.gram = [=](const double* w, int64_t nrows, double* H, const IrlsBuffers& b, hipStream_t s) {
+            return onehot_gram_impl(plan, numk, pn, codesk, pc, w, nrows, H, p, b.ws_pass, b.ws_pass_bytes, s, true);
+        };
+        // (no own-Hessian steps here: measured on config 4's structured shard they halve the iterations -- 10 -> 5 per partition, exact
+        // quadratic convergence -- but two structured Grams per partition cost what the five saved launch-bound iterations did: 13.7 -> 15.2 ms)
+        return d;
+    };
+    return irls_fit_core(make_data, [=](int64_t n) { return onehot_workspace_bytes_impl(plan, n); }, ybytes,
+                         irls_chain_cap(max_rows, 128.0), irls_chain_seed(max_rows, 128.0), offs.data(), K, p, tol, max_iter, coef, Sig_inv, Sig_invMcoef, n_iter_host,
+                         status_host, loglik_host, ws, ws_bytes, stream);
+}
+
 }  // namespace dlsa
 
 extern "C" {
@@ -1332,7 +1366,7 @@ int dlsa_gram_icpt_f64(const double* X, int64_t ldx, const double* w, int64_t n,
     return gram_icpt_impl(X, ldx, w, n, p, H, ldh, ws, ws_bytes, (hipStream_t)stream);
 }
 
-// One-hot designs: the same fit on raw numerics + level codes (onehot.hip), never materialising the dense matrix.
+// The structured logistic fit (onehot_irls_fit_rows above) of contiguous partitions given by their offsets
 size_t dlsa_onehot_irls_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows_per_partition) {
     if (!plan || max_rows_per_partition < 0) return 0;
     return dlsa::align_up(dlsa::irls_layout(max_rows_per_partition, dlsa::onehot_plan_p(plan),
@@ -1347,32 +1381,13 @@ int dlsa_onehot_irls_fit_f64(const dlsa_onehot_plan* plan, const double* num, in
     using namespace dlsa;
     DLSA_REQUIRE(plan && y && part_offsets_host && coef && Sig_inv && Sig_invMcoef, "onehot irls_fit: null argument");
     DLSA_REQUIRE(K > 0 && max_iter > 0 && tol > 0, "onehot irls_fit: bad K/tol/max_iter");
-    const int p = onehot_plan_p(plan);
-    auto make_data = [=](int, int64_t r0, char*, hipStream_t) {
-        const double* numk = num ? num + r0 * ldn : nullptr;
-        const int32_t* codesk = codes ? codes + r0 * ldc : nullptr;
-        const double* yk = y + r0;
-        IrlsData d;
-        d.logit = [=](const double* beta, int64_t nrows, double* w, double* g, double* ll, const IrlsBuffers& b, hipStream_t s) {
-            return onehot_logit_pass_impl(plan, numk, ldn, codesk, ldc, yk, beta, nrows, w, g, ll, b.ws_pass, b.ws_pass_bytes, s);
-        };
-        d.gram = [=](const double* w, int64_t nrows, double* H, const IrlsBuffers& b, hipStream_t s) {
-            return onehot_gram_impl(plan, numk, ldn, codesk, ldc, w, nrows, H, p, b.ws_pass, b.ws_pass_bytes, s, true);
-        };
-        // (no own-Hessian steps here: measured on config 4's structured shard they halve the iterations -- 10 -> 5 per partition, exact
-        // quadratic convergence -- but two structured Grams per partition cost what the five saved launch-bound iterations did: 13.7 -> 15.2 ms)
-        return d;
-    };
-    int64_t max_rows = 0;
-    for (int k = 0; k < K; ++k) max_rows = std::max(max_rows, part_offsets_host[k + 1] - part_offsets_host[k]);
-    return irls_fit_core(make_data, [=](int64_t rows) { return onehot_workspace_bytes_impl(plan, rows); }, 0,
-                         irls_chain_cap(max_rows, 128.0), irls_chain_seed(max_rows, 128.0), part_offsets_host, K, p, tol, max_iter, coef, Sig_inv, Sig_invMcoef,
-                         n_iter_host, status_host, loglik_host, ws, ws_bytes, stream);
+    std::vector<int64_t> rows((size_t)K);             // (offsets that are not monotone: refused by the fit core, as for the dense entry)
+    for (int k = 0; k < K; ++k) rows[(size_t)k] = part_offsets_host[k + 1] - part_offsets_host[k];
+    return onehot_irls_fit_rows(plan, num, ldn, codes, ldc, y, part_offsets_host, rows.data(), 1, K, tol, max_iter, coef, Sig_inv,
+                                Sig_invMcoef, n_iter_host, status_host, loglik_host, ws, ws_bytes, stream);
 }
 
-// The same for partitions given as (first row, rows, common row step): partition_id = i % K (models.py:33) is first = 0..K-1,
-// step = K -- strided VIEWS of the raw numerics and the level codes (row pitches ldn * step, ldc * step), nothing gathered
-// but the partition's labels (8 bytes per row).
+// The same for partitions given as (first row, rows, common row step)
 size_t dlsa_onehot_irls_ex_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows_per_partition, int64_t row_step) {
     if (!plan || max_rows_per_partition < 0 || row_step < 1) return 0;
     const size_t ybuf = row_step > 1 ? dlsa::align_up((size_t)std::max<int64_t>(max_rows_per_partition, 1) * sizeof(double), 256) : 0;
@@ -1386,44 +1401,18 @@ int dlsa_onehot_irls_fit_ex_f64(const dlsa_onehot_plan* plan, const double* num,
     using namespace dlsa;
     DLSA_REQUIRE(plan && y && part_first_host && part_rows_host && coef && Sig_inv && Sig_invMcoef, "onehot irls_fit_ex: null argument");
     DLSA_REQUIRE(K > 0 && max_iter > 0 && tol > 0 && row_step >= 1, "onehot irls_fit_ex: bad K/tol/max_iter/row_step");
-    const int p = onehot_plan_p(plan);
     int64_t max_rows = 0;
-    std::vector<int64_t> offs((size_t)K + 1, 0);
     for (int k = 0; k < K; ++k) {
         DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "onehot irls_fit_ex: negative partition shape");
         max_rows = std::max(max_rows, part_rows_host[k]);
-        offs[(size_t)k + 1] = offs[(size_t)k] + part_rows_host[k];
     }
     const size_t need = dlsa_onehot_irls_ex_workspace_bytes(plan, max_rows, row_step);
     if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
         set_error("onehot irls_fit_ex: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
         return DLSA_ERR_WORKSPACE;
     }
-    const size_t ybytes = row_step > 1 ? align_up((size_t)std::max<int64_t>(max_rows, 1) * sizeof(double), 256) : 0;
-    const int64_t pn = ldn * row_step, pc = ldc * row_step;
-    auto make_data = [=](int k, int64_t, char* extra, hipStream_t st) {
-        const double* numk = num ? num + part_first_host[k] * ldn : nullptr;
-        const int32_t* codesk = codes ? codes + part_first_host[k] * ldc : nullptr;
-        const double* yk = y + part_first_host[k];
-        const int64_t nk = part_rows_host[k];
-        if (row_step > 1 && nk > 0) {
-            double* ybuf = (double*)extra;
-            hipLaunchKernelGGL(gather_strided_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, y, part_first_host[k],
-                               row_step, nk, ybuf);
-            yk = ybuf;
-        }
-        IrlsData d;
-        d.logit = [=](const double* beta, int64_t nrows, double* w, double* g, double* ll, const IrlsBuffers& b, hipStream_t s) {
-            return onehot_logit_pass_impl(plan, numk, pn, codesk, pc, yk, beta, nrows, w, g, ll, b.ws_pass, b.ws_pass_bytes, s);
-        };
-        d.gram = [=](const double* w, int64_t nrows, double* H, const IrlsBuffers& b, hipStream_t s) {
-            return onehot_gram_impl(plan, numk, pn, codesk, pc, w, nrows, H, p, b.ws_pass, b.ws_pass_bytes, s, true);
-        };
-        return d;
-    };
-    return irls_fit_core(make_data, [=](int64_t rows) { return onehot_workspace_bytes_impl(plan, rows); }, ybytes,
-                         irls_chain_cap(max_rows, 128.0), irls_chain_seed(max_rows, 128.0), offs.data(), K, p, tol, max_iter, coef, Sig_inv, Sig_invMcoef, n_iter_host,
-                         status_host, loglik_host, ws, ws_bytes, stream);
+    return onehot_irls_fit_rows(plan, num, ldn, codes, ldc, y, part_first_host, part_rows_host, row_step, K, tol, max_iter, coef, Sig_inv,
+                                Sig_invMcoef, n_iter_host, status_host, loglik_host, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -17,215 +17,34 @@
 // from run to run like those of the dense kernels; DLSA_OH_ORDERED=0 lets all waves add at once (faster Gram, last bits vary).  The factor-pair tables of the Gram are dealt to
 // workgroup ROLES so that each role's tables fit in LDS (every role streams all rows; they are cheap).
 #include "common.h"
-#include <vector>
-#include <algorithm>
+#include "onehot_plan.h"
 #include <string.h>
 
 namespace dlsa {
 
-constexpr int OH_MAXD = 8;            // dense columns (intercept + numerics) handled in registers
-constexpr int OH_MAXF = 8;            // factors
-constexpr int OH_THREADS = 256;
+#include "logistic.h"     // exp_neg, rcp_newton
+#include "onehot_pass.h"  // oh_row_kernel, oh_row_pass
+
 #ifndef DLSA_OH_GRAM_THREADS
 #define DLSA_OH_GRAM_THREADS 1024
 #endif
 constexpr int OH_GRAM_THREADS = DLSA_OH_GRAM_THREADS;      // the Gram pass: one workgroup per CU (its tables fill the LDS), so all its latency hiding is waves
 constexpr int OH_LDS_BUDGET = 152 * 1024;     // bytes of histogram tables per workgroup role
-constexpr int OH_LOGIT_REP = 8;             // LDS copies (at most) of the logit pass's residual histogram
-// copies actually used: as many as keep the workgroup's LDS near 32 KB (several workgroups per CU), at least one
-static int oh_logit_rep(int p) {
-    int r = OH_LOGIT_REP;
-    while (r > 1 && (size_t)(1 + r) * p * sizeof(double) > 32 * 1024) r /= 2;
-    return r;
-}
 constexpr int OH_MAX_BLOCKS = 512;          // two workgroups per CU; every workgroup flushes its tables once
 
-struct OhTable {                      // one factor-pair table of a Gram role (t <= u; t == u: the diagonal counts), or a BAND of its rows
-    int t, u;                         // factor indices
-    int lds_off;                      // offset (doubles) of its ltn x L_u (or ltn) cells in the role's LDS image
-    int lt0, ltn;                     // the levels lt0 .. lt0 + ltn - 1 of factor t: a table larger than the LDS budget is cut into
-                                      // row bands that go to different roles (300 x 300 levels: five bands of 64 rows)
-};
-
-struct OhRole {
-    int ntab;
-    OhTable tab[OH_MAXF * (OH_MAXF + 1) / 2];
-    int with_dense;                   // this role also accumulates H_DD and H_D,dummy
-    int dense_off;                    // offset of the D x nlev_total block (H_D,dummy), if with_dense
-    int cells;                        // doubles in the LDS image (and in the role's partial)
-    int dense_rep;                    // copies of the H_D,dummy block in LDS (copy r >= 1 sits after the image, at
-                                      // cells + (r-1) * nlev_total * OH_MAXD): lanes spread over them, so the lanes of a
-                                      // wave that share a hot level do not all serialise on the same eight addresses
-};
-
-struct OhDesc {                       // device-visible description of the design
-    int p, D, f;
-    int dense_kind[OH_MAXD];          // 0: constant 1, 1: numeric column dense_src
-    int dense_src[OH_MAXD];
-    double dense_shift[OH_MAXD], dense_scale[OH_MAXD];
-    int dense_col[OH_MAXD];           // output column of dense column a
-    int lvl_off[OH_MAXF + 1];         // factor t's levels occupy [lvl_off[t], lvl_off[t+1]) of level_col
-    int nlev_total;
-    int dbg;                          // DLSA_OH_DBG (timing experiments only, wrong results): 1 = no dense x level atomics, 2 = no pair-table atomics
-    int ordered;                      // LDS accumulation of the passes.  2 (default, Gram): EXACT -- every addend goes in as a 64-bit
-                                      // fixed-point integer (ds_add_u64), integer addition is associative, so all waves add at once
-                                      // and the result is bit-identical from run to run whatever the order; 1: floating-point adds in
-                                      // a fixed wave order (turn-taking in the logit pass, the systolic schedule in the Gram;
-                                      // DLSA_OH_ORDERED=1, and the Gram's fall-back when an addend leaves the fixed-point range);
-                                      // 0 (DLSA_OH_ORDERED=0): floating-point adds from all waves at once, last bits vary
-    int* overflow;                    // exact mode: set to 1 by a thread whose addend exceeds OH_FIX_VMAX (or is not finite)
-};
-
-}  // namespace dlsa
-
-struct dlsa_onehot_plan {
-    dlsa::OhDesc desc;
-    int32_t* d_level_col;             // device: column of every (factor, level), -1 = no column (baseline / dropped)
-    std::vector<int32_t> h_level_col;
-    std::vector<dlsa::OhRole> roles;
-    dlsa::OhRole* d_roles;
-    bool needs_num;                   // some dense column is numeric
-};
-
-namespace dlsa {
-
-// standardised dense vector of row i (d[a], a < D)
-__device__ __forceinline__ void oh_dense_row(const OhDesc& ds, const double* __restrict__ num, int64_t ldn, int64_t i,
-                                             double (&d)[OH_MAXD]) {
-#pragma unroll
-    for (int a = 0; a < OH_MAXD; ++a) {
-        d[a] = 0.0;
-        if (a < ds.D) d[a] = ds.dense_kind[a] == 0 ? 1.0 : (num[i * ldn + ds.dense_src[a]] - ds.dense_shift[a]) / ds.dense_scale[a];
-    }
-}
-
-__device__ __forceinline__ double oh_exp_neg(double a) {      // exp(-a), a >= 0 (as logit.hip)
-    a = fmin(a, 745.2);
-    const double kf = rint(a * 1.4426950408889634);
-    double r = fma(kf, 6.93147180369123816490e-01, -a);
-    r = fma(kf, 1.90821492927058770002e-10, r);
-    double q = 1.6059043836821613e-10;
-    q = fma(q, r, 2.08767569878681e-09);
-    q = fma(q, r, 2.505210838544172e-08);
-    q = fma(q, r, 2.755731922398589e-07);
-    q = fma(q, r, 2.7557319223985893e-06);
-    q = fma(q, r, 2.48015873015873e-05);
-    q = fma(q, r, 1.984126984126984e-04);
-    q = fma(q, r, 1.388888888888889e-03);
-    q = fma(q, r, 8.333333333333333e-03);
-    q = fma(q, r, 4.1666666666666664e-02);
-    q = fma(q, r, 1.6666666666666666e-01);
-    q = fma(q, r, 0.5);
-    q = fma(q, r, 1.0);
-    q = fma(q, r, 1.0);
-    return ldexp(q, -(int)kf);
-}
-
-__device__ __forceinline__ double oh_block_sum(double v, double* red) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
-    return s;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// logit pass: w, per-workgroup partial of g (p doubles) and loglik
+// logit pass: w, per-workgroup partial of g (p doubles) and loglik -- oh_row_kernel<OhLogitRow> (onehot_pass.h)
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(OH_THREADS) void oh_logit_kernel(OhDesc ds, const int32_t* __restrict__ level_col,
-                                                              const double* __restrict__ num, int64_t ldn,
-                                                              const int32_t* __restrict__ codes, int64_t ldc,
-                                                              const double* __restrict__ y, const double* __restrict__ beta,
-                                                              int64_t n, double* __restrict__ w_out,
-                                                              double* __restrict__ gpart, double* __restrict__ llpart, int nrep) {
-    extern __shared__ double sm[];
-    double* sbeta = sm;                           // p
-    double* sg = sm + ds.p;                       // nrep x p (histograms of residuals; lanes spread over the copies,
-                                                  // so the lanes of a wave that share a hot level do not serialise on one address)
-    int* scol = reinterpret_cast<int*>(sm + (1 + nrep) * ds.p);     // nlev_total
-    double* red = reinterpret_cast<double*>(scol + ((ds.nlev_total + 1) & ~1));
-    for (int j = threadIdx.x; j < ds.p; j += blockDim.x) sbeta[j] = beta[j];
-    for (int j = threadIdx.x; j < nrep * ds.p; j += blockDim.x) sg[j] = 0.0;
-    double* sg_mine = sg + (threadIdx.x % nrep) * ds.p;
-    for (int j = threadIdx.x; j < ds.nlev_total; j += blockDim.x) scol[j] = level_col[j];
-    __syncthreads();
-    double gd[OH_MAXD];
-#pragma unroll
-    for (int a = 0; a < OH_MAXD; ++a) gd[a] = 0.0;
-    double ll = 0.0;
-    // every thread runs the same number of rounds (the ordered mode has barriers inside): rows past n are clamped and masked
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t rounds = (n - (int64_t)blockIdx.x * blockDim.x + stride - 1) / stride;
-    const int mywave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    for (int64_t rd = 0; rd < rounds; ++rd) {
-        const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + rd * stride;
-        const bool valid = i0 < n;
-        const int64_t i = valid ? i0 : n - 1;
-        double d[OH_MAXD];
-        oh_dense_row(ds, num, ldn, i, d);
-        double eta = 0.0;
-#pragma unroll
-        for (int a = 0; a < OH_MAXD; ++a)
-            if (a < ds.D) eta = fma(d[a], sbeta[ds.dense_col[a]], eta);
-        int cols[OH_MAXF];
-#pragma unroll
-        for (int t = 0; t < OH_MAXF; ++t) {
-            cols[t] = -1;
-            if (t < ds.f) {
-                const int code = codes[i * ldc + t];
-                const int nl = ds.lvl_off[t + 1] - ds.lvl_off[t];
-                if (code >= 0 && code < nl) cols[t] = scol[ds.lvl_off[t] + code];
-                if (cols[t] >= 0) eta += sbeta[cols[t]];
-            }
-        }
-        const double yv = y[i];
-        const double e = oh_exp_neg(fabs(eta));
-        double inv = __builtin_amdgcn_rcp(1.0 + e);
-        inv = fma(fma(-(1.0 + e), inv, 1.0), inv, inv);
-        inv = fma(fma(-(1.0 + e), inv, 1.0), inv, inv);
-        const double mu = eta >= 0.0 ? inv : e * inv;
-        if (w_out && valid) w_out[i] = e * inv * inv;
-        const double r = valid ? yv - mu : 0.0;
-        if (valid) ll += yv * eta - (fmax(eta, 0.0) + log1p(e));
-#pragma unroll
-        for (int a = 0; a < OH_MAXD; ++a) gd[a] = fma(r, d[a], gd[a]);
-        if (ds.ordered) {                           // one wave at a time, in wave order: a fixed order of the LDS adds (modes 1 and 2)
-            for (int turn = 0; turn < nwaves; ++turn) {
-                if (turn == mywave && valid) {
-#pragma unroll
-                    for (int t = 0; t < OH_MAXF; ++t)
-                        if (t < ds.f && cols[t] >= 0) unsafeAtomicAdd(&sg_mine[cols[t]], r);
-                }
-                __syncthreads();
-            }
-        } else if (valid) {
-#pragma unroll
-            for (int t = 0; t < OH_MAXF; ++t)
-                if (t < ds.f && cols[t] >= 0) unsafeAtomicAdd(&sg_mine[cols[t]], r);
-        }
+struct OhLogitRow {       // e = exp(-|eta|): mu = sigmoid(eta), w = mu (1 - mu) = e / (1 + e)^2, term = y eta - softplus(eta)
+    double e, inv;        // of the row in hand: exp(-|eta|) and 1 / (1 + e)
+    __device__ __forceinline__ double mean(int64_t, double& eta) {
+        e = exp_neg(fabs(eta));
+        inv = rcp_newton(1.0 + e);
+        return eta >= 0.0 ? inv : e * inv;
     }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < OH_MAXD; ++a) {
-        const double sgd = oh_block_sum(gd[a], red);
-        if (threadIdx.x == 0 && a < ds.D) sg[ds.dense_col[a]] += sgd;
-    }
-    const double sll = oh_block_sum(ll, red);
-    __syncthreads();
-    double* gp = gpart + (int64_t)blockIdx.x * ds.p;
-    for (int j = threadIdx.x; j < ds.p; j += blockDim.x) {
-        double t = sg[j];
-        for (int r = 1; r < nrep; ++r) t += sg[r * ds.p + j];      // fixed order
-        gp[j] = t;
-    }
-    if (threadIdx.x == 0) llpart[blockIdx.x] = sll;
-}
-
-// g[j] = sum_b gpart[b][j], loglik = sum_b llpart[b] in a fixed order: the dense pass's finish kernel (logit.hip)
-void logit_finish_launch(const double* gpart, const double* llpart, int nblocks, int pitch, int p, double* g,
-                         double* loglik, hipStream_t stream, const double* s0part, double* s0);
+    __device__ __forceinline__ double weight(double) const { return e * inv * inv; }
+    __device__ __forceinline__ double term(double y, double eta, double) const { return y * eta - (fmax(eta, 0.0) + log1p(e)); }
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // Exact LDS accumulation.  An addend v (|v| <= OH_FIX_VMAX = 16: w d with w <= 1/4 and a standardised numeric below 64 sigma,
@@ -430,15 +249,6 @@ static int oh_blocks(int64_t n) {
     const int64_t want = (n + OH_THREADS * 16 - 1) / (OH_THREADS * 16);
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, OH_MAX_BLOCKS));
 }
-// The logit pass keeps little in LDS, so many small workgroups share a CU: four rows per thread, up to eight
-// workgroups per CU (a 1e6-row partition: 977 workgroups instead of 244 -- one per CU, four waves, nothing to hide the
-// row loads behind: 72 us for 76 MB)
-constexpr int OH_LOGIT_MAX_BLOCKS = 2048;
-static int oh_logit_blocks(int64_t n) {
-    const int64_t want = (n + OH_THREADS * 4 - 1) / (OH_THREADS * 4);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(want, OH_LOGIT_MAX_BLOCKS));
-}
-
 int onehot_plan_p(const dlsa_onehot_plan* pl) { return pl->desc.p; }
 
 size_t onehot_workspace_bytes_impl(const dlsa_onehot_plan* pl, int64_t n) {
@@ -456,27 +266,11 @@ int onehot_logit_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_
                            void* ws, size_t ws_bytes, hipStream_t s) {
     DLSA_REQUIRE(pl && y && beta && (num || !pl->needs_num || n == 0) && (codes || pl->desc.f == 0 || n == 0),
                  "onehot logit pass: null argument");
-    OhDesc ds = pl->desc;
-    { const char* e = kernel_knob("DLSA_OH_ORDERED"); ds.ordered = e ? (atoi(e) != 0) : 1; }      // the logit pass: wave turn-taking unless 0
-    ds.overflow = nullptr;
     if (!ws || ws_bytes < onehot_workspace_bytes_impl(pl, n) || ((uintptr_t)ws & 255)) {
         set_error("onehot logit pass: workspace %zu bytes needed (256-aligned), got %zu", onehot_workspace_bytes_impl(pl, n), ws_bytes);
         return DLSA_ERR_WORKSPACE;
     }
-    const int nb = oh_logit_blocks(n);
-    Arena ar(ws, ws_bytes);
-    double* gpart = (double*)ar.take((size_t)nb * ds.p * sizeof(double));
-    double* llpart = (double*)ar.take((size_t)nb * sizeof(double));
-    const int nrep = oh_logit_rep(ds.p);
-    const size_t shm = (size_t)((1 + nrep) * ds.p + 16) * sizeof(double) + (size_t)((ds.nlev_total + 1) & ~1) * sizeof(int);
-    hipLaunchKernelGGL(oh_logit_kernel, dim3(nb), dim3(OH_THREADS), shm, s, ds, (const int32_t*)pl->d_level_col, num, ldn, codes,
-                       ldc, y, beta, n, w_out, gpart, llpart, nrep);
-    DLSA_HIP_CHECK(hipGetLastError());
-    if (g || loglik) {
-        logit_finish_launch((const double*)gpart, (const double*)llpart, nb, ds.p, ds.p, g, loglik, s, nullptr, nullptr);
-        DLSA_HIP_CHECK(hipGetLastError());
-    }
-    return DLSA_OK;
+    return oh_row_pass("onehot logit pass", OhLogitRow{}, pl, num, ldn, codes, ldc, y, beta, n, w_out, g, loglik, ws, ws_bytes, s);
 }
 
 // irls_weights: w are the logistic weights mu (1 - mu) in (0, 1/4] of this library's own logit pass (the IRLS driver) -- the addends'

@@ -1,11 +1,7 @@
-// The structured one-hot plan and the small helpers of its row passes, for translation units other than onehot.hip.
-//
-// onehot.hip still carries its own copy of every definition below: its source is pinned by the committed hardware-counter
-// evidence (bench/pmc_evidence.py hashes it), so it is left byte for byte as it is.  This header is a TOKEN-IDENTICAL MIRROR
-// of those definitions (identical definitions in two translation units are well-formed);
-// tests/test_onehot_poisson_cpu.py extracts both copies, strips comments and whitespace and asserts that they are equal, so
-// the two cannot drift.  The next time onehot.hip's counters are re-taken, onehot.hip is to include this header instead of
-// defining these itself.
+// The structured one-hot plan (OhDesc, OhRole, OhTable, dlsa_onehot_plan), the sizing rules and small device helpers of its row
+// passes, and the host functions of onehot.hip that other translation units call.  Included by onehot.hip (the logistic row
+// pass, the Gram, plan creation), onehot_poisson.hip (the Poisson row pass) and irls.hip (the structured logistic fit); the
+// row-pass kernel and its launch driver are onehot_pass.h.
 #pragma once
 #include "common.h"
 #include <vector>
@@ -101,5 +97,17 @@ static int oh_logit_blocks(int64_t n) {
     const int64_t want = (n + OH_THREADS * 4 - 1) / (OH_THREADS * 4);
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, OH_LOGIT_MAX_BLOCKS));
 }
+
+// g[j] = sum_b gpart[b][j], loglik = sum_b llpart[b] in a fixed order: the dense pass's finish kernel (logit.hip)
+void logit_finish_launch(const double* gpart, const double* llpart, int nblocks, int pitch, int p, double* g,
+                         double* loglik, hipStream_t stream, const double* s0part, double* s0);
+// onehot.hip
+int onehot_plan_p(const dlsa_onehot_plan* pl);
+size_t onehot_workspace_bytes_impl(const dlsa_onehot_plan* pl, int64_t n);
+int onehot_logit_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                           const double* y, const double* beta, int64_t n, double* w_out, double* g, double* loglik,
+                           void* ws, size_t ws_bytes, hipStream_t s);
+int onehot_gram_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                     const double* w, int64_t n, double* H, int64_t ldh, void* ws, size_t ws_bytes, hipStream_t s, bool irls_weights);
 
 }  // namespace dlsa

@@ -4,10 +4,11 @@
 // dlsa_design_f64 would build (to rounding).
 //
 // Launches per evaluation at a fixed beta:
-//   1 oh_poisson_kernel     one thread per row as oh_logit_kernel (onehot.hip): eta = d . beta_D + sum_t beta[col(t, code_t)] + o
-//                           (a gather), mu = exp_full(eta) (-> w), r = y - mu, per-workgroup partials of g (dense part in
-//                           registers, level part an LDS histogram with replicated copies and wave turn-taking: a fixed
-//                           order of the adds, bit-reproducible) and of sum y eta - mu;
+//   1 oh_row_kernel<OhPoisRow<OFF>>  the one-thread-per-row pass of onehot_pass.h (shared with the logistic model,
+//                           onehot.hip) with the Poisson terms: eta = d . beta_D + sum_t beta[col(t, code_t)] + o (a gather),
+//                           mu = exp_full(eta) (-> w), r = y - mu, per-workgroup partials of g (dense part in registers, level
+//                           part an LDS histogram with replicated copies and wave turn-taking: a fixed order of the adds,
+//                           bit-reproducible) and of sum y eta - mu;
 //   2 logit_finish_launch   the fixed-order column sums of those partials (logit.hip, shared);
 //   3 the Gram              onehot_gram_impl(plan, num, codes, mu) with irls_weights = false: mu is unbounded, so the ordered
 //                           floating-point mode (full relative accuracy at any scale, bit-reproducible), never the fixed-point one.
@@ -23,99 +24,18 @@
 namespace dlsa {
 
 #include "poisson_exp.h"  // exp_full
+#include "onehot_pass.h"  // oh_row_kernel, oh_row_pass
 
-size_t onehot_workspace_bytes_impl(const dlsa_onehot_plan* pl, int64_t n);
-int onehot_plan_p(const dlsa_onehot_plan* pl);
-int onehot_gram_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
-                     const double* w, int64_t n, double* H, int64_t ldh, void* ws, size_t ws_bytes, hipStream_t s, bool irls_weights);
-
-// The skeleton of oh_logit_kernel with the Poisson terms.  Every thread runs the same number of rounds (the ordered mode has
-// barriers inside): rows past n are clamped to row n - 1 and masked.  OFF = false reads no offsets.
-template <bool OFF>
-__global__ __launch_bounds__(OH_THREADS) void oh_poisson_kernel(OhDesc ds, const int32_t* __restrict__ level_col,
-                                                                const double* __restrict__ num, int64_t ldn,
-                                                                const int32_t* __restrict__ codes, int64_t ldc,
-                                                                const double* __restrict__ y, const double* __restrict__ off,
-                                                                const double* __restrict__ beta, int64_t n,
-                                                                double* __restrict__ w_out, double* __restrict__ gpart,
-                                                                double* __restrict__ llpart, int nrep) {
-    extern __shared__ double sm[];
-    double* sbeta = sm;                           // p
-    double* sg = sm + ds.p;                       // nrep x p histograms of residuals (lanes spread over the copies)
-    int* scol = reinterpret_cast<int*>(sm + (1 + nrep) * ds.p);     // nlev_total
-    double* red = reinterpret_cast<double*>(scol + ((ds.nlev_total + 1) & ~1));
-    for (int j = threadIdx.x; j < ds.p; j += blockDim.x) sbeta[j] = beta[j];
-    for (int j = threadIdx.x; j < nrep * ds.p; j += blockDim.x) sg[j] = 0.0;
-    double* sg_mine = sg + (threadIdx.x % nrep) * ds.p;
-    for (int j = threadIdx.x; j < ds.nlev_total; j += blockDim.x) scol[j] = level_col[j];
-    __syncthreads();
-    double gd[OH_MAXD];
-#pragma unroll
-    for (int a = 0; a < OH_MAXD; ++a) gd[a] = 0.0;
-    double ll = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t rounds = (n - (int64_t)blockIdx.x * blockDim.x + stride - 1) / stride;
-    const int mywave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    for (int64_t rd = 0; rd < rounds; ++rd) {
-        const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + rd * stride;
-        const bool valid = i0 < n;
-        const int64_t i = valid ? i0 : n - 1;
-        double d[OH_MAXD];
-        oh_dense_row(ds, num, ldn, i, d);
-        double eta = 0.0;
-#pragma unroll
-        for (int a = 0; a < OH_MAXD; ++a)
-            if (a < ds.D) eta = fma(d[a], sbeta[ds.dense_col[a]], eta);
-        int cols[OH_MAXF];
-#pragma unroll
-        for (int t = 0; t < OH_MAXF; ++t) {
-            cols[t] = -1;
-            if (t < ds.f) {
-                const int code = codes[i * ldc + t];
-                const int nl = ds.lvl_off[t + 1] - ds.lvl_off[t];
-                if (code >= 0 && code < nl) cols[t] = scol[ds.lvl_off[t] + code];      // an unknown / baseline level contributes nothing
-                if (cols[t] >= 0) eta += sbeta[cols[t]];
-            }
-        }
-        const double yv = y[i];
+template <bool OFF>       // OFF = false reads no offsets
+struct OhPoisRow {        // eta += o, mu = exp(eta) = w, term = y eta - mu
+    const double* off;
+    __device__ __forceinline__ double mean(int64_t i, double& eta) const {
         if constexpr (OFF) eta += off[i];
-        const double mu = exp_full(eta);
-        if (w_out && valid) w_out[i] = mu;
-        const double r = valid ? yv - mu : 0.0;
-        if (valid) ll += yv * eta - mu;
-#pragma unroll
-        for (int a = 0; a < OH_MAXD; ++a) gd[a] = fma(r, d[a], gd[a]);
-        if (ds.ordered) {                           // one wave at a time, in wave order: a fixed order of the LDS adds
-            for (int turn = 0; turn < nwaves; ++turn) {
-                if (turn == mywave && valid) {
-#pragma unroll
-                    for (int t = 0; t < OH_MAXF; ++t)
-                        if (t < ds.f && cols[t] >= 0) unsafeAtomicAdd(&sg_mine[cols[t]], r);
-                }
-                __syncthreads();
-            }
-        } else if (valid) {
-#pragma unroll
-            for (int t = 0; t < OH_MAXF; ++t)
-                if (t < ds.f && cols[t] >= 0) unsafeAtomicAdd(&sg_mine[cols[t]], r);
-        }
+        return exp_full(eta);
     }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < OH_MAXD; ++a) {
-        const double sgd = oh_block_sum(gd[a], red);
-        if (threadIdx.x == 0 && a < ds.D) sg[ds.dense_col[a]] += sgd;
-    }
-    const double sll = oh_block_sum(ll, red);
-    __syncthreads();
-    double* gp = gpart + (int64_t)blockIdx.x * ds.p;
-    for (int j = threadIdx.x; j < ds.p; j += blockDim.x) {
-        double t = sg[j];
-        for (int r = 1; r < nrep; ++r) t += sg[r * ds.p + j];      // fixed order
-        gp[j] = t;
-    }
-    if (threadIdx.x == 0) llpart[blockIdx.x] = sll;
-}
+    __device__ __forceinline__ double weight(double mu) const { return mu; }
+    __device__ __forceinline__ double term(double y, double eta, double mu) const { return y * eta - mu; }
+};
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 struct OhPoisLayout {
@@ -159,31 +79,10 @@ static int oh_pois_icpt_col(const dlsa_onehot_plan* pl) {      // the plan's con
 static int oh_pois_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
                              const double* y, const double* off, const double* beta, int64_t n, double* H, int64_t ldh, double* g,
                              double* loglik, double* w, void* ws_oh, size_t ws_oh_bytes, hipStream_t s) {
-    OhDesc ds = pl->desc;
-    { const char* e = kernel_knob("DLSA_OH_ORDERED"); ds.ordered = e ? (atoi(e) != 0) : 1; }      // wave turn-taking unless 0
-    ds.overflow = nullptr;
-    const int nb = oh_logit_blocks(n);
-    Arena ar(ws_oh, ws_oh_bytes);
-    double* gpart = (double*)ar.take((size_t)nb * ds.p * sizeof(double));
-    double* llpart = (double*)ar.take((size_t)nb * sizeof(double));
-    if (!gpart || !llpart) {
-        set_error("onehot poisson pass: the pass arena of %zu bytes is too small", ws_oh_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
-    const int nrep = oh_logit_rep(ds.p);
-    const size_t shm = (size_t)((1 + nrep) * ds.p + 16) * sizeof(double) + (size_t)((ds.nlev_total + 1) & ~1) * sizeof(int);
-    if (off)
-        hipLaunchKernelGGL(oh_poisson_kernel<true>, dim3(nb), dim3(OH_THREADS), shm, s, ds, (const int32_t*)pl->d_level_col, num, ldn,
-                           codes, ldc, y, off, beta, n, w, gpart, llpart, nrep);
-    else
-        hipLaunchKernelGGL(oh_poisson_kernel<false>, dim3(nb), dim3(OH_THREADS), shm, s, ds, (const int32_t*)pl->d_level_col, num, ldn,
-                           codes, ldc, y, off, beta, n, w, gpart, llpart, nrep);
-    DLSA_HIP_CHECK(hipGetLastError());
-    if (g || loglik) {
-        logit_finish_launch((const double*)gpart, (const double*)llpart, nb, ds.p, ds.p, g, loglik, s, nullptr, nullptr);
-        DLSA_HIP_CHECK(hipGetLastError());
-    }
-    if (!H) return DLSA_OK;
+    const char* who = "onehot poisson pass";
+    const int rc = off ? oh_row_pass(who, OhPoisRow<true>{off}, pl, num, ldn, codes, ldc, y, beta, n, w, g, loglik, ws_oh, ws_oh_bytes, s)
+                       : oh_row_pass(who, OhPoisRow<false>{off}, pl, num, ldn, codes, ldc, y, beta, n, w, g, loglik, ws_oh, ws_oh_bytes, s);
+    if (rc || !H) return rc;
     // (the Gram's partials overwrite the pass's in the same arena: the finish launch above has consumed them, in stream order)
     return onehot_gram_impl(pl, num, ldn, codes, ldc, w, n, H, ldh, ws_oh, ws_oh_bytes, s, false);
 }

@@ -68,24 +68,49 @@ def _plan(api, p, desc, nl, level_col):
 @pytest.mark.parametrize("n,q,nlevels", [(5000, 7, (11, 6, 20)), (3001, 2, (3,)), (20000, 0, (5, 4)), (777, 7, (40, 40, 9, 2)),
                                          (4000, 3, (110, 110, 20, 6)), (1, 1, (2,)), (6000, 2, (1400, 5)), (3000, 0, (700, 8, 3))])
 def test_onehot_passes_match_dense_oracle(api, orc, n, q, nlevels):
+    _check_passes(api, orc, n, q, nlevels)
+
+
+def _check_passes(api, orc, n, q, nlevels, intercept=True, baseline=True, ordered=None):
+    import contextlib
     from dlsa_amd import engine
     rng = np.random.default_rng(n + q)
-    p, num, codes, desc, nl, level_col = _random_design(rng, n, q, nlevels)
+    p, num, codes, desc, nl, level_col = _random_design(rng, n, q, nlevels, intercept=intercept, baseline=baseline)
     codes[rng.integers(0, n, max(1, n // 50)), 0] = -1          # unknown level: no column
     plan = _plan(api, p, desc, nl, level_col)
     X, _ = orc.design_matrix(num, codes, *desc)
     beta = rng.normal(size=p) * 0.4
     y = (rng.random(n) < 0.5).astype(np.float64)
     wo, go, llo = orc.logit_pass(X, y, beta)
-    w, g, ll = engine.onehot_logit_pass(plan, dev(num) if q else None, dev(codes), dev(y), dev(beta))
-    assert rel_inf(w.cpu().numpy(), wo) < 1e-12
-    assert rel_inf(g.cpu().numpy(), go) < 1e-11 and abs(ll.item() - llo) < 1e-11 * abs(llo)
-    H = engine.onehot_gram(plan, dev(num) if q else None, dev(codes), dev(wo)).cpu().numpy()
+    with contextlib.nullcontext() if ordered is None else engine.kernel_options(onehot_ordered=ordered):
+        w, g, ll = engine.onehot_logit_pass(plan, dev(num) if q else None, dev(codes), dev(y), dev(beta))
+        H = engine.onehot_gram(plan, dev(num) if q else None, dev(codes), dev(wo)).cpu().numpy()
     Ho = orc.gram(X, wo)
-    assert np.max(np.abs(H - Ho)) < 1e-12 * np.max(np.abs(Ho))
+    figs = (rel_inf(w.cpu().numpy(), wo), rel_inf(g.cpu().numpy(), go), abs(ll.item() - llo) / abs(llo), np.max(np.abs(H - Ho)) / np.max(np.abs(Ho)))
+    print("passes", (n, q, nlevels, intercept, baseline, ordered), "p", p, "rel err w %.2e g %.2e ll %.2e H %.2e" % figs)
+    assert figs[0] < 1e-12
+    assert figs[1] < 1e-11 and figs[2] < 1e-11
+    assert figs[3] < 1e-12
     assert np.array_equal(H, H.T)
     if nlevels[:2] == (110, 110):
         assert plan.roles >= 2                                  # the 110 x 110 table gets a role of its own
+    return p
+
+
+def test_onehot_passes_with_two_histogram_copies(api, orc):
+    """p = 1001: the residual histogram of the row pass runs with two LDS copies (the shapes above give eight, four and one)."""
+    assert _check_passes(api, orc, 2000, 1, (1000,)) == 1001
+
+
+def test_onehot_passes_without_a_dense_column_and_a_masked_second_round(api, orc):
+    """No intercept, no numerics, no baselines; 257 rows: one workgroup, whose second round has 255 of 256 threads clamped and masked
+    while the ordered barriers run."""
+    assert _check_passes(api, orc, 257, 0, (3, 2), intercept=False, baseline=False) == 5
+
+
+def test_onehot_passes_with_unordered_adds(api, orc):
+    """DLSA_OH_ORDERED=0: all waves add at once, last bits vary from run to run -- against the oracle only."""
+    _check_passes(api, orc, 777, 7, (40, 40, 9, 2), ordered=0)
 
 
 @pytest.mark.parametrize("seed", range(20))

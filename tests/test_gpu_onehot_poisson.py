@@ -19,7 +19,9 @@ torch = pytest.importorskip("torch")
 TOL_PASS = 1e-12
 TOL_FIT = 1e-10
 SHAPES = [(5000, 7, (11, 6, 20)), (3001, 2, (3,)), (20000, 0, (5, 4)), (777, 7, (40, 40, 9, 2)),
-          (4000, 3, (110, 110, 20, 6)), (1, 1, (2,)), (6000, 2, (1400, 5)), (3000, 0, (700, 8, 3))]
+          (4000, 3, (110, 110, 20, 6)), (1, 1, (2,)), (6000, 2, (1400, 5)), (3000, 0, (700, 8, 3)),
+          (2000, 1, (1000,)),           # p = 1001: the row pass's residual histogram runs with two LDS copies (the others: 8, 4, 1)
+          (257, 0, (3, 2))]             # one workgroup whose second round has 255 of 256 threads masked; no dense column without intercept
 
 
 def rel(a, b):
@@ -79,6 +81,20 @@ def test_pass_matches_reference(api, orc, n, q, nlevels, intercept, baseline, of
     o = np.log(rng.uniform(0.5, 2.0, n)) if offset else None
     y = _counts(rng, X, beta, o)
     _check_pass(plan, num, codes, y, o, beta, X, (n, q, nlevels, intercept, baseline, offset))
+
+
+def test_pass_with_unordered_adds(api, orc):
+    """DLSA_OH_ORDERED=0: all waves add at once, last bits vary from run to run -- against the reference only."""
+    from dlsa_amd import engine
+    n, q, nlevels = 777, 7, (40, 40, 9, 2)
+    rng = np.random.default_rng(n + q)
+    p, num, codes, desc, nl, level_col = _random_design(rng, n, q, nlevels)
+    plan = _plan(api, p, desc, nl, level_col)
+    X, _ = orc.design_matrix(num, codes, *desc)
+    beta = rng.normal(size=p) * 0.4
+    o = np.log(rng.uniform(0.5, 2.0, n))
+    with engine.kernel_options(onehot_ordered=0):
+        _check_pass(plan, num, codes, _counts(rng, X, beta, o), o, beta, X, (n, q, nlevels, "unordered"))
 
 
 @pytest.mark.parametrize("n,q,nlevels", [(30000, 2, (300, 300)), (9000, 3, (700, 40))])

@@ -1,7 +1,7 @@
 """CPU checks of the structured one-hot Poisson map step (csrc/onehot_poisson.hip): the three C-ABI entries are exported and
-bound, refuse null / bad arguments before any HIP call, the workspace query is 0 for bad arguments -- and the mirror header
-csrc/onehot_plan.h holds token for token the definitions onehot.hip (whose source is pinned by committed counter evidence)
-still carries itself.  A dlsa_onehot_plan cannot be created without a device (its level table is uploaded at creation), so the
+bound, refuse null / bad arguments before any HIP call, the workspace query is 0 for bad arguments -- and the plan, its sizing
+rules and the row passes' helpers are defined once (csrc/onehot_plan.h), for onehot.hip and onehot_poisson.hip alike.  A
+dlsa_onehot_plan cannot be created without a device (its level table is uploaded at creation), so the
 argument checks that need a plan run in tests/test_gpu_onehot_poisson.py."""
 import ctypes
 import os
@@ -63,10 +63,10 @@ def test_workspace_query_is_zero_for_bad_arguments(lib):
     assert lib.dlsa_onehot_poisson_workspace_bytes(None, 1000, 0) == 0
 
 
-# ---- the mirror header --------------------------------------------------------------------------------------------------
-MIRRORED = [("const", n) for n in ("OH_MAXD", "OH_MAXF", "OH_THREADS", "OH_LOGIT_REP", "OH_LOGIT_MAX_BLOCKS")] + \
-           [("struct", n) for n in ("OhTable", "OhRole", "OhDesc", "dlsa_onehot_plan")] + \
-           [("func", n) for n in ("oh_logit_rep", "oh_logit_blocks", "oh_dense_row", "oh_block_sum")]
+# ---- one definition of the plan ------------------------------------------------------------------------------------------
+SHARED = [("const", n) for n in ("OH_MAXD", "OH_MAXF", "OH_THREADS", "OH_LOGIT_REP", "OH_LOGIT_MAX_BLOCKS")] + \
+         [("struct", n) for n in ("OhTable", "OhRole", "OhDesc", "dlsa_onehot_plan")] + \
+         [("func", n) for n in ("oh_logit_rep", "oh_logit_blocks", "oh_dense_row", "oh_block_sum", "exp_neg")]
 
 
 def _strip(text):
@@ -103,29 +103,36 @@ def _definition(text, kind, name):
     return re.sub(r"\s+", "", hits[0])
 
 
-def test_mirror_header_is_token_identical_to_onehot_hip():
-    src = _strip(open(os.path.join(CSRC, "onehot.hip")).read())
-    mir = _strip(open(os.path.join(CSRC, "onehot_plan.h")).read())
-    for kind, name in MIRRORED:
-        a, b = _definition(src, kind, name), _definition(mir, kind, name)
-        assert a and a == b, (kind, name)
-    # the header mirrors, it does not add: every struct / function / constant it defines is on the list
-    defined = set(re.findall(r"\bstruct\s+(\w+)\s*\{", mir)) | set(re.findall(r"constexpr\s+int\s+(\w+)\s*=", mir)) | \
-        set(re.findall(r"^[ \t]*(?:static|__device__)[^\n;{}()]*\b(\w+)\s*\(", mir, flags=re.M))
-    assert defined == {n for _, n in MIRRORED}, defined ^ {n for _, n in MIRRORED}
+def _sources():
+    return {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h", ".inc"))}
 
 
-def test_mirror_guard_notices_a_drift():
-    src = _strip(open(os.path.join(CSRC, "onehot.hip")).read())
-    drifted = src.replace("constexpr int OH_MAXD = 8;", "constexpr int OH_MAXD = 9;")
-    assert drifted != src and _definition(drifted, "const", "OH_MAXD") != _definition(src, "const", "OH_MAXD")
-    drifted = src.replace("int lt0, ltn;", "int ltn, lt0;")
-    assert drifted != src and _definition(drifted, "struct", "OhTable") != _definition(src, "struct", "OhTable")
+def test_the_plan_and_the_pass_helpers_are_defined_once():
+    src = _sources()
+    everything = _strip("\n".join(src.values()))
+    for kind, name in SHARED:
+        assert _definition(everything, kind, name), (kind, name)          # (_definition asserts exactly one hit)
+    # one row kernel and one launch driver, in onehot_pass.h; the copies they replace are gone
+    assert len(re.findall(r"__global__[^;{]*\boh_row_kernel\s*\(", everything)) == 1 and "oh_row_kernel(" in src["onehot_pass.h"]
+    assert _definition(everything, "func", "oh_row_pass") and _definition(_strip(src["onehot_pass.h"]), "func", "oh_row_pass")
+    assert not any(gone in text for text in src.values() for gone in ("oh_exp_neg", "oh_logit_kernel", "oh_poisson_kernel"))
+    for kind, name in SHARED[:-1]:
+        assert _definition(_strip(src["onehot_plan.h"]), kind, name), (kind, name)
+    assert _definition(_strip(src["logistic.h"]), "func", "exp_neg")
 
 
-def test_only_the_new_unit_includes_the_mirror_and_exp_full_is_shared():
-    users = [f for f in sorted(os.listdir(CSRC)) if f != "onehot_plan.h" and '#include "onehot_plan.h"' in open(os.path.join(CSRC, f)).read()]
-    assert users == ["onehot_poisson.hip"]
+def test_a_second_definition_is_noticed():
+    everything = _strip("\n".join(_sources().values()))
+    for kind, name, again in (("const", "OH_MAXD", "constexpr int OH_MAXD = 8;"), ("struct", "OhTable", "struct OhTable { int t, u; };"),
+                              ("func", "exp_neg", "__device__ __forceinline__ double exp_neg(double a) { return a; }")):
+        with pytest.raises(AssertionError):
+            _definition(everything + "\n" + again + "\n", kind, name)
+
+
+def test_both_units_include_the_plan_header_and_exp_full_is_shared():
+    for f in ("onehot.hip", "onehot_poisson.hip"):
+        text = open(os.path.join(CSRC, f)).read()
+        assert '#include "onehot_plan.h"' in text and '#include "onehot_pass.h"' in text, f
     # one polynomial: exp_full is defined in the shared header only
     defs = [f for f in sorted(os.listdir(CSRC)) if re.search(r"double\s+exp_full\s*\(\s*double", open(os.path.join(CSRC, f)).read())]
     assert defs == ["poisson_exp.h"]
