@@ -9,33 +9,29 @@
 //     the CYCLIC classes: tile row i owns the 16 tiles (i, (i + d) mod 31), d = 0..15 -- every unordered pair {i, j} exactly
 //     once because 31 is odd (a wrapped tile is the transpose of the one the triangle wants; the epilogue stores it so).
 //     So all tile rows carry the same load: 31 x 16 = 496 tiles, no diagonal special case, no triangular wave.
-//   * a GROUP of 4 workgroups (one per CU, same XCD) shares a slab of rows.  Its 32 waves are the 16 row blocks (2 tile rows)
-//     x 2 distance halves: 16 tiles = 128 AGPRs per wave, two waves per SIMD (the two halves of one row block), every wave
-//     the same instruction stream.  Per 4-row k-step a wave reads 2 A + 9 B fragments for 16 v_mfma_f64_16x16x4_f64; the
-//     weight goes on the A side (2 multiplications).  The d < 8 wave of a row block also issues the 2 G
-//     v_mfma_f64_4x4x4_4b_f64 of its rows' tail columns (gram_narrow.hip explains the instruction).
+//   * a GROUP of 4 workgroups (one per CU, same XCD) shares a slab of rows.  Its 64 waves are the 16 row blocks (2 tile rows)
+//     x 2 tile rows x 2 distance halves: 8 tiles = 64 AGPRs per wave, FOUR waves per SIMD (the four of one row block), every
+//     wave the same instruction stream.  Per 4-row k-step a wave reads 1 A + 8 B fragments for 8 v_mfma_f64_16x16x4_f64; the
+//     weight goes on the A side (1 multiplication).  The d < 8 wave of a tile row also issues the G
+//     v_mfma_f64_4x4x4_4b_f64 of its row's tail columns (gram_narrow.hip explains the instruction).  A SIMD's matrix pipe
+//     idles only when all four of its waves are outside their MFMAs at once.  (Until this shape the kernel ran two waves per
+//     SIMD, two tile rows each: it is kept as gram_cyclic_rw2_kernel behind gram_variant bit 16, with the same bits in H.)
 //   * every workgroup streams the slab's full rows through LDS: 8-row chunks, four stages, LDS-DMA issued three chunks
-//     ahead, two pieces behind each tile row of a chunk's second k-step, no per-lane masks; fragment addresses are
+//     ahead, a wave's two pieces behind the MFMAs of a chunk's second k-step, no per-lane masks; fragment addresses are
 //     per-lane registers + compile-time immediates (the chunk loop is unrolled over the stages).  The four workgroups of
 //     a group do equal work, stay within microseconds of each other, and three of the four fetches of a row are L2 hits
 //     (TCC hit rate 73 %, fabric traffic = 1.0x the algorithmic bytes at p = 496).
 // 64 groups = 256 CUs, one launch wave, no tail; the 64 slab partials are summed by gram.hip's reduce kernel.
-// Same-box timings per 2.5e7 rows (gram.hip's panel kernel / this one): p = 496 99.9 / 90.8 ms (68.0 TF), p = 500 100.0 /
-// 94.9 ms (66.1 TF = 84 % of the 78.6 TF fp64 MFMA peak), p = 504 100.0 / 96.7 ms.
+// Same-box, same-process timings (four waves per SIMD / the two-wave twin / the two-wave kernel before the body was shared):
+// 2.5e7 x 500: 89.6-90.6 / 90.8-91.0 / 91.4-91.5 ms on two boxes; per 1e7 rows p = 496 35.6-36.1 / 36.2-36.6 / 37.3-37.4,
+// p = 504 37.1-37.3 / 37.5-37.6 / 37.4, p = 508 37.9-38.0 / 38.3-38.5 / 38.2 ms.  Dead ends, with their numbers in
+// docs/lab_notes_r01_r03.md and docs/lab_notes_r06.md: hand-off flags instead of the barrier, a barrier per chunk pair, static
+// wave priority, RW = 4.
 #include "common.h"
 #ifndef DLSA_CYC_SPLIT
 #define DLSA_CYC_SPLIT 1
 #endif
 #include <algorithm>
-#ifndef DLSA_CYC_FLAGS
-#define DLSA_CYC_FLAGS 0                  // experiment: per-stage LANDED / DONE flags in LDS instead of s_barrier (a SIMD that is ahead keeps issuing)
-#endif
-#ifndef DLSA_CYC_PAIR
-#define DLSA_CYC_PAIR 0                   // 1: one barrier per PAIR of chunks (16 rows), the next pair's DMA issued during this pair's first two k-steps
-#endif
-#ifndef DLSA_CYC_PRIO
-#define DLSA_CYC_PRIO 0                   // experiment: 1 = the second-dispatched waves (4..7) run at s_setprio 1, 2 = the first four
-#endif
 
 namespace dlsa {
 
@@ -52,6 +48,18 @@ constexpr int CYC_GROUP = 4;                  // workgroups per slab
 constexpr int CYC_PP = 512;
 constexpr int CYC_MIN_P = 481, CYC_MAX_P = 508;
 constexpr int64_t CYC_MIN_ROWS = 65536;
+
+// Tile rows per wave of the dispatched kernel, by tail groups.  RW = 1: 16 waves per workgroup, four per SIMD (<= 128 registers,
+// every G fits); RW = 2: 8 waves, two per SIMD.  RW = 1 won the same-process A/B at every width (see the header).
+constexpr int cyc_rw(int /*G*/) { return 1; }
+
+// RW = 1: where the four waves of a SIMD (slot = wave >> 2 = tile-row parity + 2 x distance half) meet a chunk's barrier, in
+// quarters of the chunk's 16 MFMAs: after 4 q MFMAs of the chunk, q = 1 .. 4 (1 and 3 are the middle of a k-step's tile row).
+// Two phases by tile-row parity, half a row apart -- the analogue of the two-wave split.  Measured at 2.5e7 x 500, same process
+// against the two-wave twin at 90.8 ms: {2,1,2,1} 89.6-89.8 ms, {1,2,1,2} 89.6, {2,3,2,3} 89.5, {3,2,3,2} 89.4, {2,1,1,2} 89.7 (one
+// group within run-to-run spread); by distance half {1,1,2,2} 90.0; half a chunk apart {1,3,1,3} 90.9; all four at one point
+// {2,2,2,2} 92.8-93.1; four phases {1,2,3,4} 96.5-97.2 (profiles/cyclic_rw1_ab.txt).
+constexpr int CYC_BAR_Q[4] = {2, 1, 2, 1};
 
 struct CycArgs {
     const double* X;
@@ -75,26 +83,31 @@ __device__ __forceinline__ void cyc_for_tiles(F&& fn) {
     }
 }
 
-template <int K, int KEND, typename F>
+template <int TS, int K, int KEND, typename F>
 __device__ __forceinline__ void cyc_for_tails(F&& fn) {
     if constexpr (K < KEND) {
-        fn(K, cyc_tail_read<K>());
-        cyc_for_tails<K + 1, KEND>(fn);
+        fn(K, cyc_tail_read<TS, K>());
+        cyc_for_tails<TS, K + 1, KEND>(fn);
     }
 }
 
-// A wave owns RW = 2 tile rows x 8 distances = 16 tiles (128 AGPRs): 8 waves per workgroup, two per SIMD, so that one wave's
-// LDS waits and DMA issue hide under the other's MFMAs.  (RW = 4 -- 32 tiles, one wave per SIMD, 15 instead of 22 fragment reads
-// per SIMD and k-step -- was built and measured: 101 vs 97 ms at p = 496; with nobody to cover a wave's waits the pipe idles.)
-template <bool HASW, int G>
-__global__ __launch_bounds__(512, 2) void gram_cyclic_kernel(CycArgs a) {
+// The kernel body, generic over the tile rows per wave.
+//   RW = 2: a wave owns 2 tile rows x 8 distances = 16 tiles (128 AGPRs): 8 waves per workgroup, two per SIMD (the two distance
+//           halves of one row block), so that one wave's LDS waits and DMA issue hide under the other's MFMAs.
+//   RW = 1: a wave owns 1 tile row x 8 distances = 8 tiles (64 AGPRs): 16 waves per workgroup, four per SIMD (the two tile rows of
+//           the SIMD's row block x the two distance halves).  The tiles of a SIMD, and the order in which each tile meets the
+//           k-steps, are the same as at RW = 2: H has the same bits.
+// (RW = 4 -- 32 tiles, one wave per SIMD, 15 instead of 22 fragment reads per SIMD and k-step -- was built and measured: 101 vs
+// 97 ms at p = 496; with nobody to cover a wave's waits the pipe idles.)
+template <bool HASW, int G, int RW>
+__device__ __forceinline__ void cyc_body(const CycArgs& a) {
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     constexpr int KC = CYC_KC, LDP = CYC_LDP, BUF = CYC_BUF, GA = G > 0 ? G : 1;
-    constexpr int RW = 2, NW = 8, NB = RW + 7;
-    constexpr int PIECES = KC * 4 / NW;                  // DMA pieces per wave and chunk (4): two behind each tile row of (c, 1)
-    constexpr int PPR = PIECES / RW;
+    constexpr int NW = 16 / RW, NB = RW + 7;
+    constexpr int PIECES = KC * 4 / NW;                  // DMA pieces per wave and chunk (RW = 2: 4, RW = 1: 2)
+    constexpr int PPR = RW == 2 ? PIECES / RW : PIECES;  // RW = 2: two behind each tile row of (c, 1); RW = 1: both behind the row
     constexpr int DMA_PER_CHUNK = PIECES + (HASW ? 1 : 0);
-    static_assert(KC == 8 && PPR * RW == PIECES && CYC_NST == 4, "pipeline shape");
+    static_assert((RW == 1 || RW == 2) && KC == 8 && CYC_NST == 4, "pipeline shape");
     static_assert((BUF + 4 * LDP) * 8 + 128 < 65536, "stage parity + k-step offsets must fit a ds_read immediate");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -104,11 +117,14 @@ __global__ __launch_bounds__(512, 2) void gram_cyclic_kernel(CycArgs a) {
     // block -> (slab, member): the four workgroups of a slab sit on one XCD (blocks b, b + 8, b + 16, b + 24 of a 32-block round)
     const int b = blockIdx.x, xcd = b % kNumXCD, jb = b / kNumXCD;
     const int slab = (jb / CYC_GROUP) * kNumXCD + xcd, member = jb % CYC_GROUP;
-    // waves w and w + 4 share a SIMD: they take the two distance halves of the same row block
-    const int rb = member * 4 + (wave & 3), db = wave >> 2;      // row block 0..15, distance half
-    const int i0 = RW * rb, d0 = 8 * db;
-    const bool two_rows = rb != 15;                      // 31 tile rows: the last block holds tile row 30 only
-    const bool tails = G > 0 && db == 0;                 // the d < 8 wave of a row block also takes its rows' tail columns
+    // waves w, w + 4, .. share a SIMD and the row block rb = 4 member + (wave & 3) = tile rows 2 rb, 2 rb + 1.
+    //   RW = 2: waves w, w + 4 take the two distance halves of the block;
+    //   RW = 1: slot = wave >> 2 gives the tile row 2 rb + (slot & 1) and the distance half slot >> 1.
+    const int rb = member * 4 + (wave & 3), slot = wave >> 2;
+    const int i0 = RW == 2 ? 2 * rb : 2 * rb + (slot & 1), db = RW == 2 ? slot : slot >> 1;
+    const int d0 = 8 * db;
+    const bool full_rows = i0 + RW - 1 != CYC_NT;        // 31 tile rows: "tile row 31" is the corner (columns 496 ..), tail only
+    const bool tails = G > 0 && db == 0;                 // the d < 8 wave(s) of a row block also take their rows' tail columns
 
     const int64_t rbeg = (int64_t)slab * a.rows_per_slab;
     const int64_t rend = min(rbeg + a.rows_per_slab, a.n);
@@ -135,8 +151,8 @@ __global__ __launch_bounds__(512, 2) void gram_cyclic_kernel(CycArgs a) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcW, (lds_ptr_t)(lds + buf * BUF + KC * LDP), 16, lane * 16, chunk * KC * 8, 0, 0);
     };
 
-    cyc_acc_zero<128>();
-    if constexpr (G > 0) cyc_tail_zero<2 * RW * G>();
+    cyc_acc_zero<64 * RW>();
+    if constexpr (G > 0) cyc_tail_zero<RW, G>();
 
     // Pipeline (chunk c = k-steps (c, 0), (c, 1); stage = c mod 4):
     //   (c, 0): MFMAs;  then s_waitcnt for chunk c + 1 (issued 1.5 chunks ago) + s_barrier: chunk c + 1 is visible to every wave,
@@ -145,35 +161,13 @@ __global__ __launch_bounds__(512, 2) void gram_cyclic_kernel(CycArgs a) {
     // Chunks past the end of the slab are fetched (and computed: the chunk loop runs in rounds of four stages) all the same:
     // zeros through the descriptor's bounds check, no traffic, and the in-order vmcnt bookkeeping stays a constant.
 #pragma unroll
-    for (int ch = 0; ch < (DLSA_CYC_PAIR ? 2 : 3); ++ch) {
+    for (int ch = 0; ch < 3; ++ch) {
 #pragma unroll
         for (int pc = 0; pc < PIECES; ++pc) dma_piece(ch, ch, pc);
         dma_w(ch, ch);
     }
-#if DLSA_CYC_FLAGS
-    // Per-stage hand-off flags instead of the workgroup barrier: byte w of LANDED[s] = tag of the chunk whose pieces wave w has
-    // seen land in stage s; byte w of DONE[s] = tag of the chunk wave w has finished reading there.  tag(c) = (c / 4 + 1) & 255.
-    // A wave reads a chunk once all eight LANDED bytes carry its tag, and overwrites a stage once all eight DONE bytes do.
-    unsigned long long* const flagL = reinterpret_cast<unsigned long long*>(lds + CYC_NST * BUF);      // [4]
-    unsigned long long* const flagD = flagL + 4;                                                        // [4]
-    if (tid < 8) flagL[tid] = 0ull;
-    __syncthreads();
-    auto tag_of = [](int c) { return (unsigned)(((c >> 2) + 1) & 255); };
-    auto post = [&](unsigned long long* f, int stage, int c) {
-        if (lane == 0) reinterpret_cast<volatile unsigned char*>(f + stage)[wave] = (unsigned char)tag_of(c);
-    };
-    auto await = [&](unsigned long long* f, int stage, int c) {
-        const unsigned long long want = 0x0101010101010101ull * tag_of(c);
-        while (__builtin_amdgcn_readfirstlane((int)(*reinterpret_cast<volatile unsigned long long*>(f + stage) != want)))
-            __builtin_amdgcn_s_sleep(1);
-    };
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_PER_CHUNK) : "memory");
-    post(flagL, 0, 0);
-    await(flagL, 0, 0);
-#else
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DLSA_CYC_PAIR ? 0 : 2 * DMA_PER_CHUNK) : "memory");
     asm volatile("s_barrier" ::: "memory");
-#endif
 
     // Per-lane BYTE addresses of the fragments inside stage pair sp (stages 2 sp, 2 sp + 1): row (lane >> 4) of a k-step,
     // column 16 tile + (lane & 15).  Stage parity and k-step are compile-time immediates of the ds_read (the chunk loop is
@@ -183,12 +177,22 @@ __global__ __launch_bounds__(512, 2) void gram_cyclic_kernel(CycArgs a) {
 #pragma unroll
     for (int sp = 0; sp < 2; ++sp) {
         const int sb = sp * 2 * BUF * 8;
-        adA[sp][0] = sb + lane_part + 128 * i0;
-        adA[sp][1] = sb + lane_part + 128 * (i0 + 1);                    // row block 15: tile 31 = the corner (columns 496 ..), tail only
+#pragma unroll
+        for (int r = 0; r < RW; ++r) adA[sp][r] = sb + lane_part + 128 * (i0 + r);        // tile 31 = the corner (columns 496 ..), tail only
 #pragma unroll
         for (int j = 0; j < NB; ++j) adB[sp][j] = sb + lane_part + 128 * ((i0 + d0 + j) % CYC_NT);
         adT[sp] = sb + ((lane >> 4) * LDP + CYC_C0 + (lane & 3)) * 8;      // tail columns, broadcast to the 4 blocks
         adW[sp] = sb + (KC * LDP + (lane >> 4)) * 8;
+    }
+    if constexpr (RW == 1) {
+        // 128 registers: keep hipcc from folding the second stage pair's offset (beyond a ds_read immediate) and the read's own
+        // immediate into further address registers -- one register per fragment and stage pair, as written
+#pragma unroll
+        for (int sp = 0; sp < 2; ++sp) {
+            asm volatile("" : "+v"(adA[sp][0]), "+v"(adT[sp]), "+v"(adW[sp]));
+#pragma unroll
+            for (int j = 0; j < NB; ++j) asm volatile("" : "+v"(adB[sp][j]));
+        }
     }
     const char* ldsb = (const char*)lds;
     struct Frag { double fa[RW], fb[NB], bt[GA], wv; };
@@ -206,169 +210,126 @@ __global__ __launch_bounds__(512, 2) void gram_cyclic_kernel(CycArgs a) {
         }
         f.wv = HASW ? ld(adW[sp], ((ST & 1) * BUF + ks * 4) * 8) : 1.0;
     };
-    auto kstep = [&](const Frag& f, int chunk_dma, int buf_dma, bool issue) {
-        // the weight goes on the A side: 2 multiplications per k-step instead of 9 (and the tail rows come scaled for free)
-        double aw[RW];
-#pragma unroll
-        for (int r = 0; r < RW; ++r) aw[r] = HASW ? f.fa[r] * f.wv : f.fa[r];
-        cyc_row<0>(aw[0], f.fb[0], f.fb[1], f.fb[2], f.fb[3], f.fb[4], f.fb[5], f.fb[6], f.fb[7]);
-        if (issue) {
-#pragma unroll
-            for (int k = 0; k < PPR; ++k) dma_piece(chunk_dma, buf_dma, k);
-        }
-        // Row block 15 has no second tile row.  With tail columns (G > 0) its waves run the 8 MFMAs all the same, on the corner
-        // fragment, and drop the result: with one light SIMD that workgroup ran ~1 % faster than its three partners, ended
-        // 400 us ahead of them (bench/cyc_drift.py) and took its rows out of their L2 window -- fabric traffic 1.8x, 97.7
-        // instead of 94.9 ms at p = 500.  Without tail columns the four stay within 3 us of each other either way and the
-        // dummy MFMAs only cost power (92.8 vs 90.8 ms at p = 496), so there the row is skipped.  (An explicit meeting of
-        // the four workgroups every 64 chunks -- arrival counter + bounded poll -- was measured too: no gain over this.)
-        if (G > 0 || two_rows)
-            cyc_row<1>(aw[1], f.fb[1], f.fb[2], f.fb[3], f.fb[4], f.fb[5], f.fb[6], f.fb[7], f.fb[8]);
-        if (issue) {
-#pragma unroll
-            for (int k = 0; k < PPR; ++k) dma_piece(chunk_dma, buf_dma, PPR + k);
-            dma_w(chunk_dma, buf_dma);
-        }
-        // The tail columns: 2 G small MFMAs on the A fragments the wave has just scaled.  (Measured same-box at p = 500: issuing
-        // them in batches of 2 / 4 k-steps, or one tile row per wave of the SIMD pair instead of both on the d < 8 wave: 0.5-2.5 %
-        // slower each; G = 1 and G = 2 cost the same.)
-        if constexpr (G > 0) {
-            if (tails) cyc_tail_a<RW, G>(aw, f.bt);
-        }
+    // "Tile row 31" has no tiles.  With tail columns (G > 0) its waves run the 8 MFMAs all the same, on the corner
+    // fragment, and drop the result: with one light SIMD that workgroup ran ~1 % faster than its three partners, ended
+    // 400 us ahead of them (bench/cyc_drift.py) and took its rows out of their L2 window -- fabric traffic 1.8x, 97.7
+    // instead of 94.9 ms at p = 500.  Without tail columns the four stay within 3 us of each other either way and the
+    // dummy MFMAs only cost power (92.8 vs 90.8 ms at p = 496), so there the row is skipped.  (An explicit meeting of
+    // the four workgroups every 64 chunks -- arrival counter + bounded poll -- was measured too: no gain over this.)
+    // Its tail MFMAs are real: they give the corner block H[496.., 496..].
+    const bool last_row_runs = G > 0 || full_rows;
+    auto chunk_barrier = [&]() {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_CHUNK) : "memory");      // chunk c + 1 has landed (c + 2 may be in flight)
+        asm volatile("s_barrier" ::: "memory");
     };
 
-    Frag fr0, fr1;
-    load_frags(0, 0, fr0);
-    if (DLSA_CYC_PRIO == 1 && db) __builtin_amdgcn_s_setprio(1);
-    if (DLSA_CYC_PRIO == 2 && !db) __builtin_amdgcn_s_setprio(1);
-#if DLSA_CYC_FLAGS
-    for (int c4 = 0; c4 < nchunks; c4 += 4) {
+    if constexpr (RW == 2) {
+        auto kstep = [&](const Frag& f, int chunk_dma, int buf_dma, bool issue) {
+            // the weight goes on the A side: 2 multiplications per k-step instead of 9 (and the tail rows come scaled for free)
+            double aw[RW];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {                        // chunk c = c4 + u sits in stage u
-            const int c = c4 + u;
-            load_frags(u, 1, fr1);                               // (c, 1), while (c, 0) computes
-            if (c > 0) post(flagD, (u + 3) & 3, c - 1);          // this wave's reads of chunk c - 1 were consumed by the MFMAs it has issued
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                double aw[RW];
+            for (int r = 0; r < RW; ++r) aw[r] = HASW ? f.fa[r] * f.wv : f.fa[r];
+            cyc_row<0>(aw[0], f.fb[0], f.fb[1], f.fb[2], f.fb[3], f.fb[4], f.fb[5], f.fb[6], f.fb[7]);
+            if (issue) {
 #pragma unroll
-                for (int r = 0; r < RW; ++r) aw[r] = HASW ? fr0.fa[r] * fr0.wv : fr0.fa[r];
-                cyc_row<0>(aw[0], fr0.fb[0], fr0.fb[1], fr0.fb[2], fr0.fb[3], fr0.fb[4], fr0.fb[5], fr0.fb[6], fr0.fb[7]);
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_CHUNK) : "memory");      // this wave's pieces of chunk c + 1 have landed
-                post(flagL, (u + 1) & 3, c + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (G > 0 || two_rows)
-                    cyc_row<1>(aw[1], fr0.fb[1], fr0.fb[2], fr0.fb[3], fr0.fb[4], fr0.fb[5], fr0.fb[6], fr0.fb[7], fr0.fb[8]);
-                if constexpr (G > 0) {
-                    if (tails) cyc_tail_a<RW, G>(aw, fr0.bt);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                for (int k = 0; k < PPR; ++k) dma_piece(chunk_dma, buf_dma, k);
             }
-            await(flagL, (u + 1) & 3, c + 1);                    // every wave's pieces of chunk c + 1 are there
-            load_frags((u + 1) & 3, 0, fr0);                     // (c + 1, 0), while (c, 1) computes
-            __builtin_amdgcn_sched_barrier(0);
-            if (c > 0) await(flagD, (u + 3) & 3, c - 1);         // every wave has left chunk c - 1: its stage takes chunk c + 3
-            __builtin_amdgcn_sched_barrier(0);
-            kstep(fr1, c + 3, (u + 3) & 3, true);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#elif DLSA_CYC_PAIR
-    // One barrier per PAIR of chunks: pair (c, c + 1) sits in stages (u, u + 1), the DMA of the next pair goes into the other two
-    // stages behind the tile rows of this pair's first two k-steps and is waited for (vmcnt 0) at the pair's end.  Half the
-    // barriers: the skew between the four SIMDs of a workgroup is paid once per 16 rows instead of once per 8.
-    for (int c4 = 0; c4 < nchunks; c4 += 4) {
+            if (last_row_runs)
+                cyc_row<1>(aw[1], f.fb[1], f.fb[2], f.fb[3], f.fb[4], f.fb[5], f.fb[6], f.fb[7], f.fb[8]);
+            if (issue) {
 #pragma unroll
-        for (int u = 0; u < 4; u += 2) {
-            const int c = c4 + u;
-            load_frags(u, 1, fr1);
-            __builtin_amdgcn_sched_barrier(0);
-            kstep(fr0, c + 2, (u + 2) & 3, true);
-            __builtin_amdgcn_sched_barrier(0);
-            load_frags(u + 1, 0, fr0);
-            __builtin_amdgcn_sched_barrier(0);
-            kstep(fr1, c + 3, (u + 3) & 3, true);
-            __builtin_amdgcn_sched_barrier(0);
-            load_frags(u + 1, 1, fr1);
-            __builtin_amdgcn_sched_barrier(0);
-            kstep(fr0, 0, 0, false);
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                double aw[RW];
-#pragma unroll
-                for (int r = 0; r < RW; ++r) aw[r] = HASW ? fr1.fa[r] * fr1.wv : fr1.fa[r];
-                cyc_row<0>(aw[0], fr1.fb[0], fr1.fb[1], fr1.fb[2], fr1.fb[3], fr1.fb[4], fr1.fb[5], fr1.fb[6], fr1.fb[7]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (db) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    asm volatile("s_barrier" ::: "memory");
-                }
-                if (G > 0 || two_rows)
-                    cyc_row<1>(aw[1], fr1.fb[1], fr1.fb[2], fr1.fb[3], fr1.fb[4], fr1.fb[5], fr1.fb[6], fr1.fb[7], fr1.fb[8]);
-                if constexpr (G > 0) {
-                    if (tails) cyc_tail_a<RW, G>(aw, fr1.bt);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (!db) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    asm volatile("s_barrier" ::: "memory");
-                }
+                for (int k = 0; k < PPR; ++k) dma_piece(chunk_dma, buf_dma, PPR + k);
+                dma_w(chunk_dma, buf_dma);
             }
-            load_frags((u + 2) & 3, 0, fr0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#else
-    for (int c4 = 0; c4 < nchunks; c4 += 4) {
+            // The tail columns: 2 G small MFMAs on the A fragments the wave has just scaled.  (Measured same-box at p = 500: issuing
+            // them in batches of 2 / 4 k-steps, or one tile row per wave of the SIMD pair instead of both on the d < 8 wave: 0.5-2.5 %
+            // slower each; G = 1 and G = 2 cost the same.)
+            if constexpr (G > 0) {
+                if (tails) cyc_tail_a<RW, G>(aw, f.bt);
+            }
+        };
+
+        Frag fr0, fr1;
+        load_frags(0, 0, fr0);
+        for (int c4 = 0; c4 < nchunks; c4 += 4) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {                        // chunk c4 + u sits in stage u
-            load_frags(u, 1, fr1);                               // (c, 1), while (c, 0) computes
-            __builtin_amdgcn_sched_barrier(0);
+            for (int u = 0; u < 4; ++u) {                        // chunk c4 + u sits in stage u
+                load_frags(u, 1, fr1);                               // (c, 1), while (c, 0) computes
+                __builtin_amdgcn_sched_barrier(0);
 #if DLSA_CYC_SPLIT
-            // The two waves of a SIMD (db = 0 / 1) meet the chunk barrier half an MFMA block apart: the db = 1 wave after its
-            // first tile row, the db = 0 wave after the whole k-step.  At the same program point both would run their
-            // post-barrier reads and DMA issue with the matrix pipe idle; offset, each covers the other (gram_plan_kernel.inc).
-            {
-                double aw[RW];
+                // The two waves of a SIMD (db = 0 / 1) meet the chunk barrier half an MFMA block apart: the db = 1 wave after its
+                // first tile row, the db = 0 wave after the whole k-step.  At the same program point both would run their
+                // post-barrier reads and DMA issue with the matrix pipe idle; offset, each covers the other (gram_plan_kernel.inc).
+                {
+                    double aw[RW];
 #pragma unroll
-                for (int r = 0; r < RW; ++r) aw[r] = HASW ? fr0.fa[r] * fr0.wv : fr0.fa[r];
-                cyc_row<0>(aw[0], fr0.fb[0], fr0.fb[1], fr0.fb[2], fr0.fb[3], fr0.fb[4], fr0.fb[5], fr0.fb[6], fr0.fb[7]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (db) {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_CHUNK) : "memory");
-                    asm volatile("s_barrier" ::: "memory");
+                    for (int r = 0; r < RW; ++r) aw[r] = HASW ? fr0.fa[r] * fr0.wv : fr0.fa[r];
+                    cyc_row<0>(aw[0], fr0.fb[0], fr0.fb[1], fr0.fb[2], fr0.fb[3], fr0.fb[4], fr0.fb[5], fr0.fb[6], fr0.fb[7]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (db) chunk_barrier();
+                    if (last_row_runs)
+                        cyc_row<1>(aw[1], fr0.fb[1], fr0.fb[2], fr0.fb[3], fr0.fb[4], fr0.fb[5], fr0.fb[6], fr0.fb[7], fr0.fb[8]);
+                    if constexpr (G > 0) {
+                        if (tails) cyc_tail_a<RW, G>(aw, fr0.bt);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (!db) chunk_barrier();
                 }
-                if (G > 0 || two_rows)
-                    cyc_row<1>(aw[1], fr0.fb[1], fr0.fb[2], fr0.fb[3], fr0.fb[4], fr0.fb[5], fr0.fb[6], fr0.fb[7], fr0.fb[8]);
-                if constexpr (G > 0) {
-                    if (tails) cyc_tail_a<RW, G>(aw, fr0.bt);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (!db) {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_CHUNK) : "memory");  // chunk c + 1 has landed (c + 2 may be in flight)
-                    asm volatile("s_barrier" ::: "memory");
-                }
-            }
 #else
-            kstep(fr0, 0, 0, false);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_CHUNK) : "memory");      // chunk c + 1 has landed (c + 2 may be in flight)
-            asm volatile("s_barrier" ::: "memory");
+                kstep(fr0, 0, 0, false);
+                __builtin_amdgcn_sched_barrier(0);
+                chunk_barrier();
 #endif
-            load_frags((u + 1) & 3, 0, fr0);                     // (c + 1, 0), while (c, 1) computes
+                load_frags((u + 1) & 3, 0, fr0);                     // (c + 1, 0), while (c, 1) computes
+                __builtin_amdgcn_sched_barrier(0);
+                kstep(fr1, c4 + u + 3, (u + 3) & 3, true);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    } else {
+        // Four waves per SIMD, one fragment set per wave (a second one does not fit 128 registers): per chunk a wave waits for the
+        // fragments of (c, 0), issues their 8 MFMAs, requests (c, 1), issues those 8, issues its DMA pieces of chunk c + 3 and
+        // requests (c + 1, 0).  A SIMD's matrix pipe idles only when all four of its waves are outside their MFMAs at once, and
+        // the four meet the chunk's barrier at the quarter CYC_BAR_Q[slot] of the chunk: after 4 q MFMAs.  Any q in 1 .. 4 is
+        // safe: the barrier comes before the wave's DMA issue of chunk c + 3 (every wave has then read the last fragments of
+        // chunk c - 1, whose stage that DMA overwrites) and before its request of (c + 1, 0) (chunk c + 1 is visible).
+        const int bq = slot == 0 ? CYC_BAR_Q[0] : slot == 1 ? CYC_BAR_Q[1] : slot == 2 ? CYC_BAR_Q[2] : CYC_BAR_Q[3];
+        // one k-step: the barrier slots q0 + 1 (mid-row) and q0 + 2 (behind the row and its tail MFMAs)
+        auto kstep1 = [&](const Frag& f, int q0) {
+            double aw[1] = {HASW ? f.fa[0] * f.wv : f.fa[0]};
+            if (last_row_runs) cyc_half<0, 0>(aw[0], f.fb[0], f.fb[1], f.fb[2], f.fb[3]);
             __builtin_amdgcn_sched_barrier(0);
-            kstep(fr1, c4 + u + 3, (u + 3) & 3, true);
+            if (bq == q0 + 1) chunk_barrier();
+            if (last_row_runs) cyc_half<0, 1>(aw[0], f.fb[4], f.fb[5], f.fb[6], f.fb[7]);
+            if constexpr (G > 0) {
+                if (tails) cyc_tail_a<1, G>(aw, f.bt);
+            }
             __builtin_amdgcn_sched_barrier(0);
+            if (bq == q0 + 2) chunk_barrier();
+        };
+        Frag fr;
+        load_frags(0, 0, fr);
+        for (int c4 = 0; c4 < nchunks; c4 += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {                        // chunk c4 + u sits in stage u
+                kstep1(fr, 0);
+                load_frags(u, 1, fr);
+                __builtin_amdgcn_sched_barrier(0);
+                kstep1(fr, 2);
+#pragma unroll
+                for (int k = 0; k < PPR; ++k) dma_piece(c4 + u + 3, (u + 3) & 3, k);
+                dma_w(c4 + u + 3, (u + 3) & 3);
+                load_frags((u + 1) & 3, 0, fr);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     }
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the zero-fill DMA of the chunks past the end
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");       // the last MFMAs retire before the accumulators are read
 
     // epilogue: every tile of the slab's triangle belongs to exactly one wave of the group -- store straight to the partial
     double* __restrict__ P = a.partial + (int64_t)slab * CYC_PP * CYC_PP;
-    const int nt_rows = two_rows ? 2 : 1;
+    const int nt_rows = full_rows ? RW : RW - 1;
     cyc_for_tiles<0, 8 * RW>([&](int k, double (&v)[4]) {
         const int r = k >> 3, cdist = k & 7;
         if (r < nt_rows) {
@@ -383,13 +344,26 @@ __global__ __launch_bounds__(512, 2) void gram_cyclic_kernel(CycArgs a) {
     });
     if constexpr (G > 0) {
         // tail accumulator (s, g), lane l: H[16 (i0 + s) + 4 bk + i][496 + 4 g + j], i = l >> 4, bk = (l & 15) >> 2, j = l & 3
-        if (tails) cyc_for_tails<0, RW * G>([&](int idx, double v) {
+        // (tile row 31 included: rows 496 .., the corner block)
+        if (tails) cyc_for_tails<RW, 0, RW * G>([&](int idx, double v) {
             const int s = idx / G, g = idx - s * G;
             const int row = 16 * (i0 + s) + 4 * ((lane & 15) >> 2) + (lane >> 4), col = CYC_C0 + 4 * g + (lane & 3);
             P[(int64_t)row * CYC_PP + col] = v;
         });
     }
     if (probe && lane == 0) *a.clk = __builtin_readcyclecounter() - t_begin;
+}
+
+// The dispatched kernel: the tile rows per wave, and with them the workgroup size, follow from G.
+template <bool HASW, int G>
+__global__ __launch_bounds__(1024 / cyc_rw(G), cyc_rw(G)) void gram_cyclic_kernel(CycArgs a) {
+    cyc_body<HASW, G, cyc_rw(G)>(a);
+}
+
+// Its twin: the two-waves-per-SIMD shape (gram_variant bit 16), same bits in H -- for A/B runs and the bit-identity test.
+template <bool HASW, int G>
+__global__ __launch_bounds__(512, 2) void gram_cyclic_rw2_kernel(CycArgs a) {
+    cyc_body<HASW, G, 2>(a);
 }
 
 static int cyc_slabs(int64_t n, int64_t& rows_per_slab) {
@@ -427,19 +401,25 @@ int gram_cyclic_f64(const double* X, int64_t ldx, const double* w, int64_t n, in
         set_error("gram: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
         return DLSA_ERR_WORKSPACE;
     }
-    const int g = a.p <= CYC_C0 ? 0 : (a.p - CYC_C0 + 3) / 4;
-    const size_t shm = (size_t)CYC_NST * CYC_BUF * 8 + (DLSA_CYC_FLAGS ? 64 : 0);
+    const int g = a.p <= CYC_C0 ? 0 : std::min((a.p - CYC_C0 + 3) / 4, 3);
+    const size_t shm = (size_t)CYC_NST * CYC_BUF * 8;
     const int blocks = a.nslab * CYC_GROUP;
-#define DLSA_LAUNCH_CYC(HW, GV) do { \
-        DLSA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_cyclic_kernel<HW, GV>), \
+    // gram_variant bit 16 (DLSA_GRAM_DBG 16): the two-waves-per-SIMD twin where the dispatched kernel is the four-wave shape
+    // (valid results, the same bits: A/B runs and tests/test_gpu_gram_cyclic_rw1.py)
+    const char* knob = kernel_knob("DLSA_GRAM_DBG");
+    const bool twin = knob && (atoi(knob) & 16) && cyc_rw(g) != 2;
+#define DLSA_LAUNCH_CYC(KERNEL, THREADS, HW, GV) do { \
+        DLSA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL<HW, GV>), \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
-        hipLaunchKernelGGL((gram_cyclic_kernel<HW, GV>), dim3(blocks), dim3(512), shm, stream, a); } while (0)
+        hipLaunchKernelGGL((KERNEL<HW, GV>), dim3(blocks), dim3(THREADS), shm, stream, a); } while (0)
 #define DLSA_LAUNCH_CYC_G(HW) do { switch (g) { \
-        case 0: DLSA_LAUNCH_CYC(HW, 0); break; case 1: DLSA_LAUNCH_CYC(HW, 1); break; \
-        case 2: DLSA_LAUNCH_CYC(HW, 2); break; default: DLSA_LAUNCH_CYC(HW, 3); break; } } while (0)
+        case 0: if (twin) DLSA_LAUNCH_CYC(gram_cyclic_rw2_kernel, 512, HW, 0); else DLSA_LAUNCH_CYC(gram_cyclic_kernel, 1024 / cyc_rw(0), HW, 0); break; \
+        case 1: if (twin) DLSA_LAUNCH_CYC(gram_cyclic_rw2_kernel, 512, HW, 1); else DLSA_LAUNCH_CYC(gram_cyclic_kernel, 1024 / cyc_rw(1), HW, 1); break; \
+        case 2: if (twin) DLSA_LAUNCH_CYC(gram_cyclic_rw2_kernel, 512, HW, 2); else DLSA_LAUNCH_CYC(gram_cyclic_kernel, 1024 / cyc_rw(2), HW, 2); break; \
+        default: if (twin) DLSA_LAUNCH_CYC(gram_cyclic_rw2_kernel, 512, HW, 3); else DLSA_LAUNCH_CYC(gram_cyclic_kernel, 1024 / cyc_rw(3), HW, 3); break; } } while (0)
     if (w) DLSA_LAUNCH_CYC_G(true);
     else DLSA_LAUNCH_CYC_G(false);
-    note_gram_kernel(a.clk, stream, "gram_cyclic_kernel<%s,%d>", w ? "true" : "false", g > 3 ? 3 : g);
+    note_gram_kernel(a.clk, stream, twin ? "gram_cyclic_rw2_kernel<%s,%d>" : "gram_cyclic_kernel<%s,%d>", w ? "true" : "false", g);
 #undef DLSA_LAUNCH_CYC_G
 #undef DLSA_LAUNCH_CYC
     DLSA_HIP_CHECK(hipGetLastError());

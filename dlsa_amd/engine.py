@@ -531,7 +531,7 @@ class KernelOptions:
     chol_small: Optional[bool] = None       # one-launch SPD inverse for p <= 112
     gram_wide_f32: Optional[bool] = None    # the fp32 wide Gram kernel (p >= 768)
     onehot_ordered: Optional[int] = None    # 0 unordered, 1 ordered floating point
-    gram_variant: Optional[int] = None      # valid-result A/B bits of the fp64 Gram dispatch (2 | 4 | 8 | 32 | 64 | 256)
+    gram_variant: Optional[int] = None      # valid-result A/B bits of the fp64 Gram dispatch (2 | 4 | 8 | 32 | 64 | 256; 16 = the cyclic kernel's two-wave twin)
     cooperative: Optional[bool] = None      # multi-workgroup kernels launched cooperatively
 
     def as_c(self):

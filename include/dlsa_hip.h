@@ -188,7 +188,8 @@ typedef struct dlsa_kernel_options {
     int chol_small;      /* one-launch SPD inverse for p <= 112; 0 = the blocked Cholesky                                  */
     int gram_wide_f32;   /* the fp32 wide Gram kernel (p >= 768); 0 = the panel kernel                                     */
     int onehot_ordered;  /* accumulation of the structured one-hot passes: 0 unordered, 1 ordered floating point (the Gram's default for caller weights is the exact fixed-point mode) */
-    int gram_variant;    /* valid-result A/B bits of the fp64 Gram dispatch: 2 | 4 | 8 | 32 | 64 | 256 (gram.hip)          */
+    int gram_variant;    /* valid-result A/B bits of the fp64 Gram dispatch: 2 | 4 | 8 | 32 | 64 | 256 (gram.hip),
+                            16 = the two-waves-per-SIMD twin of the cyclic kernel, same bits (gram_cyclic.hip)            */
     int cooperative;     /* 1 = multi-workgroup kernels launched with hipLaunchCooperativeKernel; default 0: plain launch + bounded barrier (streams created after a cooperative launch serialise on this runtime) */
 } dlsa_kernel_options;
 void dlsa_kernel_options_init(dlsa_kernel_options* opt);        /* every field on automatic */

@@ -6,8 +6,9 @@ nothing in the C++ model stops a future hipcc from using the same registers betw
 VGPR spill slots, which on gfx950 are v_accvgpr_write / v_accvgpr_read pairs).  This script reads the code objects the
 library actually ships and asserts, per kernel:
   * no scratch: .private_segment_fixed_size == 0, .vgpr_spill_count == 0, .sgpr_spill_count == 0;
-  * .agpr_count == the accumulator count the generators planned (narrow_nreg / GPlan::NREG / 128 + 4 G);
-  * VGPRs + AGPRs fit two waves per SIMD (<= 256) where the kernel is launched that way;
+  * .agpr_count == the accumulator count the generators planned (narrow_nreg / GPlan::NREG / (64 + 2 G) per tile row of a
+    gram_cyclic wave);
+  * VGPRs + AGPRs fit two waves per SIMD (<= 256), or four (<= 128), where the kernel is launched that way;
   * NO v_accvgpr_read / v_accvgpr_write inside any loop (a cycle of the kernel's control-flow graph, found with Tarjan's
     algorithm on the disassembly's basic blocks): the only accumulator moves are the zeroing prologue and the store
     epilogue, both straight-line code outside the row loop.
@@ -24,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 LLVM = os.environ.get("DLSA_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+CYC_RW1_MAX_G = 3          # gram_cyclic.hip cyc_rw: the widths whose dispatched kernel runs four waves per SIMD (<= 128 registers)
 
 
 def tool(name):
@@ -181,9 +183,11 @@ def expected_agprs(name):
     if m:                                                          # irls_pass.hip: one wave per SIMD
         nt, g = int(m.group(1)), int(m.group(2))
         return 8 * (nt * (nt + 1) // 2) + 2 * (nt + 1) * g, 512
-    m = re.search(r"gram_cyclic_kernelILb[01]ELi(\d+)EE", name)
-    if m:
-        return 128 + 4 * int(m.group(1)), 256
+    m = re.search(r"gram_cyclic(_rw2)?_kernelILb[01]ELi(\d+)EE", name)
+    if m:                                                          # gram_cyclic.hip: cyc_rw(G) tile rows per wave, 8 tiles + 2 G tail registers each
+        g = int(m.group(2))
+        rw = 2 if m.group(1) or g > CYC_RW1_MAX_G else 1
+        return 64 * rw + 2 * rw * g, 128 * rw                      # 16 / rw waves per workgroup = 4 / rw per SIMD
     m = re.search(r"gram_plan_kernelILb[01]ELi(\d+)ELi(\d+)EE", name)
     if m:
         import gen_gram_plan_asm as gp
