@@ -144,6 +144,9 @@ SIGNATURES = {
                                             ctypes.POINTER(c_dbl), c_vp, c_sz, c_vp]),
     "dlsa_gram_plan_check": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "dlsa_gram_wide_plan_check": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "dlsa_newton_solve_probe_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "dlsa_newton_solve_probe_f64": (c_int, [c_int, c_vp, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                            c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void chol_diag_kernel(double* __restrict__ L, i
         if (j < nb) {                                        // wave-uniform
             const double d = __shfl(r[j], j, 64);            // the pivot sits in lane j
             double sq;
-            if (!(d > 0.0) || !isfinite(d)) { bad = isfinite(d) ? 1 : 2; sq = 1.0; }
+            if (!(d > 0.0) || !isfinite(d)) { bad = max(bad, isfinite(d) ? 1 : 2); sq = 1.0; }   // the worst code of the block
             else sq = sqrt(d);
             const double lj = (lane == j) ? sq : r[j] / sq;  // l_ij for lane i >= j
             if (lane >= j) r[j] = lj;
@@ -529,3 +529,58 @@ int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const doubl
 }
 
 }  // namespace dlsa
+
+// ---------------------------------------------------------------------------------------------------------------
+// Test hook (include/dlsa_hip.h): one route of the step solver on the caller's systems through the launch functions
+// above, raw results out.  Inside a fit a wrong step only costs passes (the gradient and Sig_inv come from the data
+// passes), so the routes are compared with an extended-precision solve here instead.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+size_t dlsa_newton_solve_probe_workspace_bytes(int route, int p, int count) {
+    if (route < 0 || route > 4 || p <= 0 || count <= 0) return 0;
+    return 256 + (route == 2 ? dlsa::align_up((size_t)p * p * sizeof(double), 256) : 0);
+}
+
+int dlsa_newton_solve_probe_f64(int route, const double* S, int64_t lds, int p, int count, int64_t ss, const double* v,
+                                const double* v2, const double* ref, int64_t sv, double* x, double* M, int64_t sm,
+                                double* stats, int64_t st, const int* active, void* ws, size_t ws_bytes, void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(route >= 0 && route <= 4, "newton_solve_probe: route %d (0 factor, 1 reuse, 2 inverse, 3 sweep, 4 batched sweep)", route);
+    DLSA_REQUIRE(S && v && x && M && stats, "newton_solve_probe: null argument");
+    DLSA_REQUIRE(p > 0 && lds >= p, "newton_solve_probe: bad shape p=%d lds=%lld", p, (long long)lds);
+    DLSA_REQUIRE((route == 1) == (v2 != nullptr), "newton_solve_probe: v2 is the second right-hand side of route 1 alone");
+    if (route == 4) {
+        DLSA_REQUIRE(count > 0, "newton_solve_probe: count=%d", count);
+        DLSA_REQUIRE(count == 1 || (ss >= (int64_t)(p - 1) * lds + p && sv >= p && sm >= (int64_t)p * p && st >= 3),
+                     "newton_solve_probe: strides S %lld, vectors %lld, M %lld, stats %lld overlap at p=%d lds=%lld",
+                     (long long)ss, (long long)sv, (long long)sm, (long long)st, p, (long long)lds);
+    } else {
+        DLSA_REQUIRE(count == 1 && !active, "newton_solve_probe: route %d takes one system and no mask", route);
+    }
+    const size_t need = dlsa_newton_solve_probe_workspace_bytes(route, p, count);
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
+        set_error("newton_solve_probe: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
+        return DLSA_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int rc = DLSA_OK;
+    if (route <= 2) {
+        double* L = route == 2 ? (double*)ws : M;
+        rc = launch_chol_solve(S, lds, 0, v, 0, ref, 0, p, 1, L, x, 0, stats, 0, s, 0);
+        if (rc) return rc;
+        if (route == 1) rc = launch_chol_solve(S, lds, 0, v2, 0, ref, 0, p, 1, L, x, 0, stats, 0, s, 1);
+        if (route == 2) {
+            rc = launch_tri_inverse(L, p, M, s);
+            if (rc) return rc;
+            rc = launch_inv_apply(M, p, v, ref, x, stats, s);
+        }
+    } else if (route == 3) {
+        rc = launch_chol_small(S, lds, p, v, ref, M, x, stats, s);
+    } else {
+        rc = launch_chol_small_batched(count, S, lds, ss, p, v, ref, sv, M, sm, x, stats, st, active, s);
+    }
+    return rc;
+}
+
+}  // extern "C"

@@ -952,6 +952,42 @@ def spd_solve(S, v):
     return theta
 
 
+NEWTON_ROUTES = {"factor": 0, "reuse": 1, "inverse": 2, "sweep": 3, "sweep_batched": 4}
+
+
+def newton_solve_probe(route, S, v, p, lds, count=1, ref=None, v2=None, active=None, ss=0, sv=0, sm=0, st=0,
+                       x=None, M=None, stats=None):
+    """Test hook (dlsa_newton_solve_probe_f64): one route of the Newton-step solver on caller-supplied systems, raw results.
+    S, v, ref, v2 are flat fp64 device buffers: system b is the p x p matrix at S[b ss:] with row pitch lds and the vectors at
+    v / ref / x[b sv:]; route "sweep_batched" takes `count` systems and an int32 `active` mask, every other route one.
+    x, M (L, Linv or Hinv by route; count blocks of p x p at pitch sm) and stats (3 doubles at pitch st) may be passed
+    pre-filled: the outputs of an inactive system are left as they are.  Returns (x, M, stats) as flat tensors."""
+    lib = _lib.load()
+    r = NEWTON_ROUTES[route] if isinstance(route, str) else int(route)
+    _require_gpu(S, v, ref, v2, active, x, M, stats)
+    p, lds, count = int(p), int(lds), int(count)
+    if p <= 0 or lds < p or count <= 0:
+        raise ValueError("newton_solve_probe: bad shape p=%d lds=%d count=%d" % (p, lds, count))
+    last = count - 1
+    need = {"S": last * ss + (p - 1) * lds + p, "v": last * sv + p, "M": last * sm + p * p, "stats": last * st + 3}
+    dev = S.device
+    x = torch.empty((need["v"],), dtype=torch.float64, device=dev) if x is None else x
+    M = torch.empty((need["M"],), dtype=torch.float64, device=dev) if M is None else M
+    stats = torch.empty((need["stats"],), dtype=torch.float64, device=dev) if stats is None else stats
+    for name, t, n in (("S", S, need["S"]), ("v", v, need["v"]), ("ref", ref, need["v"]), ("v2", v2, p), ("x", x, need["v"]),
+                       ("M", M, need["M"]), ("stats", stats, need["stats"])):
+        if t is None:
+            continue
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < n:
+            raise ValueError("newton_solve_probe: %s must be a contiguous float64 buffer of at least %d elements" % (name, n))
+    if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() < count):
+        raise ValueError("newton_solve_probe: active must be a contiguous int32 tensor of count entries")
+    ws = _workspace(lib.dlsa_newton_solve_probe_workspace_bytes(r, p, count), dev)
+    check(lib.dlsa_newton_solve_probe_f64(r, _ptr(S), lds, p, count, ss, _ptr(v), _ptr(v2), _ptr(ref), sv, _ptr(x), _ptr(M), sm,
+                                          _ptr(stats), st, _ptr(active), _ptr(ws), ws.numel(), _stream()))
+    return x, M, stats
+
+
 def _solve_args(S, v, who):
     _require_gpu(S, v)
     _f64(S, "S")

@@ -542,6 +542,25 @@ int dlsa_gram_plan_check(int p, int* nitems, int* nslots, int* ntiles);
  * p % 4 == 0, 16-byte aligned rows). */
 int dlsa_gram_wide_plan_check(int p, int* nitems, int* nslots, int* ntiles);
 
+/* test hook: ONE route of the Newton-step solver (chol.hip) on caller-supplied systems, through the launch functions the
+ * fit drivers call, with the RAW results -- nothing is folded into a return code, no DLSA_CHOL_SMALL / DLSA_IRLS_INVERSE knob
+ * is read.  (No reference counterpart: the linear solves inside sklearn's newton-cg, dlsa/models.py:113.)
+ *   route 0  blocked Cholesky factor + triangular solves                        M = L    (p x p, zeros above the diagonal)
+ *   route 1  route 0 on `v`, then a second solve of `v2` that REUSES the factor  M = L    x / stats are the second solve's
+ *   route 2  route 0 on `v`, the factor's explicit inverse, x = Linv' (Linv v)   M = Linv (the factor stays in the workspace)
+ *   route 3  sweep-operator inverse, p <= 112, one system                        M = Hinv
+ *   route 4  the same, `count` systems in one launch                             M = Hinv
+ * S: p x p, row pitch lds >= p, read only.  v, ref (nullable), x: p doubles; stats: 3 doubles as the kernels leave them
+ * ([0] max|x|, [1] max|ref|, [2] info: 0 ok, 1 non-positive pivot, 2 NaN/Inf); M: p x p dense.  Routes 0 - 3 take count = 1
+ * and ignore the strides; route 4 works on system b at S + b ss, v / ref / x + b sv (ONE stride, as the launch has), M + b sm,
+ * stats + b st and leaves the outputs of a system with active[b] == 0 untouched (active: device ints, nullable).  v2 is
+ * route 1's second right-hand side (NULL elsewhere).  Argument checks come before any HIP call; p beyond a route's own
+ * limit is refused by that route's launch function with its message. */
+size_t dlsa_newton_solve_probe_workspace_bytes(int route, int p, int count);
+int dlsa_newton_solve_probe_f64(int route, const double* S, int64_t lds, int p, int count, int64_t ss, const double* v,
+                                const double* v2, const double* ref, int64_t sv, double* x, double* M, int64_t sm,
+                                double* stats, int64_t st, const int* active, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,34 @@ def test_onehot_plan_validates_its_descriptor_without_a_gpu(lib):
     assert lib.dlsa_onehot_workspace_bytes(None, 10) == 0
 
 
+def test_newton_solve_probe_checks_its_arguments_without_a_gpu(lib):
+    """the solver probe refuses a bad route, shape, mask, workspace or a p beyond the sweep's registers before any HIP call"""
+    from dlsa_amd import _lib
+    one = ctypes.c_void_p(256)                       # non-null, 256-aligned, never dereferenced: every call below is refused first
+
+    def probe(route, p=4, lds=4, count=1, v2=None, active=None, ws=one, ws_bytes=1 << 20, strides=(0, 0, 0, 0)):
+        ss, sv, sm, st = strides
+        return lib.dlsa_newton_solve_probe_f64(route, one, lds, p, count, ss, one, v2, None, sv, one, one, sm, one, st, active,
+                                               ws, ws_bytes, None)
+
+    assert probe(5) == 1 and "route 5" in _lib.last_error()
+    assert probe(-1) == 1
+    assert lib.dlsa_newton_solve_probe_f64(0, None, 4, 4, 1, 0, one, None, None, 0, one, one, 0, one, 0, None, one, 256, None) == 1
+    assert "null" in _lib.last_error()
+    assert probe(0, p=4, lds=3) == 1 and "lds=3" in _lib.last_error()
+    assert probe(0, p=0) == 1
+    assert probe(0, v2=one) == 1 and probe(1) == 1 and "route 1" in _lib.last_error()      # v2: route 1, and only route 1
+    assert probe(0, count=2) == 1 and probe(3, active=one) == 1 and "one system" in _lib.last_error()
+    assert probe(4, count=0) == 1
+    assert probe(4, count=2, strides=(16, 4, 15, 3)) == 1 and "overlap" in _lib.last_error()
+    assert probe(2, ws_bytes=256) == 3 and probe(0, ws=ctypes.c_void_p(264)) == 3 and probe(0, ws=None) == 3
+    assert probe(3, p=113, lds=113) == 1 and "spd_inverse_small: p=113" in _lib.last_error()
+    assert probe(4, p=113, lds=113, count=2, strides=(113 * 113, 113, 113 * 113, 3)) == 1 and "batched" in _lib.last_error()
+    q = lib.dlsa_newton_solve_probe_workspace_bytes
+    assert q(0, 500, 1) >= 256 and q(2, 500, 1) >= 500 * 500 * 8 + 256 and q(2, 500, 1) % 256 == 0
+    assert q(5, 500, 1) == 0 and q(0, 0, 1) == 0 and q(4, 100, 0) == 0
+
+
 def test_engine_refuses_cpu_tensors():
     import torch
     from dlsa_amd import engine

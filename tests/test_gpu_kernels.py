@@ -300,6 +300,17 @@ def test_spd_solve(eng):
     from dlsa_amd._lib import DlsaError
     with pytest.raises(DlsaError):
         eng.spd_solve(dev(np.array([[1.0, 2.0], [2.0, 1.0]])), dev(np.array([1.0, 1.0])))
+    # p = 65 (two full blocks and a block of one row): a non-positive pivot in the second block is NOT_SPD, a NaN entry is NAN
+    S = np.eye(65) + 0.01 * np.cos(np.add.outer(np.arange(65.0), np.arange(65.0)))
+    S[40, 40] -= 2.0
+    with pytest.raises(DlsaError) as e:
+        eng.spd_solve(dev(S), dev(np.ones(65)))
+    assert e.value.code == 4
+    S[40, 40] += 2.0
+    S[64, 63] = S[63, 64] = np.nan
+    with pytest.raises(DlsaError) as e:
+        eng.spd_solve(dev(S), dev(np.ones(65)))
+    assert e.value.code == 6
 
 
 # ---------------------------------------------------------------------------------------
