@@ -147,6 +147,8 @@ SIGNATURES = {
     "dlsa_newton_solve_probe_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "dlsa_newton_solve_probe_f64": (c_int, [c_int, c_vp, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
                                             c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "dlsa_newton_replay": (c_int, [c_int, c_dbl, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_int),
+                                   ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@
 // see profiles/).  The two triangular solves run in ONE workgroup with one barrier pair per block.
 // stats: [0] max|x|, [1] max|ref| (ref nullable), [2] info (0 ok, 1 not SPD, 2 NaN/Inf).
 #include "common.h"
+#include "host_calls.h"
 #include <algorithm>
 
 namespace dlsa {

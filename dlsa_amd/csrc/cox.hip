@@ -58,6 +58,7 @@
 // the smallest group max among ends of the row's own stratum at or after the row, each such max covers the row's eta, and
 // "every exponent <= 0" holds stratum by stratum.  A stratum without events has hazard 0 at all its ends and adds nothing.
 #include "common.h"
+#include "newton_fit.h"     // the Newton state, loop and epilogue; host_calls.h
 #include <math.h>
 #include <algorithm>
 #include <type_traits>
@@ -68,16 +69,6 @@ namespace dlsa {
 
 #include "logistic.h"      // exp_neg
 #include "rowdot.h"        // merged_reduce, row_of_lane, lane_of_row, read_lane_f64
-
-int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
-                  int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
-size_t gram_workspace_bytes_impl(int64_t n, int p, int elem_bytes);
-int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
-                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
-                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);
-int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s);
-int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
-int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
 
 constexpr int COX_THREADS = 256;
 constexpr int COX_WAVES = COX_THREADS / 64;
@@ -762,14 +753,6 @@ static CoxWs cox_workspace(char* base, int64_t max_rows, int p, int ties, bool s
     return w;
 }
 
-static int cox_check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
-    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
-        set_error("%s: workspace %zu bytes needed (256-aligned), got %zu", who, need, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
-    return DLSA_OK;
-}
-
 static bool cox_vec_ok(const double* X, int64_t ldx, int p) {
     return (p % 2 == 0) && (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0);
 }
@@ -899,9 +882,8 @@ extern "C" {
 size_t dlsa_cox_strata_workspace_bytes(int64_t max_rows, int p, int ties, int stratified) {
     if (p <= 0 || p > 2048 || max_rows < 0 || (ties != DLSA_COX_TIES_BRESLOW && ties != DLSA_COX_TIES_EFRON)) return 0;
     if (stratified != 0 && stratified != 1) return 0;
-    // Newton state after the pass scratch: beta, prev, delta, g (p each), stats, the Cholesky factor (p x p)
-    return dlsa::align_up(dlsa::cox_workspace(nullptr, max_rows, p, ties, stratified != 0).total, 256) +
-           dlsa::align_up(8 * (size_t)(4 * p + 8), 256) + dlsa::align_up(8 * (size_t)p * p, 256);
+    // the Newton state after the pass scratch
+    return dlsa::align_up(dlsa::cox_workspace(nullptr, max_rows, p, ties, stratified != 0).total, 256) + dlsa::newton_state_bytes(p);
 }
 
 size_t dlsa_cox_ties_workspace_bytes(int64_t max_rows, int p, int ties) { return dlsa_cox_strata_workspace_bytes(max_rows, p, ties, 0); }
@@ -917,7 +899,7 @@ int dlsa_cox_pass_strata_f64(const double* X, int64_t ldx, const double* time, c
                  (long long)n, p, (long long)ldx, (long long)ldh);
     DLSA_REQUIRE(ties == DLSA_COX_TIES_BRESLOW || ties == DLSA_COX_TIES_EFRON, "cox_pass: unknown ties method %d", ties);
     const CoxWs w = cox_workspace((char*)ws, n, p, ties, strata != nullptr);
-    int rc = cox_check_ws("cox", ws, ws_bytes, w.total);
+    int rc = newton_check_ws("cox", ws, ws_bytes, w.total);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     CoxRows rows;
@@ -959,85 +941,35 @@ int dlsa_cox_fit_strata_f64(const double* X, int64_t ldx, const double* time, co
     const bool stratified = strata != nullptr;
     char* wsc = (char*)ws;
     const CoxWs w = cox_workspace(wsc, max_rows, p, ties, stratified);
-    int rcw = cox_check_ws("cox_fit", ws, ws_bytes, dlsa_cox_strata_workspace_bytes(max_rows, p, ties, stratified ? 1 : 0));
+    int rcw = newton_check_ws("cox_fit", ws, ws_bytes, dlsa_cox_strata_workspace_bytes(max_rows, p, ties, stratified ? 1 : 0));
     if (rcw) return rcw;
     hipStream_t s = (hipStream_t)stream;
-    double* st = (double*)(wsc + align_up(w.total, 256));
-    double* stats = st;                 // [0] |delta|_inf, [1] |beta|_inf, [2] factor status, [3] loglik
-    double* beta = st + 8;
-    double* prev = beta + p;
-    double* delta = prev + p;
-    double* g = delta + p;
-    double* Lf = (double*)(wsc + align_up(w.total, 256) + align_up(8 * (size_t)(4 * p + 8), 256));
+    const NewtonState st = newton_state_at(wsc + align_up(w.total, 256), p);
     int overall = DLSA_OK;
     for (int k = 0; k < K; ++k) {
         const int64_t nk = part_offsets_host[k + 1] - part_offsets_host[k];
         const int64_t* ok = order + part_offsets_host[k];
         double* Hk = Sig_inv + (size_t)k * p * p;
-        double* ck = coef + (size_t)k * p;
-        double* sk = Sig_invMcoef + (size_t)k * p;
-        int st_k = DLSA_PART_EMPTY, iters = 0;
-        double ll = 0.0;
+        NewtonOutcome o{DLSA_PART_EMPTY, 0, 0, 0.0};
         if (nk > 0) {
             CoxRows rows;
             int rc = cox_rows(ok, nk, w.misc, &rows, s);
             if (rc) return rc;
             rc = cox_strata_flags(strata, ok, nk, w, s);
             if (rc) return rc;
-            DLSA_HIP_CHECK(hipMemsetAsync(beta, 0, (size_t)p * sizeof(double), s));
-            double ll_prev = -INFINITY;
-            bool have_prev = false, done = false;
-            int halvings = 0;
-            st_k = DLSA_PART_NOT_CONVERGED;
-            for (int it = 0; it < max_iter + 1 && !done; ++it) {
+            DLSA_HIP_CHECK(hipMemsetAsync(st.beta, 0, (size_t)p * sizeof(double), s));
+            const auto eval = [&](bool& nothing) {
                 int64_t D = 0;
-                rc = cox_pass_impl(X, ldx, time, event, ok, nk, p, ties, rows, beta, Hk, p, g, stats + 3, nullptr, w, &D, s);
-                if (rc) return rc;
-                if (D == 0) { st_k = DLSA_PART_EMPTY; break; }
-                rc = launch_chol_solve(Hk, p, 0, g, 0, beta, 0, p, 1, Lf, delta, 0, stats, 0, s, 0);
-                if (rc) return rc;
-                double h[4];
-                DLSA_HIP_CHECK(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, s));
-                DLSA_HIP_CHECK(hipStreamSynchronize(s));
-                ll = h[3];
-                if (!isfinite(ll)) { st_k = DLSA_PART_NAN; break; }
-                // the previous step overshot (the partial likelihood dropped): halve it
-                if (have_prev && ll < ll_prev - 1e-12 * fabs(ll_prev) && halvings < 30) {
-                    ++halvings;
-                    rc = launch_axpby(beta, prev, -1.0, p, delta, s);     // delta = beta - prev
-                    if (rc) return rc;
-                    rc = launch_axpby(prev, delta, 0.5, p, beta, s);      // beta = prev + delta / 2
-                    if (rc) return rc;
-                    continue;
-                }
-                halvings = 0;
-                if (h[2] == 1.0) { st_k = DLSA_PART_NOT_SPD; break; }
-                if (h[2] == 2.0) { st_k = DLSA_PART_NAN; break; }
-                iters = it + 1;
-                if (h[0] <= tol * std::max(1.0, h[1])) { st_k = DLSA_PART_OK; done = true; break; }     // H, g, loglik are at beta
-                if (it == max_iter) break;          // (the extra pass evaluated H at the last iterate)
-                rc = launch_advance(prev, beta, delta, p, s);
-                if (rc) return rc;
-                ll_prev = ll;
-                have_prev = true;
-            }
-        }
-        if (st_k == DLSA_PART_EMPTY) {
-            ll = 0.0;
-            DLSA_HIP_CHECK(hipMemsetAsync(Hk, 0, (size_t)p * p * sizeof(double), s));
-            DLSA_HIP_CHECK(hipMemsetAsync(ck, 0, (size_t)p * sizeof(double), s));
-            DLSA_HIP_CHECK(hipMemsetAsync(sk, 0, (size_t)p * sizeof(double), s));
-        } else {
-            DLSA_HIP_CHECK(hipMemcpyAsync(ck, beta, (size_t)p * sizeof(double), hipMemcpyDeviceToDevice, s));
-            const int rc = launch_matvec(Hk, p, beta, p, sk, s);
+                const int rce = cox_pass_impl(X, ldx, time, event, ok, nk, p, ties, rows, st.beta, Hk, p, st.g, st.stats + 3, nullptr, w, &D, s);
+                nothing = D == 0;                   // no event: nothing to fit
+                return rce;
+            };
+            rc = newton_fit_loop(NEWTON_COX, tol, max_iter + 1, eval, NewtonDevice{st, Hk, p, s}, newton_no_hook, o);
             if (rc) return rc;
         }
-        if (n_iter_host) n_iter_host[k] = iters;
-        if (status_host) status_host[k] = st_k;
-        if (loglik_host) loglik_host[k] = ll;
-        if (st_k == DLSA_PART_NOT_CONVERGED && overall == DLSA_OK) overall = DLSA_ERR_NOT_CONVERGED;
-        if (st_k == DLSA_PART_NOT_SPD && overall == DLSA_OK) overall = DLSA_ERR_NOT_SPD;
-        if (st_k == DLSA_PART_NAN && overall == DLSA_OK) overall = DLSA_ERR_NAN;
+        const int rc = newton_fit_finish(o.status, o.n_iter, o.ll, st.beta, p, Hk, coef + (size_t)k * p, Sig_invMcoef + (size_t)k * p, k,
+                                         n_iter_host, status_host, loglik_host, overall, s);
+        if (rc) return rc;
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;

@@ -2,6 +2,7 @@
 // (dlsa/models.py:131), the local block sum that feeds the one-round all-reduce (dlsa/dlsa.py:30-34)
 // and the C entry of the WLS combine (dlsa.py:48-49; the blocked Cholesky itself is chol.hip).
 #include "common.h"
+#include "host_calls.h"
 
 namespace dlsa {
 
@@ -82,10 +83,6 @@ __global__ __launch_bounds__(1024) void step_stats_kernel(const double* __restri
         stats[0] = a; stats[1] = b; stats[2] = c != 0.0 ? 2.0 : 0.0;
     }
 }
-
-int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
-                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
-                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);   // chol.hip
 
 int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s) {
     hipLaunchKernelGGL(matvec_kernel, dim3((p + 3) / 4), dim3(256), 0, s, A, lda, x, p, y);

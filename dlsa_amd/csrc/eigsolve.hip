@@ -14,6 +14,7 @@
 // (2 MB at p = 500) stay in L2.  A sweep ends with a reduction of the off-diagonal mass; 6-10 sweeps reach 1e-30 relative.
 // Latency-bound and rarely taken (only when the Cholesky of the combine fails or is numerically rank-deficient).
 #include "common.h"
+#include "host_calls.h"
 #include <algorithm>
 #include <math.h>
 #include <vector>
@@ -201,10 +202,6 @@ int sym_pinv_solve_impl(const double* S, int64_t lds, const double* v, int p, do
     if (sweeps_host) *sweeps_host = sweeps;
     return DLSA_OK;
 }
-
-int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
-                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
-                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);   // chol.hip
 
 }  // namespace dlsa
 

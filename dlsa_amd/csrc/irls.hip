@@ -21,6 +21,8 @@
 #include "common.h"
 #include "onehot_plan.h"    // the structured passes of onehot.hip
 #include "options.h"
+#include "host_calls.h"
+#include "newton_fit.h"     // newton_overshot, NEWTON_MAX_HALVINGS: the safeguard's test and limit
 #include <math.h>
 #include <algorithm>
 #include <stdlib.h>
@@ -32,59 +34,7 @@
 #include <thread>
 
 namespace dlsa {
-int gram_impl_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
-                  int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
-size_t gram_workspace_bytes_impl(int64_t n, int p, int elem_bytes);
-// irls_pass.hip: one Newton pass in one launch where the shape allows it (narrow designs: the rows staged for the MFMAs also
-// feed the logistic terms -- one read of X per fresh Hessian instead of two)
-bool irls_pass_fused_eligible(const double* X, int64_t ldx, const double* y, int64_t n, int p);
-size_t irls_pass_workspace_bytes_impl(int64_t n, int p);
-bool irls_pass_fused_icpt_eligible(const double* X, int64_t ldx, const double* y, int64_t n, int p);
-int irls_pass_icpt_impl(const double* X, int64_t ldx, const double* y, const double* beta, int64_t n, int p, double* H, int64_t ldh,
-                        double* g, double* loglik, double* w_out, void* ws, size_t ws_bytes, hipStream_t stream);
-int irls_pass_impl(const double* X, int64_t ldx, const double* y, const double* beta, int64_t n, int p, double* H, int64_t ldh,
-                   double* g, double* loglik, double* w_out, double* w_scratch, void* ws, size_t ws_bytes, hipStream_t stream,
-                   int* fused_out);
-size_t logit_workspace_bytes_impl(int64_t n, int p);
-int logit_pass_impl(const double* X, int64_t ldx, const double* y, const double* beta, int64_t n, int p,
-                    double* w_out, double* g, double* loglik, void* ws, size_t ws_bytes, hipStream_t stream, int intercept);
-bool logit_border_ok(const double* X, int64_t ldx, int p);
-int logit_pass_border_impl(const double* X, int64_t ldx, const double* y, const double* beta, int64_t n, int p,
-                           double* w_out, double* g, double* loglik, double* border, void* ws, size_t ws_bytes, hipStream_t stream);
-int xtv_impl(const double* X, int64_t ldx, const double* v, int64_t n, int p, double* g, double* vv, double* sv,
-             void* ws, size_t ws_bytes, hipStream_t s);
-// irls_small.hip: all partitions in ONE launch, a workgroup each (many small partitions)
-bool irls_small_eligible(const int64_t* rows_host, int K, int pe, double* est_ms = nullptr);
-size_t irls_small_workspace_bytes(int K);
-int irls_small_fit(const double* X, int64_t ldx, const double* y, const int64_t* first_host, const int64_t* rows_host,
-                   int64_t step, int K, int p, int intercept, double tol, int max_iter, double* coef, double* Sig_inv,
-                   double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws, size_t ws_bytes,
-                   hipStream_t s);
-int launch_chol_solve(const double* A, int64_t lda, int64_t strideA, const double* rhs, int64_t stride_rhs,
-                      const double* ref, int64_t stride_ref, int p, int nsys, double* Lws, double* xout,
-                      int64_t stride_x, double* stats, int64_t stride_stats, hipStream_t s, int reuse_factor);
-int launch_matvec(const double* A, int64_t lda, const double* x, int p, double* y, hipStream_t s);
-int launch_tri_inverse(const double* L, int p, double* Linv, hipStream_t s);
-bool chol_small_ok(int p);
-int launch_chol_small(const double* A, int64_t lda, int p, const double* rhs, const double* ref, double* Hinv, double* xout,
-                      double* stats, hipStream_t s);
-int launch_inv_apply(const double* Linv, int p, const double* rhs, const double* ref, double* xout, double* stats, hipStream_t s);
-int launch_axpby(const double* a, const double* b, double sc, int n, double* out, hipStream_t s);
-int launch_advance(double* prev, double* beta, const double* delta, int n, hipStream_t s);
-int launch_matvec_axpy(const double* A, int64_t lda, const double* x, int p, double alpha, const double* z, double beta, double* y, hipStream_t s);
-int launch_step_stats(const double* delta, const double* ref, int p, double* stats, hipStream_t s);
-// irls_wide.hip: the logit pass of a wide design that also yields the partition's own Hessian in reduced precision (bf16 products)
-bool irls_wide_eligible(const double* X, int64_t ldx, int64_t n, int p, int icpt);
-size_t irls_wide_workspace_bytes(int64_t n, int p, int icpt);
-int irls_wide_pass_impl(const double* X, int64_t ldx, const double* y, const double* beta, int64_t n, int p, int icpt, double* w_out,
-                        double* g, double* loglik, double* Happrox, int64_t ldh, void* ws, size_t ws_bytes, hipStream_t stream);
-constexpr int64_t kWideMaxRows = 4000000;  // (the pass keeps a bf16 image of the partition, 1 KiB per row at p = 500.  A single 2.5e7-row partition would be served too -- measured: 7 -> 5 full passes, 0.2437 -> 0.2398 s -- for 25 GB more workspace: not taken)
-// irls_batch.hip: the lock-step fit of all partitions of a call together
-bool irls_batched_eligible(const double* X, int64_t ldx, const double* y, const int64_t* rows_host, int K, int p, int intercept, int64_t row_step,
-                           double* est_ms = nullptr);
-int irls_batched_fit(const double* X, int64_t ldx, const double* y, const int64_t* first_host, const int64_t* rows_host, int64_t row_step, int K,
-                     int p, int intercept, double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
-                     double* loglik_host, hipStream_t stream);
+constexpr int64_t kWideMaxRows = 4000000;  // (the wide pass keeps a bf16 image of the partition, 1 KiB per row at p = 500.  A single 2.5e7-row partition would be served too -- measured: 7 -> 5 full passes, 0.2437 -> 0.2398 s -- for 25 GB more workspace: not taken)
 // which driver the calling thread's last fit took: 0 = host-driven partition chains, 1 = the one-launch kernel for small partitions,
 // 2 = lock step (dlsa_irls_last_fit_path)
 static thread_local int g_last_fit_path = 0;
@@ -652,7 +602,7 @@ static int newton_run(const IrlsData& d, int64_t n, int p, double tol, int max_i
         if (h[2] == 1.0) { *status = DLSA_PART_NOT_SPD; return DLSA_OK; }
         if (h[2] == 2.0 || !isfinite(ll)) { *status = DLSA_PART_NAN; return DLSA_OK; }
         // safeguard: the previous step overshot (log-likelihood dropped) -> halve it, refresh H
-        if (have_prev && ll < ll_prev - 1e-12 * fabs(ll_prev) && halvings < 30) {
+        if (have_prev && newton_overshot(ll, ll_prev) && halvings < NEWTON_MAX_HALVINGS) {
             ++halvings;
             ord.m = 0; qn_have_gprev = false;                            // the rejected step gives no valid pair
             approx_ok = false; have_Ha = false;                          // (whatever preconditioner produced it: exact Hessians from here)
@@ -1101,7 +1051,7 @@ __global__ void icpt_border_kernel(double* __restrict__ H, int64_t ldh, int p) {
 }
 // (border: [sum w | X'w] already known -- the logit pass that produced w left it, logit_pass_border_impl -- instead of a pass of its own)
 int gram_icpt_impl(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
-                   void* ws, size_t ws_bytes, hipStream_t s, const double* border = nullptr) {
+                   void* ws, size_t ws_bytes, hipStream_t s, const double* border) {
     int rc = gram_impl_f64(X, ldx, w, n, p, H + ldh + 1, ldh, 0, ws, ws_bytes, s);
     if (rc) return rc;
     if (n == 0) { DLSA_HIP_CHECK(hipMemsetAsync(H, 0, (size_t)(p + 1) * sizeof(double), s)); }

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "options.h"
 #include "irls_batch.h"
+#include "host_calls.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -32,19 +33,6 @@
 #include <stdlib.h>
 
 namespace dlsa {
-
-// irls_pass.hip
-int irls_pass_batched_pp(int p);
-int irls_pass_batched_gp(int p);
-int irls_pass_batched_ll_at(int p);
-bool irls_pass_batched_shape_ok(const double* X, int64_t ldx, const double* y, int p, int intercept, int64_t base_ldx);
-int irls_pass_batched_launch(const double* X, int64_t ldx, const double* y, const double* beta, int64_t beta_stride, int p, int intercept,
-                             const FusedSlab* d_slabs, int nslab, const int* d_active, double* partial, double* gpart,
-                             unsigned long long* clk, hipStream_t stream, int want_h);
-// chol.hip
-bool chol_small_ok(int p);
-int launch_chol_small_batched(int count, const double* A, int64_t lda, int64_t sA, int p, const double* rhs, const double* ref, int64_t sV,
-                              double* Hinv, int64_t sH, double* xout, double* stats, int64_t sS, const int* active, hipStream_t s);
 
 constexpr int BATCH_SLAB_ROWS = 24576;          // a partition longer than this is cut into equal slabs (whole 32-row chunks)
 

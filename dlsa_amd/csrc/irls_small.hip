@@ -20,6 +20,7 @@
 // Width: p + intercept <= 64 columns (4 tiles per side, 10 accumulator tiles per wave); the implicit intercept is the LAST
 // column inside the kernel and the FIRST one in the outputs (models.py:136-142).
 #include "common.h"
+#include "host_calls.h"
 #include "options.h"
 #include <algorithm>
 #include <atomic>

@@ -158,7 +158,7 @@ static NbLayout nb_layout(int64_t max_rows, int p, int intercept, int64_t row_st
     l.off_tst = take(8 * 16);
     l.off_w = take(8 * (size_t)n);
     l.off_mu = take(8 * (size_t)n);
-    l.off_state = take(pois_state_bytes(pe));
+    l.off_state = take(newton_state_bytes(pe));
     l.off_gram = take(gram_workspace_bytes_impl(n, p, 8));
     l.total = std::max(o, align_up(l.off_pois + pois_bytes, 256));
     return l;
@@ -186,13 +186,11 @@ static int nb_theta_launch(const double* y, const double* mu, const double* off,
 constexpr double NB_ALPHA_START_MIN = 1e-3;     // floor of the moment start
 constexpr double NB_ALPHA_POISSON = 1e-8;       // the theta iteration below this alpha: the partition is Poisson (alpha = 0)
 
-struct NbFitCtx : PoisState {                  // (stats, beta, prev, delta, g, Lf: the Newton state)
+struct NbFitCtx : NewtonState {                // (stats, beta, prev, delta, g, Lf: the Newton state)
     const double* Xk; int64_t pitch; const double* yk; const double* ok; int64_t nk;
-    int p, intercept, pe;
     double tol;
-    double* Hk;
     double* w; double* mu; double* tpart; double* tst;
-    char* ws; const NbLayout* l; hipStream_t s;
+    hipStream_t s;
 };
 
 static int nb_theta_eval(const NbFitCtx& c, double alpha, int want_lg, double* t) {
@@ -207,14 +205,6 @@ static int nb_theta_eval(const NbFitCtx& c, double alpha, int want_lg, double* t
 // where the step has stopped shrinking below 1e-8 (the rounding floor of the score).  t holds the sums at the returned alpha,
 // first_step the size of the first step (0 <=> alpha did not move), yl_first sum (y + theta) L at the alpha it came in with.
 // poisson = true: alpha fell below NB_ALPHA_POISSON.
-
-// The fit proper, from the Poisson MLE in c.beta and the start alpha: after every ACCEPTED evaluation at (beta, alpha) -- H, g, the
-// row log-likelihood, w, mu -- theta is solved for that mu (16 bytes per row and iteration), then beta takes the Newton step that
-// evaluation gave.  H is the expected information, so at alpha > 0 the beta iteration is Fisher scoring (linear convergence); one
-// theta solve per step keeps the two in lockstep instead of nesting one iteration in the other.  A step is halved (<= 30 times) while
-// the row log-likelihood at the SAME alpha drops or is not finite: the previous point's value is moved to the new alpha with
-// sum (y + theta) L of its mu.  Converged where the step of beta meets the IRLS rule and theta did not move: then H, g and t are at
-// the returned (beta, alpha).  fixed: no theta steps.
 static int nb_theta_solve(const NbFitCtx& c, double& alpha, double* t, int& theta_iters, bool& poisson, double& first_step,
                           double& yl_first) {
     double prev_step = INFINITY;
@@ -239,52 +229,6 @@ static int nb_theta_solve(const NbFitCtx& c, double& alpha, double* t, int& thet
     return DLSA_OK;
 }
 
-static int nb_joint_loop(const NbFitCtx& c, bool fixed, double& alpha, double* t, int& passes, int max_passes, int& theta_iters,
-                         bool& poisson, double& ll1, int& st) {
-    double ll_prev = -INFINITY;
-    bool have_prev = false;
-    int halvings = 0;
-    st = DLSA_PART_NOT_CONVERGED;
-    poisson = false;
-    while (passes < max_passes) {
-        int rc = nb_pass_impl(c.Xk, c.pitch, c.yk, c.ok, c.beta, alpha, c.nk, c.p, c.intercept, c.Hk, c.pe, c.g, c.stats + 3, c.w, c.mu,
-                              c.ws, *c.l, c.s);
-        if (rc) return rc;
-        ++passes;
-        rc = launch_chol_solve(c.Hk, c.pe, 0, c.g, 0, c.beta, 0, c.pe, 1, c.Lf, c.delta, 0, c.stats, 0, c.s, 0);
-        if (rc) return rc;
-        double h[4];
-        DLSA_HIP_CHECK(hipMemcpyAsync(h, c.stats, sizeof(h), hipMemcpyDeviceToHost, c.s));
-        DLSA_HIP_CHECK(hipStreamSynchronize(c.s));
-        ll1 = h[3];
-        const bool worse = !isfinite(ll1) || (have_prev && ll1 < ll_prev - 1e-12 * fabs(ll_prev));
-        if (have_prev && worse && halvings < 30) {
-            ++halvings;
-            rc = launch_axpby(c.beta, c.prev, -1.0, c.pe, c.delta, c.s);     // delta = beta - prev
-            if (rc) return rc;
-            rc = launch_axpby(c.prev, c.delta, 0.5, c.pe, c.beta, c.s);      // beta = prev + delta / 2
-            if (rc) return rc;
-            continue;
-        }
-        if (!isfinite(ll1)) { st = DLSA_PART_NAN; break; }
-        halvings = 0;
-        if (h[2] == 1.0) { st = DLSA_PART_NOT_SPD; break; }
-        if (h[2] == 2.0) { st = DLSA_PART_NAN; break; }
-        double first_step = 0.0, yl_old = 0.0;
-        if (!fixed) {
-            rc = nb_theta_solve(c, alpha, t, theta_iters, poisson, first_step, yl_old);
-            if (rc) return rc;
-            if (poisson) break;
-        }
-        if (h[0] <= c.tol * std::max(1.0, h[1]) && first_step <= 100.0 * c.tol) { st = DLSA_PART_OK; break; }
-        rc = launch_advance(c.prev, c.beta, c.delta, c.pe, c.s);
-        if (rc) return rc;
-        ll_prev = fixed ? ll1 : ll1 + (yl_old - t[NB_YL]);                   // this point's row log-likelihood at the new alpha
-        have_prev = true;
-    }
-    return DLSA_OK;
-}
-
 }  // namespace dlsa
 
 extern "C" {
@@ -305,16 +249,14 @@ int dlsa_negbin_pass_f64(const double* X, int64_t ldx, const double* y, const do
                  (long long)n, p, (long long)ldx, (long long)ldh);
     DLSA_REQUIRE(alpha > 0 && isfinite(alpha), "negbin_pass: alpha must be positive and finite (alpha = 0 is dlsa_poisson_pass_f64)");
     const NbLayout l = nb_layout(n, p, intercept, 1, 0);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
-        set_error("negbin_pass: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
+    int rc = newton_check_ws("negbin_pass", ws, ws_bytes, l.total);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
     double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
     const bool want_theta = loglik || theta_terms;
     double* mu = mu_out ? mu_out : (want_theta ? (double*)(wsc + l.off_mu) : nullptr);
-    int rc = nb_pass_impl(X, ldx, y, offset, beta, alpha, n, p, intercept, H, ldh, g, loglik, w, mu, wsc, l, s);
+    rc = nb_pass_impl(X, ldx, y, offset, beta, alpha, n, p, intercept, H, ldh, g, loglik, w, mu, wsc, l, s);
     if (rc || !want_theta) return rc;
     double* tst = (double*)(wsc + l.off_tst);
     rc = nb_theta_launch(y, mu, offset, n, alpha, loglik ? 1 : 0, (double*)(wsc + l.off_tpart), tst, s);
@@ -347,19 +289,17 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
     }
     const size_t pois_bytes = dlsa_poisson_workspace_bytes(max_rows, p, intercept, row_step);
     const NbLayout l = nb_layout(max_rows, p, intercept, row_step, pois_bytes);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
-        set_error("negbin_fit: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
+    const int rcw = newton_check_ws("negbin_fit", ws, ws_bytes, l.total);
+    if (rcw) return rcw;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
     NbFitCtx c{};
-    c.pitch = ldx * row_step; c.p = p; c.intercept = intercept; c.pe = pe; c.tol = tol;
-    // (NbFitCtx derives from PoisState so that the Newton loops keep reading c.beta, c.g, ... while the carving has one copy)
-    static_cast<PoisState&>(c) = pois_state_at(wsc + l.off_state, pe);
+    c.pitch = ldx * row_step; c.tol = tol;
+    // (NbFitCtx derives from NewtonState so that the passes keep reading c.beta, c.g, ... while the carving has one copy)
+    static_cast<NewtonState&>(c) = newton_state_at(wsc + l.off_state, pe);
     c.w = (double*)(wsc + l.off_w); c.mu = (double*)(wsc + l.off_mu);
     c.tpart = (double*)(wsc + l.off_tpart); c.tst = (double*)(wsc + l.off_tst);
-    c.ws = wsc; c.l = &l; c.s = s;
+    c.s = s;
     int overall = DLSA_OK;
     for (int k = 0; k < K; ++k) {
         const int64_t nk = part_rows_host[k];
@@ -377,7 +317,7 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
         }
         if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
         if (st_k == DLSA_PART_OK) {
-            c.Xk = X + part_first_host[k] * ldx; c.nk = nk; c.Hk = Hk;
+            c.Xk = X + part_first_host[k] * ldx; c.nk = nk;
             c.yk = y + part_first_host[k];
             c.ok = offset ? offset + part_first_host[k] : nullptr;
             if (row_step > 1) {                               // the partition's counts and offsets, gathered once
@@ -413,8 +353,30 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
                     if (rc) return rc;
                 }
                 if (!poisson) {
-                    rc = nb_joint_loop(c, fixed, alpha, t, passes, max_passes, theta_iters, poisson, ll1, st_k);
+                    // The fit proper, from the Poisson MLE in c.beta and the start alpha, is newton_fit_loop with the policy
+                    // NEWTON_NB2 and this hook: after every ACCEPTED evaluation at (beta, alpha) -- H, g, the row log-likelihood, w,
+                    // mu -- theta is solved for that mu (16 bytes per row and iteration), then beta takes the Newton step that
+                    // evaluation gave..  H is the expected information, so at alpha > 0 the beta iteration is Fisher scoring (linear
+                    // convergence); one theta solve per step keeps the two in lockstep instead of nesting one iteration in the
+                    // other..  A step is halved while the row log-likelihood at the SAME alpha drops or is not finite: the previous
+                    // point's value is moved to the new alpha with sum (y + theta) L of its mu (ll_shift)..  Converged where the step of
+                    // beta meets the IRLS rule and theta did not move (first_step): then H, g and t are at the returned (beta,
+                    // alpha)..  fixed: no theta steps.
+                    const auto eval = [&](bool&) {
+                        return nb_pass_impl(c.Xk, c.pitch, c.yk, c.ok, c.beta, alpha, nk, p, intercept, Hk, pe, c.g, c.stats + 3, c.w, c.mu, wsc, l, s);
+                    };
+                    const auto theta_hook = [&](bool& leave, double& first_step, double& ll_shift) {
+                        if (fixed) return (int)DLSA_OK;
+                        double yl_old = 0.0;
+                        const int rch = nb_theta_solve(c, alpha, t, theta_iters, poisson, first_step, yl_old);
+                        leave = poisson;                           // alpha fell to 0: the Poisson block, below
+                        ll_shift = yl_old - t[NB_YL];              // this point's row log-likelihood at the new alpha
+                        return rch;
+                    };
+                    NewtonOutcome o;
+                    rc = newton_fit_loop(NEWTON_NB2, tol, max_passes - passes, eval, NewtonDevice{c, Hk, pe, s}, theta_hook, o);
                     if (rc) return rc;
+                    passes += o.evals; ll1 = o.ll; st_k = o.status;
                 }
                 if (poisson && passes == 1) {                  // the dispersion iterate ran off to 0 before H was touched
                     alpha = 0.0;
@@ -446,7 +408,7 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
         if (alpha_host) alpha_host[k] = alpha;
         if (alpha_info_host) alpha_info_host[k] = info;
         if (pearson_host) pearson_host[k] = pearson;
-        pois_fold_status(st_k, overall);
+        newton_fold_status(st_k, overall);
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;

@@ -56,7 +56,7 @@ static OhPoisLayout oh_pois_layout(const dlsa_onehot_plan* pl, int64_t max_rows,
     l.off_o = take(row_step > 1 ? 8 * (size_t)n : 0);
     l.off_cpart = take(8 * 4 * (size_t)POIS_CONST_BLOCKS);
     l.off_cst = take(8 * 4);
-    l.off_state = take(pois_state_bytes(onehot_plan_p(pl)));
+    l.off_state = take(newton_state_bytes(onehot_plan_p(pl)));
     l.total = o;
     return l;
 }
@@ -116,10 +116,8 @@ int dlsa_onehot_poisson_pass_f64(const dlsa_onehot_plan* plan, const double* num
     const int p = onehot_plan_p(plan);
     DLSA_REQUIRE(n >= 1 && (!H || ldh >= p), "onehot_poisson_pass: bad shape n=%lld p=%d ldh=%lld", (long long)n, p, (long long)ldh);
     const OhPoisLayout l = oh_pois_layout(plan, n, 1);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
-        set_error("onehot_poisson_pass: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
+    rc = newton_check_ws("onehot_poisson_pass", ws, ws_bytes, l.total);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
     double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
@@ -147,16 +145,14 @@ int dlsa_onehot_poisson_fit_f64(const dlsa_onehot_plan* plan, const double* num,
     }
     const int p = onehot_plan_p(plan);
     const OhPoisLayout l = oh_pois_layout(plan, max_rows, row_step);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
-        set_error("onehot_poisson_fit: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
+    rc = newton_check_ws("onehot_poisson_fit", ws, ws_bytes, l.total);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
     PoisFitBufs b{};
     b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
     b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
-    b.st = pois_state_at(wsc + l.off_state, p);
+    b.st = newton_state_at(wsc + l.off_state, p);
     double* wv = (double*)(wsc + l.off_w);
     void* ws_oh = wsc + l.off_oh;
     const size_t oh_bytes = l.oh_bytes;

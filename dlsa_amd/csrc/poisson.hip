@@ -15,8 +15,9 @@
 //   3 the Gram              dlsa_gram_f64's dispatch on (X, mu) into the p x p block (gram_icpt_impl with the border).
 // The constant sum lgamma(y + 1) is a small reduction of its own, once per partition (poisson_const_kernel), which also
 // counts the rows with a negative or non-finite count or offset and sums y and e^o for the intercept's start value.
-// The Newton loop (pois_fit_core) takes the evaluation at beta as a callable and is shared with the structured one-hot fit
-// (onehot_poisson.hip) through poisson_internal.h, as are the constant-term, log-likelihood-fix and gather launchers.
+// The fit driver (pois_fit_core) takes the evaluation at beta as a callable and is shared with the structured one-hot fit
+// (onehot_poisson.hip) through poisson_internal.h, as are the constant-term, log-likelihood-fix and gather launchers; the Newton
+// iteration itself is newton_fit.h's, shared with negbin.hip and cox.hip.
 #include "common.h"
 #include "poisson_internal.h"
 #include <math.h>
@@ -142,13 +143,12 @@ static int pois_pass_impl(const double* X, int64_t ldx, const double* y, const d
                       ws + l.off_gram, l.total - l.off_gram, s);
 }
 
-// The Newton loop of the Poisson fits (dense rows here, raw one-hot rows in onehot_poisson.hip): `eval` is the only part that
-// knows the representation of the design.
+// The driver of the Poisson fits (dense rows here, raw one-hot rows in onehot_poisson.hip): `eval` is the only part that knows
+// the representation of the design; the iteration is newton_fit_loop (newton_fit.h).
 int pois_fit_core(const char* who, const double* y, const double* offset, const int64_t* part_first_host,
                   const int64_t* part_rows_host, int64_t row_step, int K, int pe, int icpt_col, double tol, int max_iter,
                   double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
                   const PoisFitBufs& b, const PoisEval& eval, hipStream_t s) {
-    double *stats = b.st.stats, *beta = b.st.beta, *prev = b.st.prev, *delta = b.st.delta, *g = b.st.g, *Lf = b.st.Lf;
     int overall = DLSA_OK;
     for (int k = 0; k < K; ++k) {
         const int64_t nk = part_rows_host[k];
@@ -184,59 +184,17 @@ int pois_fit_core(const char* who, const double* y, const double* offset, const 
         if (nk > 0 && cst[1] > 0.0) {
             // the intercept starts at log(sum y / sum e^o), the exact MLE of the intercept-only model
             const double b0 = (icpt_col >= 0 && cst[2] > 0.0 && isfinite(cst[2])) ? log(cst[1] / cst[2]) : 0.0;
-            hipLaunchKernelGGL(poisson_start_kernel, dim3((pe + 255) / 256), dim3(256), 0, s, beta, pe, icpt_col, b0);
+            hipLaunchKernelGGL(poisson_start_kernel, dim3((pe + 255) / 256), dim3(256), 0, s, b.st.beta, pe, icpt_col, b0);
             DLSA_HIP_CHECK(hipGetLastError());
-            double ll_prev = -INFINITY;
-            bool have_prev = false;
-            int halvings = 0;
-            st_k = DLSA_PART_NOT_CONVERGED;
-            for (int it = 0; it < max_iter + 1; ++it) {
-                int rc = eval(k, yk, ok, nk, beta, Hk, g, stats + 3);
-                if (rc) return rc;
-                rc = launch_chol_solve(Hk, pe, 0, g, 0, beta, 0, pe, 1, Lf, delta, 0, stats, 0, s, 0);
-                if (rc) return rc;
-                double h[4];
-                DLSA_HIP_CHECK(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, s));
-                DLSA_HIP_CHECK(hipStreamSynchronize(s));
-                ll = h[3];
-                // the previous step overshot (the likelihood dropped, or mu overflowed): halve it
-                const bool worse = !isfinite(ll) || (have_prev && ll < ll_prev - 1e-12 * fabs(ll_prev));
-                if (have_prev && worse && halvings < 30) {
-                    ++halvings;
-                    rc = launch_axpby(beta, prev, -1.0, pe, delta, s);     // delta = beta - prev
-                    if (rc) return rc;
-                    rc = launch_axpby(prev, delta, 0.5, pe, beta, s);      // beta = prev + delta / 2
-                    if (rc) return rc;
-                    continue;
-                }
-                if (!isfinite(ll)) { st_k = DLSA_PART_NAN; break; }
-                halvings = 0;
-                if (h[2] == 1.0) { st_k = DLSA_PART_NOT_SPD; break; }
-                if (h[2] == 2.0) { st_k = DLSA_PART_NAN; break; }
-                iters = it + 1;
-                if (h[0] <= tol * std::max(1.0, h[1])) { st_k = DLSA_PART_OK; break; }     // H, g, loglik are at beta
-                if (it == max_iter) break;          // (the extra pass evaluated H at the last iterate)
-                rc = launch_advance(prev, beta, delta, pe, s);
-                if (rc) return rc;
-                ll_prev = ll;
-                have_prev = true;
-            }
+            const NewtonDevice dev{b.st, Hk, pe, s};
+            NewtonOutcome o;
+            const int rcl = newton_fit_loop(NEWTON_POISSON, tol, max_iter + 1,
+                                            [&](bool&) { return eval(k, yk, ok, nk, b.st.beta, Hk, b.st.g, b.st.stats + 3); }, dev, newton_no_hook, o);
+            if (rcl) return rcl;
+            st_k = o.status; iters = o.n_iter; ll = o.ll;
         }
-        if (st_k == DLSA_PART_EMPTY) {
-            ll = 0.0;
-            DLSA_HIP_CHECK(hipMemsetAsync(Hk, 0, (size_t)pe * pe * sizeof(double), s));
-            DLSA_HIP_CHECK(hipMemsetAsync(ck, 0, (size_t)pe * sizeof(double), s));
-            DLSA_HIP_CHECK(hipMemsetAsync(sk, 0, (size_t)pe * sizeof(double), s));
-        } else {
-            ll -= cst[0];
-            DLSA_HIP_CHECK(hipMemcpyAsync(ck, beta, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
-            const int rc = launch_matvec(Hk, pe, beta, pe, sk, s);
-            if (rc) return rc;
-        }
-        if (n_iter_host) n_iter_host[k] = iters;
-        if (status_host) status_host[k] = st_k;
-        if (loglik_host) loglik_host[k] = ll;
-        pois_fold_status(st_k, overall);
+        const int rcf = newton_fit_finish(st_k, iters, ll - cst[0], b.st.beta, pe, Hk, ck, sk, k, n_iter_host, status_host, loglik_host, overall, s);
+        if (rcf) return rcf;
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;
@@ -248,7 +206,7 @@ extern "C" {
 
 size_t dlsa_poisson_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step) {
     if (p <= 0 || p + (intercept ? 1 : 0) > 2048 || max_rows < 0 || row_step < 1) return 0;
-    return dlsa::align_up(dlsa::pois_layout(max_rows, p, row_step).total, 256) + dlsa::pois_state_bytes(p + (intercept ? 1 : 0));
+    return dlsa::align_up(dlsa::pois_layout(max_rows, p, row_step).total, 256) + dlsa::newton_state_bytes(p + (intercept ? 1 : 0));
 }
 
 int dlsa_poisson_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, int64_t n, int p,
@@ -260,14 +218,12 @@ int dlsa_poisson_pass_f64(const double* X, int64_t ldx, const double* y, const d
     DLSA_REQUIRE(n >= 1 && p > 0 && pe <= 2048 && ldx >= p && (!H || ldh >= pe), "poisson_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
                  (long long)n, p, (long long)ldx, (long long)ldh);
     const PoisLayout l = pois_layout(n, p, 1);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
-        set_error("poisson_pass: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
+    int rc = newton_check_ws("poisson_pass", ws, ws_bytes, l.total);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
     double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
-    int rc = pois_pass_impl(X, ldx, y, offset, beta, n, p, intercept, H, ldh, g, loglik, w, wsc, l, s);
+    rc = pois_pass_impl(X, ldx, y, offset, beta, n, p, intercept, H, ldh, g, loglik, w, wsc, l, s);
     if (rc || !loglik) return rc;
     rc = pois_const(y, offset, n, (double*)(wsc + l.off_cpart), (double*)(wsc + l.off_cst), s);
     if (rc) return rc;
@@ -291,16 +247,14 @@ int dlsa_poisson_fit_f64(const double* X, int64_t ldx, const double* y, const do
     }
     const PoisLayout l = pois_layout(max_rows, p, row_step);
     const size_t need = dlsa_poisson_workspace_bytes(max_rows, p, intercept, row_step);
-    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255)) {
-        set_error("poisson_fit: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes);
-        return DLSA_ERR_WORKSPACE;
-    }
+    const int rcw = newton_check_ws("poisson_fit", ws, ws_bytes, need);
+    if (rcw) return rcw;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
     PoisFitBufs b{};
     b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
     b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
-    b.st = pois_state_at(wsc + align_up(l.total, 256), pe);
+    b.st = newton_state_at(wsc + align_up(l.total, 256), pe);
     double* wv = (double*)(wsc + l.off_w);
     const int64_t pitch = ldx * row_step;                     // rows first, first + step, ...: a strided view, no copy of X
     const PoisEval eval = [=](int k, const double* yk, const double* ok, int64_t nk, const double* beta, double* Hk, double* g,

@@ -561,6 +561,22 @@ int dlsa_newton_solve_probe_f64(int route, const double* S, int64_t lds, int p, 
                                 const double* v2, const double* ref, int64_t sv, double* x, double* M, int64_t sm,
                                 double* stats, int64_t st, const int* active, void* ws, size_t ws_bytes, void* stream);
 
+/* test hook: the safeguarded Newton loop of the Poisson, NB2 and Cox fits (the loop the fits run, with callables that read a
+ * script instead of launching anything; no HIP call, no device).  policy: which family's rules (the table).
+ * budget: evaluations permitted (the fits pass max_iter + 1).  readback: n_script x 4 host doubles, what evaluation e reads back
+ * after its solve: [|delta|_inf, |beta|_inf, factor flag (0 ok, 1 not SPD, 2 NaN), loglik].  nothing (Cox only, nullable):
+ * nothing[e] != 0: evaluation e finds nothing to fit.  first_step, ll_shift, fell (NB2 only; all three or none = alpha fixed): what
+ * the dispersion solve after an ACCEPTED evaluation e reports -- the size of its first step, the shift of the likelihood to the
+ * new alpha, and fell[e] != 0: alpha fell to the Poisson limit.  Outputs: actions[e], e < budget, what followed evaluation e
+ * (DLSA_NEWTON_*; NOT_REACHED beyond the last one), the partition status, n_iter as the family's fit reports it (NB2: all
+ * evaluations; else those up to and including the last accepted one) and whether beta was advanced after the last evaluation.
+ * DLSA_ERR_INVALID when the loop asks for more than n_script evaluations. */
+enum { DLSA_NEWTON_POLICY_POISSON = 0, DLSA_NEWTON_POLICY_NB2 = 1, DLSA_NEWTON_POLICY_COX = 2 };
+enum { DLSA_NEWTON_NOT_REACHED = 0, DLSA_NEWTON_HALVE = 1, DLSA_NEWTON_ADVANCE = 2, DLSA_NEWTON_STOP = 3 };
+int dlsa_newton_replay(int policy, double tol, int budget, int n_script, const double* readback, const int* nothing,
+                       const double* first_step, const double* ll_shift, const int* fell, int* actions, int* status,
+                       int* n_iter, int* advanced_last);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import cox_reference as cr
+import newton_reference as nw
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -91,10 +92,10 @@ def test_pass_edge_cases(eng, case):
     _check_pass(eng, X, t, ev, beta)
 
 
-def _fit(eng, X, t, ev, offs):
+def _fit(eng, X, t, ev, offs, **kw):
     Xd, td, ed = _dev(X, t, ev)
     order = np.concatenate([offs[k] + np.argsort(-t[offs[k]:offs[k + 1]], kind="stable") for k in range(len(offs) - 1)])
-    return eng.cox_fit(Xd, td, ed, torch.from_numpy(order.astype(np.int64)).cuda(), offs)
+    return eng.cox_fit(Xd, td, ed, torch.from_numpy(order.astype(np.int64)).cuda(), offs, **kw)
 
 
 @pytest.mark.parametrize("p,ties", [(3, None), (20, 20), (100, None)])
@@ -111,6 +112,29 @@ def test_fit_matches_reference(eng, p, ties):
         assert rel(r["Sig_inv"][k].cpu().numpy(), H) <= 1e-10
         assert rel(r["Sig_invMcoef"][k].cpu().numpy(), H @ b) <= 1e-10
         assert abs(r["loglik"][k] - ll) <= 1e-10 * abs(ll)
+
+
+# Only the host loop is under test: one partition of 600 rows, p = 3.  The generator's times with the first column's effect
+# sharpened from 1 to 8: the undamped reference then needs 6 evaluations from beta = 0, so max_iter + 1 <= 4 never suffices.
+# (No halving case here: no Cox case of this suite overshoots, and none was found at this size; the safeguard's Cox rules are
+# checked on scripted sequences in test_newton_fit_cpu.py.)
+@pytest.mark.parametrize("max_iter", [1, 2, 3])
+def test_budget_stops_at_the_evaluated_iterate(eng, max_iter):
+    n, p = 600, 3
+    X, t, ev = _data(70, n, p)
+    t = t * np.exp(-7.0 * X[:, 0])
+    evals, bs, lls = nw.undamped(lambda b: cr.breslow_cumsum(X, t, ev, b), np.zeros(p), 1e-13)
+    assert evals is not None and evals > max_iter + 1 and nw.monotone(lls[:max_iter + 1])       # no halving in the budget
+    r = _fit(eng, X, t, ev, [0, n], max_iter=max_iter)
+    assert r["status"] == [1] and r["rc"] == 5
+    assert r["n_iter"] == [max_iter + 1]
+    # max_iter steps were taken; the last evaluation's step was not: coef is where H, g and loglik were evaluated
+    coef = r["coef"][0].cpu().numpy()
+    assert rel(coef, bs[max_iter]) <= 1e-10
+    assert abs(r["loglik"][0] - lls[max_iter]) <= 1e-10 * abs(lls[max_iter])
+    H, _, _, _ = _pass(eng, X, t, ev, coef)
+    assert rel(r["Sig_inv"][0].cpu().numpy(), H) <= 1e-12
+    assert rel(r["Sig_invMcoef"][0].cpu().numpy(), H @ coef) <= 1e-12
 
 
 def test_fit_empty_and_all_censored_partitions(eng):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import negbin_reference as nr
+import newton_reference as nw
 import poisson_reference as pr
 
 pytestmark = pytest.mark.gpu
@@ -275,6 +276,59 @@ def test_fixed_alpha(eng):
         dlsa_amd.fit_negbin_partitions(*_dev(X, y), alpha=0.0)
     with pytest.raises(ValueError):
         _fit(eng, X, y, o, [0, n], True, alpha=-1.0)
+
+
+def _poisson_mle_at_the_start(seed, n, p):
+    """rows whose Poisson MLE is the Poisson fit's own start (the intercept at log(sum y / sum e^o), slopes 0): y = mu + r with
+    r orthogonal to [1 | X], heteroscedastic, scaled so that y > 0.  The Poisson start then converges at its first evaluation and
+    every further row pass of a fixed-alpha NB2 fit belongs to the NB2 loop, whose score differs: it weighs r by 1 / (1 + alpha mu)."""
+    rng = np.random.default_rng(seed)
+    X = rng.uniform(-0.5, 0.5, (n, p))
+    o = np.log(rng.uniform(0.5, 2.0, n))
+    D = np.column_stack([np.ones(n), X])
+    mu = 3.0 * np.exp(0.3 + o)
+    z = rng.standard_normal(n) * mu
+    r = z - D @ np.linalg.lstsq(D, z, rcond=None)[0]
+    r *= 0.9 * np.min(mu / np.abs(r))
+    return X, mu + r, o
+
+
+# Only the host loop is under test: one partition of 600 rows, p = 3, intercept and offset on, alpha fixed.
+@pytest.mark.parametrize("max_iter", [1, 2, 3])
+def test_budget_counts_the_poisson_start_and_advances_after_the_last_pass(eng, max_iter):
+    n, p, alpha = 600, 3, 0.5
+    X, y, o = _poisson_mle_at_the_start(9, n, p)
+    Xd, yd, od = _dev(X, y, o)
+    rp = eng.poisson_fit_ex(Xd, yd, [0], [n], offset=od, fit_intercept=True, max_iter=max_iter)
+    assert rp["status"] == [0]
+    bp = rp["coef"][0].cpu().numpy()
+    # Fisher scoring at the fixed alpha from the Poisson MLE, undamped: 7 evaluations, so max_iter + 1 <= 4 never suffices
+    evals, bs, lls = nw.undamped(lambda b: nr.terms(X, y, b, alpha, o, True)[:3], bp, 1e-13)
+    assert evals is not None and evals > max_iter + 1 and nw.monotone(lls[:max_iter + 1])       # no halving in the budget
+    r = _fit(eng, X, y, o, [0, n], True, alpha=alpha, max_iter=max_iter)
+    assert r["status"] == [1] and r["rc"] == 5
+    # the Poisson start's passes, the pass for mu at the Poisson MLE, and max_iter + 1 evaluations of the NB2 loop
+    assert r["n_iter"] == [rp["n_iter"][0] + max_iter + 2]
+    # the NB2 loop advances after its last evaluation: coef is iterate max_iter + 1, one step beyond where Sig_inv was evaluated
+    assert rel(r["coef"][0].cpu().numpy(), bs[max_iter + 1]) <= 1e-10
+    assert rel(r["Sig_inv"][0].cpu().numpy(), nr.terms(X, y, bs[max_iter], alpha, o, True)[2]) <= 1e-10
+
+
+def test_far_start_is_halved(eng):
+    """the far start of the Poisson suite through the fixed-alpha fit: the undamped iteration from the same start (beta = 0, no
+    intercept) DIVERGES -- the first full step of the Poisson start overflows mu, its second evaluation is -inf -- so the fit
+    gets past it only by halving.  (alpha = 1e-4: at a larger one the scoring without an intercept needs more than max_iter steps.)"""
+    rng = np.random.default_rng(62)
+    X = rng.uniform(-0.5, 0.5, (20_000, 3))
+    y = rng.poisson(np.exp(5.0 + X @ np.array([4.0, -3.0, 2.0]))).astype(np.float64)
+    evals, _, lls = nw.undamped(lambda b: pr.terms(X, y, b, None, False)[:3], np.zeros(3), 1e-13)
+    assert evals is None and len(lls) == 2 and lls[1] == -math.inf
+    r = _fit(eng, X, y, None, [0, 20_000], False, alpha=1e-4)
+    print("far start, alpha 1e-4: %d row passes, the undamped iteration diverged at its second" % r["n_iter"][0])
+    assert r["status"] == [0] and r["rc"] == 0
+    assert r["n_iter"][0] > len(lls)
+    b = nr.fit(X, y, None, False, alpha=1e-4)[0]
+    assert rel(r["coef"][0].cpu().numpy(), b) <= 1e-10
 
 
 def test_strided_partitions_equal_contiguous_copies(eng):

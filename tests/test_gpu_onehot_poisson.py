@@ -234,6 +234,9 @@ def test_structured_equals_dense_and_strided_equals_contiguous(api, orc):
         print("structured vs dense", f, "%.2e" % err)
         assert err <= TOL_FIT
     assert rel(a.loglik, d.loglik) <= TOL_FIT
+    # (n_iter is not compared here: structured=False fits the built matrix, whose constant column is a column like any other, from
+    #  beta = 0, while the structured fit starts the plan's constant column at log(sum y / sum e^o) -- [7, 7, 7, 7, 8] against
+    #  [6, 6, 7, 7, 7] evaluations; test_structured_and_dense_fit_take_the_same_evaluations compares the two from one start)
     perm = np.concatenate([np.arange(k, n, K) for k in range(K)])
     offs = [0] + list(np.cumsum([len(range(k, n, K)) for k in range(K)]))
     c = api.fit_poisson_design(dev(num[perm]), dev(codes[perm]), dev(y[perm]), spec, part_offsets=offs, offset=dev(np.log(e[perm])))
@@ -246,6 +249,26 @@ def test_structured_equals_dense_and_strided_equals_contiguous(api, orc):
         api.fit_poisson_design(dn, dc, dy, spec, offset=torch.log(de), exposure=de)
     with pytest.raises(ValueError):
         api.fit_poisson_design(dn, dc, -dy - 1.0, spec)
+
+
+@pytest.mark.parametrize("max_iter", [100, 2])
+def test_structured_and_dense_fit_take_the_same_evaluations(api, orc, max_iter):
+    """one Newton loop behind both fits: a small plan whose constant column is column 0, against the dense fit of the built matrix's
+    other columns with the implicit intercept -- the same model, columns in the same order and the same start (the intercept at
+    log(sum y / sum e^o), zeros elsewhere), so the same evaluations, the same status and the same log-likelihood"""
+    from dlsa_amd import engine
+    n, q, nlevels = 600, 2, (5, 3)
+    p, num, codes, desc, nl, level_col, X, y, e = _fit_case(orc, n, q, nlevels, 611)
+    assert desc[0][0] == 0 and np.all(X[:, 0] == 1.0)                 # column 0 is the plan's constant column
+    _assert_events(X, y, [slice(0, n)])
+    o = np.log(e)
+    plan = _plan(api, p, desc, nl, level_col)
+    a = engine.onehot_poisson_fit_ex(plan, dev(num), dev(codes), dev(y), [0], [n], offset=dev(o), max_iter=max_iter)
+    d = engine.poisson_fit_ex(dev(X[:, 1:]), dev(y), [0], [n], offset=dev(o), fit_intercept=True, max_iter=max_iter)
+    print("structured / dense: n_iter", a["n_iter"], d["n_iter"], "status", a["status"], d["status"], "loglik", a["loglik"], d["loglik"])
+    assert a["n_iter"] == d["n_iter"] and a["status"] == d["status"] == [0 if max_iter == 100 else 1] and a["rc"] == d["rc"]
+    assert rel(a["loglik"], d["loglik"]) <= TOL_FIT
+    assert rel(a["coef"][0].cpu().numpy(), d["coef"][0].cpu().numpy()) <= TOL_FIT
 
 
 def test_fit_empty_and_all_zero_partitions(api, orc):

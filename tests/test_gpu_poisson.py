@@ -7,6 +7,7 @@ import warnings
 import numpy as np
 import pytest
 
+import newton_reference as nw
 import poisson_reference as pr
 
 pytestmark = pytest.mark.gpu
@@ -207,15 +208,55 @@ def test_negative_or_non_finite_counts_are_refused(eng):
     assert math.isnan(float(ll.item()))
 
 
-def test_far_start_with_large_counts_converges(eng):
+def _far_start():
     rng = np.random.default_rng(62)
     X = rng.uniform(-0.5, 0.5, (20_000, 3))
     y = rng.poisson(np.exp(5.0 + X @ np.array([4.0, -3.0, 2.0]))).astype(np.float64)
+    return X, y
+
+
+def test_far_start_with_large_counts_converges(eng):
+    X, y = _far_start()
     # no intercept: beta = 0 is far from the MLE (the counts ask for eta ~ 5), the first full steps overshoot
     r = _fit(eng, X, y, None, [0, 20_000], False)
     assert r["status"] == [0]
     b, H, ll = pr.fit(X, y, None, False)
     assert rel(r["coef"][0].cpu().numpy(), b) <= 1e-10 and rel(r["Sig_inv"][0].cpu().numpy(), H) <= 1e-10
+
+
+def test_far_start_is_halved(eng):
+    """the host loop's safeguard: the undamped iteration from the same start DIVERGES (its first full step overflows mu: the second
+    evaluation is -inf), so every evaluation the fit makes beyond those two is the halvings' doing"""
+    X, y = _far_start()
+    evals, _, lls = nw.undamped(lambda b: pr.terms(X, y, b, None, False)[:3], np.zeros(3), 1e-13)
+    assert evals is None and len(lls) == 2 and lls[1] == -math.inf
+    r = _fit(eng, X, y, None, [0, 20_000], False)
+    print("far start: %d evaluations, the undamped iteration diverged at its second" % r["n_iter"][0])
+    assert r["status"] == [0] and r["rc"] == 0
+    assert r["n_iter"][0] > len(lls)
+
+
+# Only the host loop is under test: one partition of 600 rows, intercept and offset on; p = 64 (the row pass's widest register
+# tier) once.  The undamped reference needs 5 evaluations at p = 3 and 6 at p = 64, so max_iter + 1 <= 4 never suffices.
+@pytest.mark.parametrize("p,max_iter", [(3, 1), (3, 2), (3, 3), (64, 2)])
+def test_budget_stops_at_the_evaluated_iterate(eng, p, max_iter):
+    n = 600
+    X, y, o = _data(300 + p, n, p, True, True)
+    start = np.zeros(p + 1)
+    start[0] = np.log(y.sum() / np.exp(o).sum())
+    evals, bs, lls = nw.undamped(lambda b: pr.terms(X, y, b, o, True)[:3], start, 1e-13)
+    assert evals is not None and evals > max_iter + 1 and nw.monotone(lls[:max_iter + 1])       # no halving in the budget
+    r = _fit(eng, X, y, o, [0, n], True, max_iter=max_iter)
+    assert r["status"] == [1] and r["rc"] == 5
+    assert r["n_iter"] == [max_iter + 1]
+    # max_iter steps were taken; the last evaluation's step was not: coef is where H, g and loglik were evaluated
+    coef = r["coef"][0]
+    assert rel(coef.cpu().numpy(), bs[max_iter]) <= 1e-10
+    assert abs(r["loglik"][0] - lls[max_iter]) <= 1e-10 * abs(lls[max_iter])
+    Xd, yd, od = _dev(X, y, o)
+    H, _, _, _ = eng.poisson_pass(Xd, yd, coef, offset=od, fit_intercept=True)
+    assert rel(r["Sig_inv"][0].cpu().numpy(), H.cpu().numpy()) <= 1e-12
+    assert rel(r["Sig_invMcoef"][0].cpu().numpy(), H.cpu().numpy() @ coef.cpu().numpy()) <= 1e-12
 
 
 def test_fit_is_bit_reproducible(eng):
