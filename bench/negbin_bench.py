@@ -6,6 +6,14 @@
   eval    a Newton evaluation (pass + H + the Cholesky solve) next to the Poisson evaluation, alternating;
   fit     a whole fit with an intercept and offsets (one partition) next to the Poisson fit of the same rows and to the NB fit at
           the fixed alpha-hat: times, row passes, and the share of the fit the theta iterations take at most (1 - fixed / estimated).
+With --structured (a leg of its own; the plain run stays as it is) the structured one-hot path (csrc/onehot_negbin.hip) on
+bench/surrogates.airline_shaped rows (p = 260) with NB2 counts (alpha = 0.5, exposure ~ U(0.5, 2)), every pair alternating in one
+process, medians of five:
+  oh_pass   the structured NB pass next to the structured Poisson pass on the same rows (under rocprofv3 --kernel-trace --stats:
+            oh_row_kernel<OhNbRow<true>> against oh_row_kernel<OhPoisRow<true>>);
+  oh_newton a structured Newton evaluation (pass + H) next to the structured Poisson evaluation;
+  oh_fit    the structured fit of 1e6-row i % K partitions next to the dense NB2 fit of the same partitions on the built matrix
+            (build time reported separately; condition: structured <= dense + build), with the peak device memory of both.
 Without --case every case runs in a child process of its own under its own time limit, one after another; the first failure
 stops the run.  Run one case under rocprofv3 --kernel-trace --stats for the per-kernel split."""
 import argparse
@@ -130,7 +138,111 @@ def fit_case(n, p, reps):
             "theta_share_upper_bound": round(max(0.0, 1.0 - t_fx / t_nb), 3), "status_ok": nb.status == [0] and po.status == [0]}
 
 
-CASES = {"pass": pass_case, "theta": theta_case, "eval": eval_case, "fit": fit_case}
+def airline_negbin(n, seed=7):
+    """airline_shaped rows with counts y ~ Poisson(exposure * exp(eta) * G) from its beta, G ~ Gamma(2, 1/2) as in data():
+    NB2 with alpha = 0.5, exposure ~ U(0.5, 2)"""
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import surrogates
+    d = surrogates.airline_shaped(n, seed=seed, dense=False)
+    num, codes, beta = d["num"], d["codes"], d["beta"]
+    q = num.shape[1]
+    g = torch.Generator(device="cuda").manual_seed(9)
+    o = torch.log(torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 1.5 + 0.5)
+    eta = beta[0] + ((num - 1.5) / 3.0) @ beta[1:1 + q]
+    pos = 1 + q
+    for fi, L in enumerate(d["levels"]):
+        tab = torch.cat([torch.zeros(1, dtype=torch.float64, device="cuda"), beta[pos:pos + L - 1]])
+        eta = eta + tab[codes[:, fi].long()]
+        pos += L - 1
+    u = torch.rand((2, n), dtype=torch.float64, device="cuda", generator=g).clamp_min_(1e-300)
+    mix = -ALPHA * (torch.log(u[0]) + torch.log(u[1]))
+    d["counts"] = torch.poisson(torch.exp(eta + o) * mix, generator=g)
+    d["offset"] = o
+    del d["y"]
+    return d
+
+
+def oh_pass_case(n, p, reps):
+    from dlsa_amd import engine
+    d = airline_negbin(n)
+    plan, num, codes, y, o = d["plan"], d["num"], d["codes"], d["counts"], d["offset"]
+    b = d["beta"] * 0.5
+    q, f = num.shape[1], codes.shape[1]
+    # (the NB entry's full log-likelihood costs a theta evaluation on top of the row pass; the kernel pair is read off the trace)
+    t_nb, t_po = alternating(lambda: engine.onehot_negbin_pass(plan, num, codes, y, b, ALPHA, offset=o, want_H=False, want_w=True),
+                             lambda: engine.onehot_poisson_pass(plan, num, codes, y, b, offset=o, want_H=False, want_w=True), reps * 4)
+    bn, bp = 8 * q + 4 * f + 32, 8 * q + 4 * f + 24
+    return {"case": "oh_pass", "n": n, "p": d["p"], "negbin_ms": round(t_nb, 4), "poisson_ms": round(t_po, 4),
+            "ratio": round(t_nb / t_po, 3), "bytes_ratio": round(bn / bp, 3),
+            "note": "entries, each with its beta-free reduction; the kernel pair: rocprofv3 --kernel-trace --stats"}
+
+
+def oh_newton_case(n, p, reps):
+    from dlsa_amd import engine
+    d = airline_negbin(n)
+    plan, num, codes, y, o = d["plan"], d["num"], d["codes"], d["counts"], d["offset"]
+    b = d["beta"] * 0.5
+    t_nb, t_po = alternating(lambda: engine.onehot_negbin_pass(plan, num, codes, y, b, ALPHA, offset=o),
+                             lambda: engine.onehot_poisson_pass(plan, num, codes, y, b, offset=o), reps * 2)
+    return {"case": "oh_newton", "n": n, "p": d["p"], "negbin_eval_ms": round(t_nb, 4), "poisson_eval_ms": round(t_po, 4),
+            "ratio": round(t_nb / t_po, 3)}
+
+
+def oh_fit_case(n, p, reps):
+    import torch
+    from dlsa_amd import engine
+    K = max(1, n // 1_000_000)
+    d = airline_negbin(n)
+    plan, num, codes, y, o = d["plan"], d["num"], d["codes"], d["counts"], d["offset"]
+    first, rows = list(range(K)), [len(range(k, n, K)) for k in range(K)]
+    raw = num.numel() * 8 + codes.numel() * 4 + y.numel() * 8 + o.numel() * 8
+
+    def fresh():
+        torch.cuda.synchronize()
+        engine.release_workspace()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            r = fn()
+        torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3 / reps
+    structured = lambda: engine.onehot_negbin_fit_ex(plan, num, codes, y, first, rows, row_step=K, offset=o)
+    fresh()
+    rs = structured()
+    torch.cuda.synchronize()
+    peak_s = torch.cuda.max_memory_allocated()
+    fresh()
+    t0 = time.perf_counter()
+    X, _ = engine.design(num, codes, *d["spec"])
+    torch.cuda.synchronize()
+    t_build = (time.perf_counter() - t0) * 1e3
+    dense = lambda: engine.negbin_fit_ex(X, y, first, rows, row_step=K, offset=o)
+    rd = dense()
+    torch.cuda.synchronize()
+    peak_d = torch.cuda.max_memory_allocated()
+    ts, td = [], []
+    for _ in range(5):                       # the pair in turns, in this process: medians of five
+        ts.append(wall(structured)[1])
+        td.append(wall(dense)[1])
+    rs, rd = structured(), dense()
+    t_s, t_d = sorted(ts)[2], sorted(td)[2]
+    gap = float((rs["coef"] - rd["coef"]).abs().max() / rd["coef"].abs().max())
+    return {"case": "oh_fit", "n": n, "p": d["p"], "partitions": K, "structured_fit_ms": round(t_s, 2), "dense_fit_ms": round(t_d, 2),
+            "dense_build_ms": round(t_build, 2), "ratio_vs_dense_plus_build": round(t_s / (t_d + t_build), 3),
+            "ratio_vs_dense_fit": round(t_s / t_d, 3), "not_slower": bool(t_s <= t_d + t_build),
+            "iters_structured": rs["n_iter"][:4], "iters_dense": rd["n_iter"][:4], "alpha_hat": rs["alpha"][:4],
+            "status_ok": all(s == 0 for s in rs["status"]) and all(s == 0 for s in rd["status"]), "coef_rel_gap": gap,
+            "raw_GB": round(raw / 1e9, 3), "structured_peak_GB": round(peak_s / 1e9, 3), "dense_peak_GB": round(peak_d / 1e9, 3),
+            "structured_peak_below_raw_plus_1GB": bool(peak_s < raw + 1e9)}
+
+
+CASES = {"pass": pass_case, "theta": theta_case, "eval": eval_case, "fit": fit_case, "oh_pass": oh_pass_case, "oh_newton": oh_newton_case,
+         "oh_fit": oh_fit_case}
 
 
 def main():
@@ -138,16 +250,19 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--small", action="store_true", help="1e6 x 100 only (a quick check)")
     ap.add_argument("--case", choices=sorted(CASES), help="run this case in this process")
+    ap.add_argument("--structured", action="store_true", help="the structured one-hot leg only (airline-shaped rows, p = 260)")
     ap.add_argument("--n", type=int, default=10_000_000)
     ap.add_argument("--p", type=int, default=100)
     ap.add_argument("--limit", type=int, default=240, help="time limit of each child process, seconds")
     a = ap.parse_args()
     if a.case:
-        reps = max(1, a.reps // 2) if a.case == "fit" else a.reps
+        reps = max(1, a.reps // 2) if a.case in ("fit", "oh_fit") else a.reps
         print(json.dumps(CASES[a.case](a.n, a.p, reps)), flush=True)
         return 0
     shapes = [(1_000_000, 100)] if a.small else [(10_000_000, 100), (2_000_000, 500)]
     jobs = [(c, n, p) for n, p in shapes for c in ("pass", "theta", "eval")] + [("fit", shapes[0][0], shapes[0][1])]
+    if a.structured:
+        jobs = [("oh_pass", 1_000_000, 260), ("oh_newton", 1_000_000, 260), ("oh_fit", 1_000_000 if a.small else 4_000_000, 260)]
     for c, n, p in jobs:             # a fresh child per case, each under its own time limit; nothing more after a failure
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--case", c, "--n", str(n), "--p", str(p),
                "--reps", str(a.reps)]

@@ -16,7 +16,7 @@
 //
 // Launches per evaluation at (beta, alpha) (every partial combines in a fixed order: no float atomics):
 //   1 count_pass_kernel     (count_pass.h, shared with poisson.hip: rowdot.h, RB rows per wave, non-temporal 16-byte loads, any row
-//                           pitch) with the terms of NbRow: w = mu q (-> the Gram's weights), mu (-> the theta step), per-block partials
+//                           pitch) with the terms of NbRow (negbin_internal.h): w = mu q (-> the Gram's weights), mu (-> the theta step), per-block partials
 //                           of g, sum (y - mu) q, sum y eta - (y + theta) L and, with the intercept and H wanted, X'w and sum w;
 //   2 logit_finish_launch   the fixed-order column sums (shared with logit.hip / poisson.hip);
 //   3 the Gram              dlsa_gram_f64's dispatch on (X, w).
@@ -27,6 +27,7 @@
 // every eta <= 709.78 and every alpha.  Above that mu = +inf and loglik = -inf: the driver's failed step, as in the Poisson fit.
 #include "common.h"
 #include "poisson_internal.h"
+#include "negbin_internal.h"   // NbRow, the NB_* sums, nb_fit_core (shared with onehot_negbin.hip)
 #include <math.h>
 #include <algorithm>
 
@@ -36,30 +37,6 @@ namespace dlsa {
 #include "poisson_exp.h"     // exp_full
 #include "negbin_special.h"  // nb_gamma_parts, nb_diffs
 #include "count_pass.h"      // count_pass_kernel, count_pass, CountScratch
-
-constexpr int NB_THETA_BLOCKS = 2048;
-// theta-step sums: c (without lgamma(y+1)), s, i, Pearson, sum (y-mu)^2 - y, bad rows, sum (y-mu)^2 - mu, sum mu^2, sum lgamma(y+1),
-// sum (y + theta) L (the alpha-dependent part of the row log-likelihood: lets the driver move it from one alpha to the next)
-constexpr int NB_NQ = 10;
-enum { NB_C = 0, NB_S = 1, NB_I = 2, NB_PEARSON = 3, NB_D0 = 4, NB_BAD = 5, NB_M1 = 6, NB_M2 = 7, NB_LG = 8, NB_YL = 9 };
-
-// the NB2 row at theta = 1 / alpha: weight mu q, residual (y - mu) q, term y eta - (y + theta) L
-struct NbRow {
-    static constexpr bool STORES_MU = true;
-    double alpha;          // >= 0 (0: the Poisson limit, used by the fit at its start)
-    double theta;          // 1 / alpha
-    double log_alpha;
-    __device__ __forceinline__ void terms(double yv, double eta, double mu, double& wgt, double& rs, double& llt) const {
-        const double amu = alpha * mu;
-        // one reciprocal: q = 1 / (1 + alpha mu), w = mu q; where alpha mu overflowed (or is NaN) the limits w = 1 / alpha, q = 0
-        const bool big = !(amu <= 1e300);
-        const double q = big ? 0.0 : 1.0 / (1.0 + amu);
-        wgt = big ? theta : mu * q;
-        const double L = amu < 9007199254740992.0 ? log1p(amu) : (mu < INFINITY ? eta + log_alpha : INFINITY);
-        rs = big ? -theta : (yv - mu) * q;
-        llt = yv * eta - (alpha > 0.0 ? (yv + theta) * L : mu);      // (y + theta) L -> mu as alpha -> 0
-    }
-};
 
 // ---- the dispersion step: the NB_NQ sums over (y, mu) at one theta -----------------------------------------------------
 // alpha = 0 (the fit's look at the Poisson MLE) skips the special functions: only Pearson, the two moment sums and the check.
@@ -174,11 +151,17 @@ static int nb_pass_impl(const double* X, int64_t ldx, const double* y, const dou
 }
 
 // the NB_NQ sums at theta = 1 / alpha (alpha = 0: no special functions) into tst (device)
-static int nb_theta_launch(const double* y, const double* mu, const double* off, int64_t n, double alpha, int want_lg, double* tpart,
-                           double* tst, hipStream_t s) {
+int nb_theta_launch(const double* y, const double* mu, const double* off, int64_t n, double alpha, int want_lg, double* tpart,
+                    double* tst, hipStream_t s) {
     const int blocks = (int)std::min<int64_t>(NB_THETA_BLOCKS, std::max<int64_t>(1, (n + 255) / 256));
     hipLaunchKernelGGL(negbin_theta_kernel, dim3(blocks), dim3(256), 0, s, y, mu, off, n, alpha, 1.0 / alpha, want_lg, tpart);
     hipLaunchKernelGGL(negbin_theta_finish_kernel, dim3(1), dim3(64 * NB_NQ), 0, s, (const double*)tpart, blocks, tst);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int nb_ll_fix(double* ll, const double* tst, hipStream_t s) {
+    hipLaunchKernelGGL(negbin_ll_fix_kernel, dim3(1), dim3(64), 0, s, ll, tst);
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
@@ -187,7 +170,7 @@ constexpr double NB_ALPHA_START_MIN = 1e-3;     // floor of the moment start
 constexpr double NB_ALPHA_POISSON = 1e-8;       // the theta iteration below this alpha: the partition is Poisson (alpha = 0)
 
 struct NbFitCtx : NewtonState {                // (stats, beta, prev, delta, g, Lf: the Newton state)
-    const double* Xk; int64_t pitch; const double* yk; const double* ok; int64_t nk;
+    const double* yk; const double* ok; int64_t nk;
     double tol;
     double* w; double* mu; double* tpart; double* tst;
     hipStream_t s;
@@ -229,6 +212,130 @@ static int nb_theta_solve(const NbFitCtx& c, double& alpha, double* t, int& thet
     return DLSA_OK;
 }
 
+// The per-partition driver of the NB2 fits (negbin_internal.h): the dense entry below and the structured one (onehot_negbin.hip)
+// differ in `pois` (the Poisson block of partition k) and `evalk` (the evaluation at (beta, alpha)) alone.
+int nb_fit_core(const char* who, const double* y, const double* offset, const int64_t* part_first_host, const int64_t* part_rows_host,
+                int64_t row_step, int K, int pe, double alpha_fixed, double tol, int max_iter, double* coef, double* Sig_inv,
+                double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, double* alpha_host,
+                double* alpha_info_host, double* pearson_host, const NbFitBufs& b, const NbPoisFit& pois, const NbEval& evalk,
+                hipStream_t s) {
+    const bool fixed = alpha_fixed > 0;
+    NbFitCtx c{};
+    c.tol = tol;
+    // (NbFitCtx derives from NewtonState so that the passes keep reading c.beta, c.g, ... while the carving has one copy)
+    static_cast<NewtonState&>(c) = b.st;
+    c.w = b.w; c.mu = b.mu; c.tpart = b.tpart; c.tst = b.tst;
+    c.s = s;
+    int overall = DLSA_OK;
+    for (int k = 0; k < K; ++k) {
+        const int64_t nk = part_rows_host[k];
+        double* Hk = Sig_inv + (size_t)k * pe * pe;
+        double* ck = coef + (size_t)k * pe;
+        double* sk = Sig_invMcoef + (size_t)k * pe;
+        // 1. the Poisson fit of the partition: the start, the data check, the EMPTY block, and the answer where alpha = 0
+        int st_k = DLSA_PART_EMPTY, iters = 0;
+        double ll = 0.0, alpha = 0.0, info = 0.0, pearson = 0.0;
+        int rc = pois(k, ck, Hk, sk, &iters, &st_k, &ll);
+        if (rc == DLSA_ERR_INVALID) {
+            set_error("%s: partition %d has rows with a negative or non-finite count or offset", who, k);
+            return rc;
+        }
+        if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
+        if (st_k == DLSA_PART_OK) {
+            c.nk = nk;
+            c.yk = y + part_first_host[k];
+            c.ok = offset ? offset + part_first_host[k] : nullptr;
+            if (row_step > 1) {                               // the partition's counts and offsets, gathered once
+                rc = pois_gather(y, part_first_host[k], row_step, nk, b.ybuf, s);
+                if (rc) return rc;
+                c.yk = b.ybuf;
+                if (offset) {
+                    rc = pois_gather(offset, part_first_host[k], row_step, nk, b.obuf, s);
+                    if (rc) return rc;
+                    c.ok = b.obuf;
+                }
+            }
+            DLSA_HIP_CHECK(hipMemcpyAsync(c.beta, ck, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
+            // mu at the Poisson MLE (alpha = 0: the Poisson limit; no H, no g), then the moment sums
+            rc = evalk(k, c.yk, c.ok, nk, c.beta, 0.0, nullptr, nullptr, nullptr, nullptr, c.mu);
+            if (rc) return rc;
+            int passes = 1, theta_iters = 0;
+            double t[NB_NQ];
+            rc = nb_theta_eval(c, 0.0, 1, t);
+            if (rc) return rc;
+            const double lg1 = t[NB_LG];
+            pearson = t[NB_PEARSON];
+            bool poisson = !fixed && !(t[NB_D0] > 0.0);        // 3. not overdispersed: the MLE is alpha = 0, the Poisson block stands
+            if (!poisson) {
+                alpha = fixed ? alpha_fixed : std::max(t[NB_M1] / t[NB_M2], NB_ALPHA_START_MIN);
+                if (!isfinite(alpha)) alpha = NB_ALPHA_START_MIN;
+                const int max_passes = max_iter + 2;
+                double ll1 = 0.0, fs = 0.0, yl = 0.0;
+                if (!fixed) {                                  // theta for the Poisson fit's mu
+                    rc = nb_theta_solve(c, alpha, t, theta_iters, poisson, fs, yl);
+                    if (rc) return rc;
+                }
+                if (!poisson) {
+                    // The fit proper, from the Poisson MLE in c.beta and the start alpha, is newton_fit_loop with the policy
+                    // NEWTON_NB2 and this hook: after every ACCEPTED evaluation at (beta, alpha) -- H, g, the row log-likelihood, w,
+                    // mu -- theta is solved for that mu (16 bytes per row and iteration), then beta takes the Newton step that
+                    // evaluation gave..  H is the expected information, so at alpha > 0 the beta iteration is Fisher scoring (linear
+                    // convergence); one theta solve per step keeps the two in lockstep instead of nesting one iteration in the
+                    // other..  A step is halved while the row log-likelihood at the SAME alpha drops or is not finite: the previous
+                    // point's value is moved to the new alpha with sum (y + theta) L of its mu (ll_shift)..  Converged where the step of
+                    // beta meets the IRLS rule and theta did not move (first_step): then H, g and t are at the returned (beta,
+                    // alpha)..  fixed: no theta steps.
+                    const auto eval = [&](bool&) {
+                        return evalk(k, c.yk, c.ok, nk, c.beta, alpha, Hk, c.g, c.stats + 3, c.w, c.mu);
+                    };
+                    const auto theta_hook = [&](bool& leave, double& first_step, double& ll_shift) {
+                        if (fixed) return (int)DLSA_OK;
+                        double yl_old = 0.0;
+                        const int rch = nb_theta_solve(c, alpha, t, theta_iters, poisson, first_step, yl_old);
+                        leave = poisson;                           // alpha fell to 0: the Poisson block, below
+                        ll_shift = yl_old - t[NB_YL];              // this point's row log-likelihood at the new alpha
+                        return rch;
+                    };
+                    NewtonOutcome o;
+                    rc = newton_fit_loop(NEWTON_NB2, tol, max_passes - passes, eval, NewtonDevice{c, Hk, pe, s}, theta_hook, o);
+                    if (rc) return rc;
+                    passes += o.evals; ll1 = o.ll; st_k = o.status;
+                }
+                if (poisson && passes == 1) {                  // the dispersion iterate ran off to 0 before H was touched
+                    alpha = 0.0;
+                } else if (poisson) {                          // ... or later: the Poisson block again
+                    rc = pois(k, ck, Hk, sk, nullptr, &st_k, &ll);
+                    if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
+                    alpha = 0.0;
+                } else {
+                    if (fixed && st_k == DLSA_PART_OK) {
+                        rc = nb_theta_eval(c, alpha, 0, t);
+                        if (rc) return rc;
+                    }
+                    ll = ll1 + (t[NB_C] - lg1);
+                    info = t[NB_I] / (alpha * alpha);
+                    pearson = t[NB_PEARSON];
+                    DLSA_HIP_CHECK(hipMemcpyAsync(ck, c.beta, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
+                    rc = launch_matvec(Hk, pe, c.beta, pe, sk, s);
+                    if (rc) return rc;
+                }
+            }
+            iters += passes;
+        } else if (st_k != DLSA_PART_EMPTY) {
+            alpha = NAN; info = NAN; pearson = NAN;
+        }
+        if (n_iter_host) n_iter_host[k] = iters;
+        if (status_host) status_host[k] = st_k;
+        if (loglik_host) loglik_host[k] = ll;
+        if (alpha_host) alpha_host[k] = alpha;
+        if (alpha_info_host) alpha_info_host[k] = info;
+        if (pearson_host) pearson_host[k] = pearson;
+        newton_fold_status(st_k, overall);
+    }
+    DLSA_HIP_CHECK(hipStreamSynchronize(s));
+    return overall;
+}
+
 }  // namespace dlsa
 
 extern "C" {
@@ -262,10 +369,7 @@ int dlsa_negbin_pass_f64(const double* X, int64_t ldx, const double* y, const do
     rc = nb_theta_launch(y, mu, offset, n, alpha, loglik ? 1 : 0, (double*)(wsc + l.off_tpart), tst, s);
     if (rc) return rc;
     if (theta_terms) DLSA_HIP_CHECK(hipMemcpyAsync(theta_terms, tst + NB_S, 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (loglik) {
-        hipLaunchKernelGGL(negbin_ll_fix_kernel, dim3(1), dim3(64), 0, s, loglik, (const double*)tst);
-        DLSA_HIP_CHECK(hipGetLastError());
-    }
+    if (loglik) return nb_ll_fix(loglik, tst, s);
     return DLSA_OK;
 }
 
@@ -281,7 +385,6 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
                  (long long)ldx, (long long)row_step);
     DLSA_REQUIRE(max_iter > 0 && tol > 0, "negbin_fit: bad tol/max_iter");
     DLSA_REQUIRE(!(alpha_fixed > 0) || isfinite(alpha_fixed), "negbin_fit: a fixed alpha must be finite");
-    const bool fixed = alpha_fixed > 0;
     int64_t max_rows = 0;
     for (int k = 0; k < K; ++k) {
         DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "negbin_fit: negative partition shape (partition %d)", k);
@@ -293,125 +396,23 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
     if (rcw) return rcw;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
-    NbFitCtx c{};
-    c.pitch = ldx * row_step; c.tol = tol;
-    // (NbFitCtx derives from NewtonState so that the passes keep reading c.beta, c.g, ... while the carving has one copy)
-    static_cast<NewtonState&>(c) = newton_state_at(wsc + l.off_state, pe);
-    c.w = (double*)(wsc + l.off_w); c.mu = (double*)(wsc + l.off_mu);
-    c.tpart = (double*)(wsc + l.off_tpart); c.tst = (double*)(wsc + l.off_tst);
-    c.s = s;
-    int overall = DLSA_OK;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        double* Hk = Sig_inv + (size_t)k * pe * pe;
-        double* ck = coef + (size_t)k * pe;
-        double* sk = Sig_invMcoef + (size_t)k * pe;
-        // 1. the Poisson fit of the partition: the start, the data check, the EMPTY block, and the answer where alpha = 0
-        int st_k = DLSA_PART_EMPTY, iters = 0;
-        double ll = 0.0, alpha = 0.0, info = 0.0, pearson = 0.0;
-        int rc = dlsa_poisson_fit_f64(X, ldx, y, offset, part_first_host + k, part_rows_host + k, row_step, 1, p, intercept, tol, max_iter,
-                                      ck, Hk, sk, &iters, &st_k, &ll, wsc + l.off_pois, l.total - l.off_pois, stream);
-        if (rc == DLSA_ERR_INVALID) {
-            set_error("negbin_fit: partition %d has rows with a negative or non-finite count or offset", k);
-            return rc;
-        }
-        if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
-        if (st_k == DLSA_PART_OK) {
-            c.Xk = X + part_first_host[k] * ldx; c.nk = nk;
-            c.yk = y + part_first_host[k];
-            c.ok = offset ? offset + part_first_host[k] : nullptr;
-            if (row_step > 1) {                               // the partition's counts and offsets, gathered once
-                double* yb = (double*)(wsc + l.off_y);
-                rc = pois_gather(y, part_first_host[k], row_step, nk, yb, s);
-                if (rc) return rc;
-                c.yk = yb;
-                if (offset) {
-                    double* ob = (double*)(wsc + l.off_o);
-                    rc = pois_gather(offset, part_first_host[k], row_step, nk, ob, s);
-                    if (rc) return rc;
-                    c.ok = ob;
-                }
-            }
-            DLSA_HIP_CHECK(hipMemcpyAsync(c.beta, ck, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
-            // mu at the Poisson MLE (alpha = 0: the kernel's Poisson limit; no H, no g), then the moment sums
-            rc = nb_pass_impl(c.Xk, c.pitch, c.yk, c.ok, c.beta, 0.0, nk, p, intercept, nullptr, pe, nullptr, nullptr, nullptr, c.mu, wsc, l, s);
-            if (rc) return rc;
-            int passes = 1, theta_iters = 0;
-            double t[NB_NQ];
-            rc = nb_theta_eval(c, 0.0, 1, t);
-            if (rc) return rc;
-            const double lg1 = t[NB_LG];
-            pearson = t[NB_PEARSON];
-            bool poisson = !fixed && !(t[NB_D0] > 0.0);        // 3. not overdispersed: the MLE is alpha = 0, the Poisson block stands
-            if (!poisson) {
-                alpha = fixed ? alpha_fixed : std::max(t[NB_M1] / t[NB_M2], NB_ALPHA_START_MIN);
-                if (!isfinite(alpha)) alpha = NB_ALPHA_START_MIN;
-                const int max_passes = max_iter + 2;
-                double ll1 = 0.0, fs = 0.0, yl = 0.0;
-                if (!fixed) {                                  // theta for the Poisson fit's mu
-                    rc = nb_theta_solve(c, alpha, t, theta_iters, poisson, fs, yl);
-                    if (rc) return rc;
-                }
-                if (!poisson) {
-                    // The fit proper, from the Poisson MLE in c.beta and the start alpha, is newton_fit_loop with the policy
-                    // NEWTON_NB2 and this hook: after every ACCEPTED evaluation at (beta, alpha) -- H, g, the row log-likelihood, w,
-                    // mu -- theta is solved for that mu (16 bytes per row and iteration), then beta takes the Newton step that
-                    // evaluation gave..  H is the expected information, so at alpha > 0 the beta iteration is Fisher scoring (linear
-                    // convergence); one theta solve per step keeps the two in lockstep instead of nesting one iteration in the
-                    // other..  A step is halved while the row log-likelihood at the SAME alpha drops or is not finite: the previous
-                    // point's value is moved to the new alpha with sum (y + theta) L of its mu (ll_shift)..  Converged where the step of
-                    // beta meets the IRLS rule and theta did not move (first_step): then H, g and t are at the returned (beta,
-                    // alpha)..  fixed: no theta steps.
-                    const auto eval = [&](bool&) {
-                        return nb_pass_impl(c.Xk, c.pitch, c.yk, c.ok, c.beta, alpha, nk, p, intercept, Hk, pe, c.g, c.stats + 3, c.w, c.mu, wsc, l, s);
-                    };
-                    const auto theta_hook = [&](bool& leave, double& first_step, double& ll_shift) {
-                        if (fixed) return (int)DLSA_OK;
-                        double yl_old = 0.0;
-                        const int rch = nb_theta_solve(c, alpha, t, theta_iters, poisson, first_step, yl_old);
-                        leave = poisson;                           // alpha fell to 0: the Poisson block, below
-                        ll_shift = yl_old - t[NB_YL];              // this point's row log-likelihood at the new alpha
-                        return rch;
-                    };
-                    NewtonOutcome o;
-                    rc = newton_fit_loop(NEWTON_NB2, tol, max_passes - passes, eval, NewtonDevice{c, Hk, pe, s}, theta_hook, o);
-                    if (rc) return rc;
-                    passes += o.evals; ll1 = o.ll; st_k = o.status;
-                }
-                if (poisson && passes == 1) {                  // the dispersion iterate ran off to 0 before H was touched
-                    alpha = 0.0;
-                } else if (poisson) {                          // ... or later: the Poisson block again
-                    rc = dlsa_poisson_fit_f64(X, ldx, y, offset, part_first_host + k, part_rows_host + k, row_step, 1, p, intercept, tol,
-                                              max_iter, ck, Hk, sk, nullptr, &st_k, &ll, wsc + l.off_pois, l.total - l.off_pois, stream);
-                    if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
-                    alpha = 0.0;
-                } else {
-                    if (fixed && st_k == DLSA_PART_OK) {
-                        rc = nb_theta_eval(c, alpha, 0, t);
-                        if (rc) return rc;
-                    }
-                    ll = ll1 + (t[NB_C] - lg1);
-                    info = t[NB_I] / (alpha * alpha);
-                    pearson = t[NB_PEARSON];
-                    DLSA_HIP_CHECK(hipMemcpyAsync(ck, c.beta, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
-                    rc = launch_matvec(Hk, pe, c.beta, pe, sk, s);
-                    if (rc) return rc;
-                }
-            }
-            iters += passes;
-        } else if (st_k != DLSA_PART_EMPTY) {
-            alpha = NAN; info = NAN; pearson = NAN;
-        }
-        if (n_iter_host) n_iter_host[k] = iters;
-        if (status_host) status_host[k] = st_k;
-        if (loglik_host) loglik_host[k] = ll;
-        if (alpha_host) alpha_host[k] = alpha;
-        if (alpha_info_host) alpha_info_host[k] = info;
-        if (pearson_host) pearson_host[k] = pearson;
-        newton_fold_status(st_k, overall);
-    }
-    DLSA_HIP_CHECK(hipStreamSynchronize(s));
-    return overall;
+    NbFitBufs b{};
+    b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
+    b.w = (double*)(wsc + l.off_w); b.mu = (double*)(wsc + l.off_mu);
+    b.tpart = (double*)(wsc + l.off_tpart); b.tst = (double*)(wsc + l.off_tst);
+    b.st = newton_state_at(wsc + l.off_state, pe);
+    const int64_t pitch = ldx * row_step;
+    const NbPoisFit pois = [=](int k, double* ck, double* Hk, double* sk, int* iters, int* st_k, double* ll) {
+        return dlsa_poisson_fit_f64(X, ldx, y, offset, part_first_host + k, part_rows_host + k, row_step, 1, p, intercept, tol, max_iter,
+                                    ck, Hk, sk, iters, st_k, ll, wsc + l.off_pois, l.total - l.off_pois, stream);
+    };
+    const NbEval eval = [=](int k, const double* yk, const double* ok, int64_t nk, const double* beta, double alpha, double* H, double* g,
+                            double* ll, double* w, double* mu) {
+        return nb_pass_impl(X + part_first_host[k] * ldx, pitch, yk, ok, beta, alpha, nk, p, intercept, H, pe, g, ll, w, mu, wsc, l, s);
+    };
+    return nb_fit_core("negbin_fit", y, offset, part_first_host, part_rows_host, row_step, K, pe, alpha_fixed, tol, max_iter, coef,
+                       Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host, alpha_host, alpha_info_host, pearson_host, b, pois,
+                       eval, s);
 }
 
 int dlsa_negbin_special_f64(const double* theta, const double* y, int64_t n, double* out, void* stream) {

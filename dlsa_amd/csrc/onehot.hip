@@ -36,12 +36,14 @@ constexpr int OH_MAX_BLOCKS = 512;          // two workgroups per CU; every work
 // logit pass: w, per-workgroup partial of g (p doubles) and loglik -- oh_row_kernel<OhLogitRow> (onehot_pass.h)
 // ---------------------------------------------------------------------------------------------------------------
 struct OhLogitRow {       // e = exp(-|eta|): mu = sigmoid(eta), w = mu (1 - mu) = e / (1 + e)^2, term = y eta - softplus(eta)
+    static constexpr bool STORES_MU = false;
     double e, inv;        // of the row in hand: exp(-|eta|) and 1 / (1 + e)
     __device__ __forceinline__ double mean(int64_t, double& eta) {
         e = exp_neg(fabs(eta));
         inv = rcp_newton(1.0 + e);
         return eta >= 0.0 ? inv : e * inv;
     }
+    __device__ __forceinline__ double resid(double y, double, double mu) const { return y - mu; }
     __device__ __forceinline__ double weight(double) const { return e * inv * inv; }
     __device__ __forceinline__ double term(double y, double eta, double) const { return y * eta - (fmax(eta, 0.0) + log1p(e)); }
 };
@@ -270,7 +272,7 @@ int onehot_logit_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_
         set_error("onehot logit pass: workspace %zu bytes needed (256-aligned), got %zu", onehot_workspace_bytes_impl(pl, n), ws_bytes);
         return DLSA_ERR_WORKSPACE;
     }
-    return oh_row_pass("onehot logit pass", OhLogitRow{}, pl, num, ldn, codes, ldc, y, beta, n, w_out, g, loglik, ws, ws_bytes, s);
+    return oh_row_pass("onehot logit pass", OhLogitRow{}, pl, num, ldn, codes, ldc, y, beta, n, w_out, nullptr, g, loglik, ws, ws_bytes, s);
 }
 
 // irls_weights: w are the logistic weights mu (1 - mu) in (0, 1/4] of this library's own logit pass (the IRLS driver) -- the addends'

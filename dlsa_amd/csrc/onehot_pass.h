@@ -1,20 +1,25 @@
-// The row pass of the structured one-hot models (logistic: onehot.hip, Poisson: onehot_poisson.hip): one kernel and its launch
-// driver, as templates on the ROW MODEL M -- a struct of the model's per-row inputs (and what it keeps of the row in hand) with
+// The row pass of the structured one-hot models (logistic: onehot.hip, Poisson: onehot_poisson.hip, NB2: onehot_negbin.hip): one
+// kernel and its launch driver, as templates on the ROW MODEL M -- a struct of the model's per-row inputs (and what it keeps of
+// the row in hand) with
+//   static constexpr bool STORES_MU   the pass also writes mu per row (mu_out, nullable) next to the Gram's weight
 //   double mean(i, eta)          row i's offset added to eta (if the model has one); returns mu
+//   double resid(y, eta, mu)     the row's residual, the multiplier of its columns in g (y - mu, or the model's own)
 //   double weight(mu)            the Gram's weight of the row (computed only where it is stored)
 //   double term(y, eta, mu)      the row's log-likelihood term (computed only for rows below n)
+// called in this order on a copy of the model per row.
 // The model is a compile-time type: an instantiation holds its own terms only, and nothing here asks which model it serves.
 // Included inside namespace dlsa after onehot_plan.h; the library is built without relocatable device code, so the kernel is
 // instantiated in the file that launches it.
 
-// One thread per row: eta = d . beta_D + sum_t beta[col(t, code_t)] is a gather, r = y - mu; per-workgroup partials of g (dense
-// part in registers, level part an LDS histogram) and of the log-likelihood terms; w per row to w_out (nullable).
+// One thread per row: eta = d . beta_D + sum_t beta[col(t, code_t)] is a gather, r = the model's residual; per-workgroup partials
+// of g (dense part in registers, level part an LDS histogram) and of the log-likelihood terms; w per row to w_out (nullable), mu
+// per row to mu_out (nullable; M::STORES_MU only).
 template <class M>
 __global__ __launch_bounds__(OH_THREADS) void oh_row_kernel(OhDesc ds, const int32_t* __restrict__ level_col,
                                                             const double* __restrict__ num, int64_t ldn,
                                                             const int32_t* __restrict__ codes, int64_t ldc,
                                                             const double* __restrict__ y, const double* __restrict__ beta,
-                                                            int64_t n, double* __restrict__ w_out,
+                                                            int64_t n, double* __restrict__ w_out, double* __restrict__ mu_out,
                                                             double* __restrict__ gpart, double* __restrict__ llpart, int nrep, M m) {
     extern __shared__ double sm[];
     double* sbeta = sm;                           // p
@@ -59,8 +64,10 @@ __global__ __launch_bounds__(OH_THREADS) void oh_row_kernel(OhDesc ds, const int
         const double yv = y[i];
         M row = m;                                  // the model's inputs and this row's own state
         const double mu = row.mean(i, eta);
+        const double rs = row.resid(yv, eta, mu);
         if (w_out && valid) w_out[i] = row.weight(mu);
-        const double r = valid ? yv - mu : 0.0;
+        if constexpr (M::STORES_MU) { if (mu_out && valid) mu_out[i] = mu; }
+        const double r = valid ? rs : 0.0;
         if (valid) ll += row.term(yv, eta, mu);
 #pragma unroll
         for (int a = 0; a < OH_MAXD; ++a) gd[a] = fma(r, d[a], gd[a]);
@@ -96,13 +103,13 @@ __global__ __launch_bounds__(OH_THREADS) void oh_row_kernel(OhDesc ds, const int
     if (threadIdx.x == 0) llpart[blockIdx.x] = sll;
 }
 
-// One partition at a fixed beta: w per row (nullable), g and loglik (the sum of the model's terms; nullable) through the
-// fixed-order column sums of the per-workgroup partials.  ws: the structured passes' arena (256-aligned, at least
+// One partition at a fixed beta: w and (M::STORES_MU) mu per row (nullable), g and loglik (the sum of the model's terms;
+// nullable) through the fixed-order column sums of the per-workgroup partials.  ws: the structured passes' arena (256-aligned, at least
 // onehot_workspace_bytes_impl(pl, n)); `who` prefixes the message.
 template <class M>
 static int oh_row_pass(const char* who, const M& m, const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes,
-                       int64_t ldc, const double* y, const double* beta, int64_t n, double* w_out, double* g, double* loglik,
-                       void* ws, size_t ws_bytes, hipStream_t s) {
+                       int64_t ldc, const double* y, const double* beta, int64_t n, double* w_out, double* mu_out, double* g,
+                       double* loglik, void* ws, size_t ws_bytes, hipStream_t s) {
     OhDesc ds = pl->desc;
     { const char* e = kernel_knob("DLSA_OH_ORDERED"); ds.ordered = e ? (atoi(e) != 0) : 1; }      // wave turn-taking unless 0
     ds.overflow = nullptr;
@@ -117,7 +124,7 @@ static int oh_row_pass(const char* who, const M& m, const dlsa_onehot_plan* pl, 
     const int nrep = oh_logit_rep(ds.p);
     const size_t shm = (size_t)((1 + nrep) * ds.p + 16) * sizeof(double) + (size_t)((ds.nlev_total + 1) & ~1) * sizeof(int);
     hipLaunchKernelGGL(oh_row_kernel<M>, dim3(nb), dim3(OH_THREADS), shm, s, ds, (const int32_t*)pl->d_level_col, num, ldn, codes,
-                       ldc, y, beta, n, w_out, gpart, llpart, nrep, m);
+                       ldc, y, beta, n, w_out, mu_out, gpart, llpart, nrep, m);
     DLSA_HIP_CHECK(hipGetLastError());
     if (g || loglik) {
         logit_finish_launch((const double*)gpart, (const double*)llpart, nb, ds.p, ds.p, g, loglik, s, nullptr, nullptr);

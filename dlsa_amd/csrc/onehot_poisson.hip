@@ -14,7 +14,7 @@
 //                           floating-point mode (full relative accuracy at any scale, bit-reproducible), never the fixed-point one.
 // Traffic per row: 8q + 4f + 8 (y) + 8 (o) + 8 (mu written) bytes for the pass, 8q + 4f + 8 for the Gram.
 // The constant sum lgamma(y + 1), the data check, the gather of a strided partition's counts / offsets and the Newton loop
-// are poisson.hip's (poisson_internal.h).
+// are poisson.hip's (poisson_internal.h).  The NB2 sibling (onehot_negbin.hip) takes the pass and the row checks from here.
 #include "common.h"
 #include "onehot_plan.h"
 #include "poisson_internal.h"
@@ -28,11 +28,13 @@ namespace dlsa {
 
 template <bool OFF>       // OFF = false reads no offsets
 struct OhPoisRow {        // eta += o, mu = exp(eta) = w, term = y eta - mu
+    static constexpr bool STORES_MU = false;
     const double* off;
     __device__ __forceinline__ double mean(int64_t i, double& eta) const {
         if constexpr (OFF) eta += off[i];
         return exp_full(eta);
     }
+    __device__ __forceinline__ double resid(double y, double, double mu) const { return y - mu; }
     __device__ __forceinline__ double weight(double mu) const { return mu; }
     __device__ __forceinline__ double term(double y, double eta, double mu) const { return y * eta - mu; }
 };
@@ -76,18 +78,18 @@ static int oh_pois_icpt_col(const dlsa_onehot_plan* pl) {      // the plan's con
 
 // One partition at a fixed beta.  H (nullable) needs w (mu per row: the Gram's weights); g, loglik (the sum of y eta - mu,
 // without the constant) nullable.  ws_oh: the structured passes' arena (256-aligned, >= onehot_workspace_bytes_impl(pl, n)).
-static int oh_pois_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+int oh_pois_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
                              const double* y, const double* off, const double* beta, int64_t n, double* H, int64_t ldh, double* g,
                              double* loglik, double* w, void* ws_oh, size_t ws_oh_bytes, hipStream_t s) {
     const char* who = "onehot poisson pass";
-    const int rc = off ? oh_row_pass(who, OhPoisRow<true>{off}, pl, num, ldn, codes, ldc, y, beta, n, w, g, loglik, ws_oh, ws_oh_bytes, s)
-                       : oh_row_pass(who, OhPoisRow<false>{off}, pl, num, ldn, codes, ldc, y, beta, n, w, g, loglik, ws_oh, ws_oh_bytes, s);
+    const int rc = off ? oh_row_pass(who, OhPoisRow<true>{off}, pl, num, ldn, codes, ldc, y, beta, n, w, nullptr, g, loglik, ws_oh, ws_oh_bytes, s)
+                       : oh_row_pass(who, OhPoisRow<false>{off}, pl, num, ldn, codes, ldc, y, beta, n, w, nullptr, g, loglik, ws_oh, ws_oh_bytes, s);
     if (rc || !H) return rc;
     // (the Gram's partials overwrite the pass's in the same arena: the finish launch above has consumed them, in stream order)
     return onehot_gram_impl(pl, num, ldn, codes, ldc, w, n, H, ldh, ws_oh, ws_oh_bytes, s, false);
 }
 
-static int oh_pois_check_rows(const char* who, const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes,
+int oh_pois_check_rows(const char* who, const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes,
                               int64_t ldc) {
     DLSA_REQUIRE(num || !pl->needs_num, "%s: null num (the plan has numeric columns)", who);
     DLSA_REQUIRE(codes || pl->desc.f == 0, "%s: null codes (the plan has factors)", who);

@@ -1,6 +1,6 @@
-// What is Poisson's among the things the count-model translation units (poisson.hip, onehot_poisson.hip, negbin.hip) share: the
-// constant-term, log-likelihood-fix and gather launchers of poisson.hip, and the fit driver that takes the evaluation as a
-// callable.  The Newton state, loop and epilogue are newton_fit.h; the prototypes of the rest of the library are host_calls.h.
+// What is Poisson's among the things the count-model translation units (poisson.hip, onehot_poisson.hip, negbin.hip,
+// onehot_negbin.hip) share: the constant-term, log-likelihood-fix and gather launchers of poisson.hip, the fit driver that takes
+// the evaluation as a callable, and the structured pass of onehot_poisson.hip.  The Newton state, loop and epilogue are newton_fit.h; the prototypes of the rest of the library are host_calls.h.
 #pragma once
 #include "common.h"
 #include "newton_fit.h"
@@ -39,5 +39,14 @@ int pois_fit_core(const char* who, const double* y, const double* offset, const 
                   const int64_t* part_rows_host, int64_t row_step, int K, int pe, int icpt_col, double tol, int max_iter,
                   double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
                   const PoisFitBufs& b, const PoisEval& eval, hipStream_t s);
+
+// ---- onehot_poisson.hip ------------------------------------------------------------------------------------------------
+// One partition at a fixed beta on the raw representation: H (nullable) needs w (mu per row); g, loglik (the sum of y eta - mu)
+// nullable.  ws_oh: the structured passes' arena (256-aligned, >= onehot_workspace_bytes_impl(pl, n)).
+int oh_pois_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc, const double* y,
+                      const double* off, const double* beta, int64_t n, double* H, int64_t ldh, double* g, double* loglik, double* w,
+                      void* ws_oh, size_t ws_oh_bytes, hipStream_t s);
+// num / codes against what the plan reads (null pointers, ldn, ldc); `who` prefixes the message
+int oh_pois_check_rows(const char* who, const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc);
 
 }  // namespace dlsa

@@ -1245,6 +1245,72 @@ def onehot_poisson_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1
             "loglik": list(ll), "rc": rc}
 
 
+def onehot_negbin_pass(plan, num, codes, y, beta, alpha, offset=None, want_H=True, want_w=False, want_theta=False):
+    """negbin_pass on the raw representation of a one-hot design (dlsa_onehot_negbin_pass_f64): rows and beta as
+    onehot_poisson_pass, alpha > 0 as negbin_pass.  Returns (H [p,p] = X' diag(mu / (1 + alpha mu)) X or None, g [p], loglik [1] = the
+    full log-likelihood, w [n] or None, mu [n] or None (with want_w), theta_terms [3] = (s, i, pearson) or None (with want_theta))
+    of the matrix dlsa_design_f64 would build -- which is never built."""
+    lib = _lib.load()
+    _require_gpu(beta)
+    _f64(beta, "beta")
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_negbin_pass")
+    p = plan.p
+    if n < 1 or beta.numel() != p:
+        raise ValueError("onehot_negbin_pass: need n >= 1 rows and beta with %d elements" % p)
+    alpha = float(alpha)
+    if not (alpha > 0.0 and alpha < float("inf")):
+        raise ValueError("onehot_negbin_pass: alpha must be positive and finite (alpha = 0 is onehot_poisson_pass)")
+    dev = y.device
+    H = torch.empty((p, p), dtype=torch.float64, device=dev) if want_H else None
+    g = torch.empty((p,), dtype=torch.float64, device=dev)
+    ll = torch.empty((1,), dtype=torch.float64, device=dev)
+    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
+    mu = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
+    tt = torch.empty((3,), dtype=torch.float64, device=dev) if want_theta else None
+    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, n, 1), dev)
+    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
+    check(lib.dlsa_onehot_negbin_pass_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), _ptr(beta), alpha, n, _ptr(H), p, _ptr(g),
+                                          _ptr(ll), _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, w, mu, tt
+
+
+def onehot_negbin_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, alpha=None, tol=1e-13, max_iter=100):
+    """negbin_fit_ex on the raw representation of a one-hot design (dlsa_onehot_negbin_fit_f64): partitions as
+    onehot_poisson_fit_ex, alpha as negbin_fit_ex.  Same result dict as negbin_fit_ex, plan.p columns in the plan's order."""
+    lib = _lib.load()
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_negbin_fit_ex")
+    p = plan.p
+    if alpha is not None:
+        alpha = float(alpha)
+        if alpha == 0.0:
+            raise ValueError("onehot_negbin_fit_ex: alpha = 0 is the Poisson model: use onehot_poisson_fit_ex")
+        if not (alpha > 0.0 and alpha < float("inf")):
+            raise ValueError("onehot_negbin_fit_ex: a fixed alpha must be positive and finite")
+    first, rows = [int(v) for v in part_first], [int(v) for v in part_rows]
+    K, step = len(first), int(row_step)
+    if len(rows) != K or K == 0 or step < 1:
+        raise ValueError("onehot_negbin_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
+    for f, r in zip(first, rows):
+        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
+            raise ValueError("onehot_negbin_fit_ex: partition outside the %d rows" % n)
+    dev = y.device
+    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
+    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
+    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
+    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, max(rows), step), dev)
+    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
+    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
+    al, info, pear = (ctypes.c_double * K)(), (ctypes.c_double * K)(), (ctypes.c_double * K)()
+    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
+    rc = lib.dlsa_onehot_negbin_fit_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), c_first, c_rows, step, K,
+                                        alpha if alpha is not None else 0.0, tol, max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter,
+                                        status, ll, al, info, pear, _ptr(ws), ws.numel(), _stream())
+    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
+        check(rc)
+    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
+            "loglik": list(ll), "alpha": list(al), "alpha_info": list(info), "pearson": list(pear), "rc": rc}
+
+
 class RcclComm:
     """An RCCL communicator opened through the C ABI (dlsa_comm_unique_id / dlsa_comm_init_rank), for hosts that do not
     use torch.distributed: rank 0 creates `RcclComm.unique_id()`, ships the 128 bytes to the other ranks out of band, every

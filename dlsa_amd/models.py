@@ -891,6 +891,43 @@ def fit_negbin_partitions(X, y, partition_num=None, part_offsets=None, fit_inter
                         extra={"alpha": r["alpha"], "alpha_info": r["alpha_info"], "pearson": r["pearson"]})
 
 
+def fit_negbin_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, alpha=None,
+                      structured=True, tol=1e-13, max_iter=100):
+    """Negative-binomial map step for a design given by its RAW columns, the sibling of fit_poisson_design: num [n, q] fp64, codes
+    [n, f] int32 level codes and counts y [n], all on the GPU.  With structured=True and a qualifying design (spec.onehot_plan())
+    the fit runs on the raw representation -- the dense [n, p] matrix is never built; otherwise the matrix is built once by the
+    design kernel and the dense NB2 fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and
+    `exposure` as fit_poisson_partitions, alpha as fit_negbin_partitions (alpha = 0 is refused: that is fit_poisson_design).  Same
+    MappedBlocks either way (names = spec.names, `extra` = {"alpha", "alpha_info", "pearson"} per partition)."""
+    if not torch.is_tensor(y) or not y.is_cuda:
+        raise RuntimeError("fit_negbin_design runs on the GPU only (no CPU fallback)")
+    if num is not None and num.dtype != torch.float64:
+        raise TypeError("fit_negbin_design: num must be float64, got %s" % num.dtype)
+    if alpha is not None and float(alpha) == 0.0:
+        raise ValueError("fit_negbin_design: alpha = 0 is the Poisson model: use fit_poisson_design")
+    y = y.to(torch.float64).contiguous()
+    n = y.numel()
+    if bool((y < 0).any()):
+        raise ValueError("fit_negbin_design: counts must be non-negative")
+    offset = _poisson_offset(offset, exposure, n, y.device)
+    if part_offsets is None:
+        K = int(partition_num) if partition_num else 1
+        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
+    else:
+        offs = [int(v) for v in part_offsets]
+        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+    plan = spec.onehot_plan() if structured else None
+    if plan is not None:
+        r = engine.onehot_negbin_fit_ex(plan, engine.row_major(num) if num is not None else None,
+                                        engine.row_major(codes) if codes is not None else None, y, first, rows, row_step=step,
+                                        offset=offset, alpha=alpha, tol=tol, max_iter=max_iter)
+    else:
+        X, _ = spec.build(num, codes)
+        r = engine.negbin_fit_ex(X, y, first, rows, row_step=step, offset=offset, alpha=alpha, tol=tol, max_iter=max_iter)
+    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], spec.names, r["status"], r["n_iter"], r["loglik"], sample_size=n,
+                        extra={"alpha": r["alpha"], "alpha_info": r["alpha_info"], "pearson": r["pearson"]})
+
+
 def combine_dispersion(mb):
     """The common dispersion of a negative-binomial map step: the information-weighted mean of log alpha_k over the partitions with
     status OK and alpha_k > 0 (weights alpha_info), returned as alpha -- the one-round combine of the dispersion, to be passed as
@@ -904,19 +941,38 @@ def combine_dispersion(mb):
 
 
 def negbin_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, alpha=None, dummy_info=[],
-                 dummy_factors_baseline=[], data_info=[]):
+                 dummy_factors_baseline=[], data_info=[], structured=False):
     """Frame-level sibling of poisson_model for overdispersed counts: one partition (a pandas frame) with the count column Y_name and
     optionally an offset or an exposure column; alpha as fit_negbin_partitions.  Returns the p x (3+p) frame `par_id, coef,
     Sig_invMcoef, [intercept,] <features>` with the dispersion in `out.attrs["alpha"]`; a chunk that lacks an expected dummy level
-    returns the all-zero block with a warning."""
-    Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
-                                           dummy_factors_baseline, data_info)
-    if Xd is None:
-        out = pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-        out.attrs["alpha"] = 0.0
-        return out
-    mb = fit_negbin_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, alpha=alpha,
-                               names=names[1:] if fit_intercept else names)
+    returns the all-zero block with a warning.  structured=True with a dummy_info and a qualifying design fits on the raw numerics +
+    level codes (fit_negbin_design; the dense one-hot matrix is never built, the missing-level check runs on the codes); the
+    default is the dense path."""
+    mb = None
+    if structured and len(dummy_info) > 0:
+        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
+                                                                    dummy_info, dummy_factors_baseline, data_info)
+        if plan is not None:
+            names = spec.names
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                shape = (len(sample_df), len(names) - (1 if fit_intercept else 0) - len(missing))
+                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape)
+                              + "Skip modeling this part of data.")
+                out = pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+                out.attrs["alpha"] = 0.0
+                return out
+            mb = fit_negbin_design(spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, spec, offset=od, exposure=ed,
+                                   alpha=alpha)
+    if mb is None:
+        Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                                               dummy_factors_baseline, data_info)
+        if Xd is None:
+            out = pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+            out.attrs["alpha"] = 0.0
+            return out
+        mb = fit_negbin_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, alpha=alpha,
+                                   names=names[1:] if fit_intercept else names)
     st = mb.status[0]
     if st == 1:
         warnings.warn("negbin_model: Newton iterations did not converge (max_iter reached)")
@@ -930,10 +986,28 @@ def negbin_model(sample_df, Y_name, fit_intercept=False, offset_name=None, expos
 
 
 def negbin_model_eval(sample_df, Y_name, par, alpha, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
-                      dummy_factors_baseline=[], data_info=[]):
+                      dummy_factors_baseline=[], data_info=[], structured=False):
     """Negative-binomial log-likelihood at dispersion alpha > 0 of every estimator column of `par` on one partition, shaped like
-    poisson_model_eval's output: one row, a column per estimator (one pass without the information per column)."""
+    poisson_model_eval's output: one row, a column per estimator (one pass without the information per column).  structured=True
+    with a dummy_info and a qualifying design evaluates on the raw numerics + level codes (one structured pass per estimator
+    column); the default is the dense path."""
     pard = np.asarray(par, dtype=np.float64)
+    if structured and len(dummy_info) > 0:
+        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
+                                                                    dummy_info, dummy_factors_baseline, data_info)
+        if plan is not None:
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                shape = (len(sample_df), len(spec.names) - (1 if fit_intercept else 0) - len(missing))
+                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape))
+            od = _poisson_offset(od, ed, yd.numel(), yd.device)
+            num, cd = spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda()
+            out = {}
+            for i in range(pard.shape[1]):
+                b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+                ll = engine.onehot_negbin_pass(plan, num, cd, yd, b, alpha, offset=od, want_H=False)[2]
+                out[par.columns[i]] = [float(ll.item())]
+            return pd.DataFrame(out)
     Xd, _, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
                                        dummy_factors_baseline, data_info, for_eval=True)
     od = _poisson_offset(od, ed, yd.numel(), yd.device)

@@ -535,6 +535,34 @@ int dlsa_onehot_poisson_fit_f64(const dlsa_onehot_plan* plan, const double* num,
                                 double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
                                 void* ws, size_t ws_bytes, void* stream);
 
+/* ---- NB2 map step on the raw representation of a one-hot design (the structured sibling of dlsa_negbin_*_f64) ----------
+ * Rows, plan, column order and unknown codes as dlsa_onehot_poisson_*_f64; the model, the outputs and their meaning as
+ * dlsa_negbin_*_f64 (intercept = 0) on the matrix dlsa_design_f64 would build, which is never built.
+ * dlsa_onehot_negbin_pass_f64 at a fixed beta and alpha > 0 (finite; alpha = 0 is dlsa_onehot_poisson_pass_f64), n >= 1:
+ * H = X' diag(mu / (1 + alpha mu)) X (nullable, ldh >= p), g = X'[(y - mu) / (1 + alpha mu)] (nullable), loglik = the full NB2
+ * log-likelihood (1 value, nullable; NaN when a count is negative or a count / offset is not finite), w_out = mu / (1 + alpha mu)
+ * and mu_out = mu (n each, nullable), theta_terms = (s, i, Pearson) at theta = 1 / alpha (3 values, nullable).  One read of the raw
+ * rows (8q + 4f + 32 bytes per row with an offset), the dispersion sums over (y, mu) when loglik or theta_terms is wanted, and
+ * the structured Gram when H is wanted, which sums w in ordered floating point; g, loglik and H are bit-reproducible.
+ * dlsa_onehot_negbin_fit_f64: partitions as dlsa_onehot_poisson_fit_f64 (num and codes of a strided partition read in place, its
+ * counts and offsets gathered once), the fit of dlsa_negbin_fit_f64 -- each partition first fitted as Poisson
+ * (dlsa_onehot_poisson_fit_f64), alpha_fixed > 0 (finite) fits beta at that dispersion, else alpha is estimated, 0 with exactly
+ * the Poisson block for a partition that is not overdispersed --, the same outputs (alpha_info_host = the information about log
+ * alpha, i theta^2), statuses and DLSA_ERR_INVALID (naming the partition) for a negative or non-finite count or offset.
+ * Workspace: dlsa_onehot_negbin_workspace_bytes(plan, max rows, row_step) (0 for a null plan, max_rows < 0 or row_step < 1;
+ * monotone in max rows); the pass takes the same query with row_step = 1. */
+size_t dlsa_onehot_negbin_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows, int64_t row_step);
+int dlsa_onehot_negbin_pass_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                const double* y, const double* offset, const double* beta, double alpha, int64_t n, double* H,
+                                int64_t ldh, double* g, double* loglik, double* w_out, double* mu_out, double* theta_terms,
+                                void* ws, size_t ws_bytes, void* stream);
+int dlsa_onehot_negbin_fit_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                               const double* y, const double* offset, const int64_t* part_first_host,
+                               const int64_t* part_rows_host, int64_t row_step, int K, double alpha_fixed, double tol, int max_iter,
+                               double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                               double* loglik_host, double* alpha_host, double* alpha_info_host, double* pearson_host, void* ws,
+                               size_t ws_bytes, void* stream);
+
 /* test hook: host-only validation of the Gram tile plan for p (0 = every tile on/above the diagonal
  * is stored exactly once; outputs: workgroup items, tile slots computed, tiles stored). */
 int dlsa_gram_plan_check(int p, int* nitems, int* nslots, int* ntiles);
