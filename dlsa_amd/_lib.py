@@ -113,6 +113,8 @@ SIGNATURES = {
     "dlsa_sym_pinv_workspace_bytes": (c_sz, [c_int]),
     "dlsa_sym_pinv_solve_f64": (c_int, [c_vp, c_i64, c_vp, c_int, c_dbl, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_dbl),
                                         c_vp, c_sz, c_vp]),
+    "dlsa_sym_pinv_probe_f64": (c_int, [c_vp, c_i64, c_vp, c_int, c_dbl, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_dbl),
+                                        ctypes.POINTER(c_int), c_vp, c_i64, c_vp, c_sz, c_vp]),
     "dlsa_lars_workspace_bytes": (c_sz, [c_int]),
     "dlsa_lars_lsa_f64": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_dbl, c_int, c_dbl, c_int,
                                   c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), c_vp, c_sz, c_vp]),

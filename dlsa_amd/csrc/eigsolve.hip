@@ -11,7 +11,12 @@
 // m - 1 rounds per sweep.  Within a round the rotations commute on disjoint 2 x 2 blocks: thread (a, b) owns the block
 // (pair a) x (pair b) of A and of V, computes the two rotations from the diagonal blocks of the INPUT copy and writes the
 // rotated block to the OUTPUT copy (ping-pong, so no thread reads what another writes).  One launch per round; the matrices
-// (2 MB at p = 500) stay in L2.  A sweep ends with a reduction of the off-diagonal mass; 6-10 sweeps reach 1e-30 relative.
+// (2 MB at p = 500) stay in L2.  A sweep ends with a reduction of the off-diagonal mass; the iteration stops when that mass is
+// below 1e-30 of the squared Frobenius norm and fails (DLSA_ERR_NOT_CONVERGED) after 40 sweeps.  Measured on an MI355X
+// (tests/test_gpu_pinv_solve.py): separated spectra take 5-6 sweeps at p = 8, 7-8 at 33 .. 65, 9-10 at 130 and 12 at 257 and 500
+// (21 at p = 130 when graded over twelve decades); clustered ones -- two eigenvalues p / 2 fold each, +-1 -- 6 at p = 8, 15-17 at
+// 33, 18-20 at 64, 22-24 at 130, 22 at 257 and 26-28 at 500.  The iteration works on 2^-e S, max |a_ij| in [1, 2)
+// (jacobi_exponent), so the sums of squares of the stopping rule cannot leave the fp64 range whatever the scale of S.
 // Latency-bound and rarely taken (only when the Cholesky of the combine fails or is numerically rank-deficient).
 #include "common.h"
 #include "host_calls.h"
@@ -69,14 +74,32 @@ __global__ void jacobi_round_kernel(const double* __restrict__ Ain, const double
     Vout[(int64_t)ja * m + ib] = cb * v10 - sb * v11; Vout[(int64_t)ja * m + jb] = sb * v10 + cb * v11;
 }
 
-// A (m x m, zero padded) <- symmetrised S;  V <- I;  acc[0..2] <- 0
+// acc[3] <- max |S_ij| over the finite entries of the p x p block (acc[3] zeroed before; non-negative doubles order as integers)
+__global__ void jacobi_amax_kernel(const double* __restrict__ S, int64_t lds, int p, double* __restrict__ acc) {
+    double mx = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < (int64_t)p * p; e += (int64_t)gridDim.x * blockDim.x) {
+        const double v = fabs(S[(e / p) * lds + e % p]);
+        if (isfinite(v)) mx = fmax(mx, v);
+    }
+    mx = wave_allreduce_max(mx);
+    if ((threadIdx.x & 63) == 0 && mx > 0.0) atomicMax((unsigned long long*)(acc + 3), (unsigned long long)__double_as_longlong(mx));
+}
+
+// The binary exponent the iteration works at: A = 2^-e S has max |a_ij| in [1, 2).  lstsq is invariant under S -> c S, v -> c v, and
+// every step of the iteration is too (c, s come from a ratio) EXCEPT the sums of squares of the stopping rule, which underflow to
+// 0 <= 1e-30 * 0 ("settled" after one sweep) for entries below 1e-154 and overflow ("NaN in the system") above 1e+154.  A power
+// of two scales exactly, so results for ordinary magnitudes keep their bits.
+__device__ __forceinline__ int jacobi_exponent(const double* acc) { return acc[3] > 0.0 ? ilogb(acc[3]) : 0; }
+
+// A (m x m, zero padded) <- symmetrised 2^-e S;  V <- I;  acc[0..2] <- 0
 __global__ void jacobi_init_kernel(const double* __restrict__ S, int64_t lds, int p, int m, double* __restrict__ A,
                                    double* __restrict__ V, double* __restrict__ acc) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int ex = -jacobi_exponent(acc);
     if (e == 0) { acc[0] = 0.0; acc[1] = 0.0; acc[2] = 0.0; }
     if (e >= (int64_t)m * m) return;
     const int i = (int)(e / m), j = (int)(e % m);
-    A[e] = (i < p && j < p) ? 0.5 * (S[(int64_t)i * lds + j] + S[(int64_t)j * lds + i]) : 0.0;
+    A[e] = (i < p && j < p) ? 0.5 * (ldexp(S[(int64_t)i * lds + j], ex) + ldexp(S[(int64_t)j * lds + i], ex)) : 0.0;
     V[e] = i == j ? 1.0 : 0.0;
 }
 
@@ -97,10 +120,12 @@ __global__ void jacobi_offnorm_kernel(const double* __restrict__ A, int m, doubl
     }
 }
 
-// t_i = (v_i . rhs) / lambda_i for |lambda_i| > cut, else 0;  lam_out[i] = lambda_i;  one thread per eigenpair (coalesced in i)
+// t_i = (v_i . rhs) / lambda_i for |lambda_i| > cut, else 0;  lam_out[i] = lambda_i;  one thread per eigenpair (coalesced in i).
+// diag(A) holds 2^-e lambda (jacobi_exponent): the cut is relative, so it is taken there; lambda itself is scaled back, exactly.
+// rank[1] is set when a projection is not finite (V is: NaN/Inf in rhs).
 __global__ void pinv_project_kernel(const double* __restrict__ A, const double* __restrict__ V, int m, int p,
-                                    const double* __restrict__ rhs, double rcond, double* __restrict__ t,
-                                    double* __restrict__ lam_out, int* __restrict__ rank) {
+                                    const double* __restrict__ rhs, double rcond, const double* __restrict__ acc,
+                                    double* __restrict__ t, double* __restrict__ lam_out, int* __restrict__ rank) {
     __shared__ double lmax_s;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     // largest |eigenvalue| (every block recomputes it: m <= 2048 values)
@@ -113,13 +138,14 @@ __global__ void pinv_project_kernel(const double* __restrict__ A, const double* 
     __syncthreads();
     const double cut = rcond * lmax_s;
     if (i >= m) return;
-    const double lam = A[(int64_t)i * m + i];
+    const double lam_s = A[(int64_t)i * m + i], lam = ldexp(lam_s, jacobi_exponent(acc));
     double dot = 0.0;
     for (int r = 0; r < p; ++r) dot = fma(V[(int64_t)r * m + i], rhs[r], dot);
-    const bool keep = fabs(lam) > cut;
+    const bool keep = fabs(lam_s) > cut;
     t[i] = keep ? dot / lam : 0.0;
     lam_out[i] = lam;
     if (keep) atomicAdd(rank, 1);
+    if (!isfinite(dot)) rank[1] = 1;
 }
 
 // theta_r = sum_i V[r][i] t_i   (one wave per row)
@@ -149,9 +175,12 @@ static PinvLayout pinv_layout(int p) {
 
 size_t sym_pinv_workspace_bytes_impl(int p) { return pinv_layout(p).total; }
 
-// theta = pinv(S) v with the lstsq(rcond) cut; eig_host (nullable, p values) receives the eigenvalues, rank_host the rank
+// theta = pinv(S) v with the lstsq(rcond) cut; eig_host (nullable, p values) receives the eigenvalues, rank_host the rank,
+// sweeps_host the number of sweeps taken, V_out (nullable, device, p rows of pitch ldv) the eigenvectors as columns, in the order
+// of eig_host
 int sym_pinv_solve_impl(const double* S, int64_t lds, const double* v, int p, double rcond, double* theta,
-                        int* rank_host, double* eig_host, int* sweeps_host, void* ws, size_t ws_bytes, hipStream_t s) {
+                        int* rank_host, double* eig_host, int* sweeps_host, double* V_out, int64_t ldv, void* ws, size_t ws_bytes,
+                        hipStream_t s) {
     const PinvLayout l = pinv_layout(p);
     if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255)) {
         set_error("sym_pinv_solve: workspace %zu bytes needed (256-aligned), got %zu", l.total, ws_bytes);
@@ -166,6 +195,8 @@ int sym_pinv_solve_impl(const double* S, int64_t lds, const double* v, int p, do
     int* rank = (int*)(base + l.rank);
     const int m = l.m, half = m / 2;
     const int64_t mm = (int64_t)m * m;
+    DLSA_HIP_CHECK(hipMemsetAsync(acc, 0, 4 * sizeof(double), s));
+    hipLaunchKernelGGL(jacobi_amax_kernel, dim3((unsigned)std::min<int64_t>(256, ((int64_t)p * p + 255) / 256)), dim3(256), 0, s, S, lds, p, acc);
     hipLaunchKernelGGL(jacobi_init_kernel, dim3((unsigned)((mm + 255) / 256)), dim3(256), 0, s, S, lds, p, m, A[0], V[0], acc);
     int cur = 0, sweeps = 0;
     bool settled = m <= 1;
@@ -189,16 +220,19 @@ int sym_pinv_solve_impl(const double* S, int64_t lds, const double* v, int p, do
         set_error("sym_pinv_solve: the Jacobi iteration did not reach its off-diagonal target in %d sweeps (p = %d)", sweeps, p);
         return DLSA_ERR_NOT_CONVERGED;
     }
-    DLSA_HIP_CHECK(hipMemsetAsync(rank, 0, sizeof(int), s));
+    DLSA_HIP_CHECK(hipMemsetAsync(rank, 0, 2 * sizeof(int), s));
     hipLaunchKernelGGL(pinv_project_kernel, dim3((m + 255) / 256), dim3(256), 0, s, (const double*)A[cur], (const double*)V[cur], m, p, v,
-                       rcond, t, lam, rank);
+                       rcond, (const double*)acc, t, lam, rank);
     hipLaunchKernelGGL(pinv_expand_kernel, dim3((p + 3) / 4), dim3(256), 0, s, (const double*)V[cur], m, p, (const double*)t, theta);
     DLSA_HIP_CHECK(hipGetLastError());
-    int rk = 0;
-    DLSA_HIP_CHECK(hipMemcpyAsync(&rk, rank, sizeof(int), hipMemcpyDeviceToHost, s));
+    int rk[2] = {0, 0};
+    DLSA_HIP_CHECK(hipMemcpyAsync(rk, rank, sizeof(rk), hipMemcpyDeviceToHost, s));
     if (eig_host) DLSA_HIP_CHECK(hipMemcpyAsync(eig_host, lam, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (V_out) DLSA_HIP_CHECK(hipMemcpy2DAsync(V_out, (size_t)ldv * sizeof(double), V[cur], (size_t)m * sizeof(double), (size_t)p * sizeof(double),
+                                               (size_t)p, hipMemcpyDeviceToDevice, s));
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
-    if (rank_host) *rank_host = rk;
+    if (rk[1]) { set_error("sym_pinv_solve: NaN/Inf in the right-hand side"); return DLSA_ERR_NAN; }
+    if (rank_host) *rank_host = rk[0];
     if (sweeps_host) *sweeps_host = sweeps;
     return DLSA_OK;
 }
@@ -218,7 +252,16 @@ int dlsa_sym_pinv_solve_f64(const double* S, int64_t lds, const double* v, int p
     DLSA_REQUIRE(S && v && theta, "sym_pinv_solve: null argument");
     DLSA_REQUIRE(p > 0 && p <= 2048 && lds >= p, "sym_pinv_solve: bad shape p=%d lds=%lld", p, (long long)lds);
     if (!(rcond >= 0.0)) rcond = 2.220446049250313e-16 * p;          // lstsq(rcond=None): eps * max(M, N)
-    return sym_pinv_solve_impl(S, lds, v, p, rcond, theta, rank_host, eig_host, nullptr, ws, ws_bytes, (hipStream_t)stream);
+    return sym_pinv_solve_impl(S, lds, v, p, rcond, theta, rank_host, eig_host, nullptr, nullptr, 0, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int dlsa_sym_pinv_probe_f64(const double* S, int64_t lds, const double* v, int p, double rcond, double* theta, int* rank_host,
+                            double* eig_host, int* sweeps_host, double* V_out, int64_t ldv, void* ws, size_t ws_bytes, void* stream) {
+    using namespace dlsa;
+    DLSA_REQUIRE(S && v && theta && V_out, "sym_pinv_probe: null argument");
+    DLSA_REQUIRE(p > 0 && p <= 2048 && lds >= p && ldv >= p, "sym_pinv_probe: bad shape p=%d lds=%lld ldv=%lld", p, (long long)lds, (long long)ldv);
+    if (!(rcond >= 0.0)) rcond = 2.220446049250313e-16 * p;
+    return sym_pinv_solve_impl(S, lds, v, p, rcond, theta, rank_host, eig_host, sweeps_host, V_out, ldv, ws, ws_bytes, (hipStream_t)stream);
 }
 
 size_t dlsa_wls_solve_workspace_bytes(int p) {
@@ -250,7 +293,14 @@ int dlsa_wls_solve_f64(const double* S, int64_t lds, const double* v, int p, dou
     DLSA_HIP_CHECK(hipMemcpy2DAsync(dl.data(), sizeof(double), L, (size_t)(p + 1) * sizeof(double), sizeof(double), (size_t)p, hipMemcpyDeviceToHost, s));
     DLSA_HIP_CHECK(hipMemcpy2DAsync(ds.data(), sizeof(double), S, (size_t)(lds + 1) * sizeof(double), sizeof(double), (size_t)p, hipMemcpyDeviceToHost, s));
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
-    if (h[2] == 2.0) { set_error("wls_solve: NaN/Inf in the system"); return DLSA_ERR_NAN; }
+    if (h[2] == 2.0) {
+        // a non-finite pivot or solution: NaN/Inf in (S, v) -- or finite entries so large that the arithmetic which continues past
+        // a failed pivot overflowed.  v is looked at here; the spectral path looks at S itself and works at a scale of its own.
+        DLSA_HIP_CHECK(hipMemcpyAsync(dl.data(), v, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, s));
+        DLSA_HIP_CHECK(hipStreamSynchronize(s));
+        for (int i = 0; i < p; ++i)
+            if (!isfinite(dl[i])) { set_error("wls_solve: NaN/Inf in the system"); return DLSA_ERR_NAN; }
+    }
     bool full = (h[2] == 0.0);
     const double thresh = 8.0 * 2.220446049250313e-16 * p;
     double lmin = INFINITY, smax = 0.0;
@@ -266,7 +316,7 @@ int dlsa_wls_solve_f64(const double* S, int64_t lds, const double* v, int p, dou
     if (full && !(lmin > 2.220446049250313e-16 * p * smax)) full = false;
     if (full) { if (rank_host) *rank_host = p; return DLSA_OK; }
     // 2. rank-deficient (or indefinite): minimum-norm least-squares solution, lstsq(rcond=None) semantics
-    return sym_pinv_solve_impl(S, lds, v, p, 2.220446049250313e-16 * p, theta, rank_host, nullptr, nullptr, ws, ws_bytes, s);
+    return sym_pinv_solve_impl(S, lds, v, p, 2.220446049250313e-16 * p, theta, rank_host, nullptr, nullptr, nullptr, 0, ws, ws_bytes, s);
 }
 
 }  // extern "C"

@@ -1025,6 +1025,29 @@ def sym_pinv_solve(S, v, rcond=None):
     return theta, rank.value, list(eig)
 
 
+def sym_pinv_probe(S, v, p, lds, rcond=None, ldv=None):
+    """Test hook (dlsa_sym_pinv_probe_f64): sym_pinv_solve with the sweep count and the eigenvectors.  S is a flat fp64 device
+    buffer holding the p x p matrix at row pitch lds.  Returns (theta, rank, eigenvalues as a host list, sweeps, V) with V a
+    [p, ldv] device tensor whose column i (i < p) is the eigenvector of eigenvalue i; columns beyond p keep NaN."""
+    lib = _lib.load()
+    _require_gpu(S, v)
+    p, lds = int(p), int(lds)
+    ldv = p if ldv is None else int(ldv)
+    if p <= 0 or lds < p or ldv < p:
+        raise ValueError("sym_pinv_probe: bad shape p=%d lds=%d ldv=%d" % (p, lds, ldv))
+    for name, t, n in (("S", S, (p - 1) * lds + p), ("v", v, p)):
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < n:
+            raise ValueError("sym_pinv_probe: %s must be a contiguous float64 buffer of at least %d elements" % (name, n))
+    theta = torch.empty((p,), dtype=torch.float64, device=S.device)
+    V = torch.full((p, ldv), float("nan"), dtype=torch.float64, device=S.device)
+    ws = _workspace(lib.dlsa_sym_pinv_workspace_bytes(p), S.device)
+    rank, sweeps = ctypes.c_int(0), ctypes.c_int(-1)
+    eig = (ctypes.c_double * p)()
+    check(lib.dlsa_sym_pinv_probe_f64(_ptr(S), lds, _ptr(v), p, -1.0 if rcond is None else float(rcond), _ptr(theta),
+                                      ctypes.byref(rank), eig, ctypes.byref(sweeps), _ptr(V), ldv, _ptr(ws), ws.numel(), _stream()))
+    return theta, rank.value, list(eig), sweeps.value, V
+
+
 def lars_path(Sigma0, b0, intercept, n, type="lar", eps=2.220446049250313e-16, max_steps=None):
     """LARS / lasso path of the LSA objective on the device (dlsa/lsa.py:90-212).
     Returns dict of device tensors AIC, BIC [steps+1], beta [steps+1, m], beta0 [steps+1]."""

@@ -396,7 +396,9 @@ int dlsa_spd_solve_f64(const double* S, int64_t lds, const double* v, int p, dou
  * rank_host (nullable) receives the numerical rank (p for the SPD case).
  * dlsa_sym_pinv_solve_f64: parallel two-sided Jacobi eigendecomposition of the symmetric S (p <= 2048), then
  * theta = V diag(1 / lambda_i : |lambda_i| > rcond * max|lambda|) V' v.  rcond < 0 = eps * p (lstsq's rcond=None).
- * eig_host (nullable, p doubles, host) receives the eigenvalues (unordered). */
+ * eig_host (nullable, p doubles, host) receives the eigenvalues (unordered).  The iteration works on 2^-e S with max |S_ij| in
+ * [1, 2), so the result does not depend on the scale of (S, v) (the same bits for a power of two); NaN/Inf in S or in v is
+ * DLSA_ERR_NAN, 40 sweeps without reaching the off-diagonal target DLSA_ERR_NOT_CONVERGED. */
 size_t dlsa_wls_solve_workspace_bytes(int p);
 int dlsa_wls_solve_f64(const double* S, int64_t lds, const double* v, int p, double* theta, int* rank_host,
                        void* ws, size_t ws_bytes, void* stream);
@@ -588,6 +590,14 @@ size_t dlsa_newton_solve_probe_workspace_bytes(int route, int p, int count);
 int dlsa_newton_solve_probe_f64(int route, const double* S, int64_t lds, int p, int count, int64_t ss, const double* v,
                                 const double* v2, const double* ref, int64_t sv, double* x, double* M, int64_t sm,
                                 double* stats, int64_t st, const int* active, void* ws, size_t ws_bytes, void* stream);
+
+/* test hook: dlsa_sym_pinv_solve_f64 with the two things it keeps to itself.  The same call into the same code (no second path:
+ * theta, rank and eigenvalues are bit-equal to the solve entry's), and additionally sweeps_host (nullable) receives the number
+ * of Jacobi sweeps taken (the budget is 40: DLSA_ERR_NOT_CONVERGED beyond) and V_out (device, p rows of pitch ldv >= p) the
+ * eigenvectors as COLUMNS, column i belonging to eig_host[i].  Workspace: dlsa_sym_pinv_workspace_bytes.  (No reference
+ * counterpart: the decomposition inside numpy.linalg.lstsq, dlsa/dlsa.py:48-49.) */
+int dlsa_sym_pinv_probe_f64(const double* S, int64_t lds, const double* v, int p, double rcond, double* theta, int* rank_host,
+                            double* eig_host, int* sweeps_host, double* V_out, int64_t ldv, void* ws, size_t ws_bytes, void* stream);
 
 /* test hook: the safeguarded Newton loop of the Poisson, NB2 and Cox fits (the loop the fits run, with callables that read a
  * script instead of launching anything; no HIP call, no device).  policy: which family's rules (the table).

@@ -131,6 +131,25 @@ def test_newton_solve_probe_checks_its_arguments_without_a_gpu(lib):
     assert q(5, 500, 1) == 0 and q(0, 0, 1) == 0 and q(4, 100, 0) == 0
 
 
+def test_sym_pinv_probe_checks_its_arguments_without_a_gpu(lib):
+    """the spectral solve's probe refuses a null pointer, a bad shape or pitch and a bad workspace before any HIP call"""
+    from dlsa_amd import _lib
+    one = ctypes.c_void_p(256)                       # non-null, 256-aligned, never dereferenced: every call below is refused first
+    need = lib.dlsa_sym_pinv_workspace_bytes(4)
+
+    def probe(S=one, v=one, theta=one, V=one, p=4, lds=4, ldv=4, ws=one, ws_bytes=1 << 20):
+        return lib.dlsa_sym_pinv_probe_f64(S, lds, v, p, -1.0, theta, None, None, None, V, ldv, ws, ws_bytes, None)
+
+    for arg in ("S", "v", "theta", "V"):
+        assert probe(**{arg: None}) == 1 and "null" in _lib.last_error()
+    assert probe(lds=3) == 1 and "lds=3" in _lib.last_error()
+    assert probe(ldv=3) == 1 and "ldv=3" in _lib.last_error()
+    assert probe(p=0) == 1 and probe(p=2049, lds=2049, ldv=2049) == 1 and "p=2049" in _lib.last_error()
+    assert need >= 4 * 4 * 4 * 8 and need % 256 == 0
+    assert probe(ws_bytes=need - 1) == 3 and probe(ws=ctypes.c_void_p(264)) == 3 and probe(ws=None) == 3
+    assert "workspace" in _lib.last_error()
+
+
 def test_engine_refuses_cpu_tensors():
     import torch
     from dlsa_amd import engine
