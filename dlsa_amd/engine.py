@@ -367,7 +367,8 @@ def newton_wide_pass(X, y, beta, fit_intercept=False, want_w=False):
     _require_gpu(X, y, beta)
     _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta")
     n, p = X.shape
-    pe = p + (1 if fit_intercept else 0)
+    icpt = 1 if fit_intercept else 0
+    pe = p + icpt
     if y.numel() != n or beta.numel() != pe:
         raise ValueError("newton_wide_pass: y must have n = %d and beta %d elements" % (n, pe))
     dev = X.device
@@ -375,8 +376,8 @@ def newton_wide_pass(X, y, beta, fit_intercept=False, want_w=False):
     g = torch.empty((pe,), dtype=torch.float64, device=dev)
     ll = torch.empty((1,), dtype=torch.float64, device=dev)
     w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
-    ws = _workspace(lib.dlsa_newton_wide_workspace_bytes(n, p, 1 if fit_intercept else 0), dev)
-    check(lib.dlsa_newton_wide_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(beta), n, p, 1 if fit_intercept else 0, _ptr(w), _ptr(g),
+    ws = _workspace(lib.dlsa_newton_wide_workspace_bytes(n, p, icpt), dev)
+    check(lib.dlsa_newton_wide_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(beta), n, p, icpt, _ptr(w), _ptr(g),
                                         _ptr(ll), _ptr(H), pe, _ptr(ws), ws.numel(), _stream()))
     return H, g, ll, w
 
@@ -603,6 +604,91 @@ def irls_last_fit_path():
     return int(_lib.load().dlsa_irls_last_fit_path())
 
 
+# Codes a fit returns after it has written every block (include/dlsa_hip.h): DLSA_OK, and the soft failures DLSA_ERR_NOT_SPD (4),
+# DLSA_ERR_NOT_CONVERGED (5) and DLSA_ERR_NAN (6), which the per-partition `status` list names partition by partition.
+FIT_WROTE_BLOCKS = (0, 4, 5, 6)
+
+
+def _i64(values):
+    return (ctypes.c_int64 * len(values))(*values)
+
+
+def _strided_partitions(who, part_first, part_rows, row_step, n):
+    """Partitions given as (first row, rows, common row step) of n rows, checked.  Returns (K, step, the largest partition's rows,
+    part_first and part_rows as int64 arrays for the C ABI)."""
+    first, rows = [int(v) for v in part_first], [int(v) for v in part_rows]
+    K, step = len(first), int(row_step)
+    if len(rows) != K or K == 0 or step < 1:
+        raise ValueError("%s: part_first / part_rows must have K >= 1 entries each, row_step >= 1" % who)
+    for f, r in zip(first, rows):
+        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
+            raise ValueError("%s: partition outside the %d rows" % (who, n))
+    return K, step, max(rows), _i64(first), _i64(rows)
+
+
+def _offset_partitions(who, part_offsets, n, ascending_from_zero=False):
+    """Partitions given as K + 1 offsets into n rows (or into an order of n entries), checked: the two ends within 0 .. n, and with
+    ascending_from_zero (the Cox fit, whose segments tile the order) a start at 0 and no decreasing step as well.  Returns (K, the
+    largest partition's rows, the offsets as an int64 array for the C ABI)."""
+    offs = [int(v) for v in part_offsets]
+    K = len(offs) - 1
+    if ascending_from_zero:
+        if K < 1 or offs[0] != 0 or offs[-1] > n or any(offs[k + 1] < offs[k] for k in range(K)):
+            raise ValueError("%s: part_offsets must be K+1 non-decreasing ints from 0 within the order" % who)
+    elif offs[0] < 0 or offs[-1] > n or K < 1:
+        raise ValueError("%s: part_offsets out of range" % who)
+    return K, max(offs[k + 1] - offs[k] for k in range(K)), _i64(offs)
+
+
+class _FitOut:
+    """What a per-partition fit of K partitions with pe coefficients writes: coef / Sig_invMcoef [K, pe] and Sig_inv [K, pe, pe] on the
+    device, n_iter / status / loglik on the host, and with `dispersion` (NB2) alpha / alpha_info / pearson.  `args` is the run of
+    output arguments every dlsa_*_fit_* entry takes, in the C ABI's order; result(rc) is the wrappers' result dict."""
+
+    def __init__(self, K, pe, device, dispersion=False):
+        self.coef = torch.empty((K, pe), dtype=torch.float64, device=device)
+        self.smc = torch.empty((K, pe), dtype=torch.float64, device=device)
+        self.sig = torch.empty((K, pe, pe), dtype=torch.float64, device=device)
+        self.host = {"n_iter": (ctypes.c_int * K)(), "status": (ctypes.c_int * K)(), "loglik": (ctypes.c_double * K)()}
+        if dispersion:
+            self.host.update({k: (ctypes.c_double * K)() for k in ("alpha", "alpha_info", "pearson")})
+        self.args = (_ptr(self.coef), _ptr(self.sig), _ptr(self.smc)) + tuple(self.host.values())
+
+    def result(self, rc):
+        if rc not in FIT_WROTE_BLOCKS:
+            check(rc)
+        return {"coef": self.coef, "Sig_invMcoef": self.smc, "Sig_inv": self.sig, **{k: list(v) for k, v in self.host.items()}, "rc": rc}
+
+
+def _pass_out(pe, n, device, want_H, want_w, negbin=False, want_theta=False):
+    """The outputs of one pass at a fixed beta, in the order the pass wrappers return them: (H [pe, pe] or None, g [pe], loglik [1],
+    w [n] or None) and for NB2 (..., mu [n] or None -- with want_w --, theta_terms [3] or None)."""
+    def new(shape, want=True):
+        return torch.empty(shape, dtype=torch.float64, device=device) if want else None
+    out = (new((pe, pe), want_H), new((pe,)), new((1,)), new((n,), want_w))
+    return out + (new((n,), want_w), new((3,), want_theta)) if negbin else out
+
+
+def _alpha_positive(who, alpha, other):
+    """The dispersion of an NB2 pass: a positive finite float."""
+    alpha = float(alpha)
+    if not 0.0 < alpha < float("inf"):
+        raise ValueError("%s: alpha must be positive and finite (alpha = 0 is %s)" % (who, other))
+    return alpha
+
+
+def _alpha_fixed(who, alpha, other):
+    """The dispersion argument of an NB2 fit as the C ABI takes it: 0.0 for None (estimate it), else a positive finite float."""
+    if alpha is None:
+        return 0.0
+    alpha = float(alpha)
+    if alpha == 0.0:
+        raise ValueError("%s: alpha = 0 is the Poisson model: use %s" % (who, other))
+    if not 0.0 < alpha < float("inf"):
+        raise ValueError("%s: a fixed alpha must be positive and finite" % who)
+    return alpha
+
+
 def irls_fit_ex(X, y, part_first, part_rows, row_step=1, fit_intercept=False, tol=1e-13, max_iter=100):
     """irls_fit without copies of the shard: partition k = rows part_first[k] + j * row_step, j < part_rows[k] (a strided
     view: partition_id = i % K is part_first = 0..K-1, row_step = K), and an IMPLICIT intercept column (fit_intercept:
@@ -613,29 +699,13 @@ def irls_fit_ex(X, y, part_first, part_rows, row_step=1, fit_intercept=False, to
     n, p = X.shape
     if y.numel() != n:
         raise ValueError("irls_fit_ex: y must have n = %d elements" % n)
-    first = [int(v) for v in part_first]
-    rows = [int(v) for v in part_rows]
-    K, step = len(first), int(row_step)
-    if len(rows) != K or K == 0 or step < 1:
-        raise ValueError("irls_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
-    for f, r in zip(first, rows):
-        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
-            raise ValueError("irls_fit_ex: partition outside the %d rows of X" % n)
-    pe = p + (1 if fit_intercept else 0)
-    dev = X.device
-    coef = torch.empty((K, pe), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, pe), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, pe, pe), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_irls_ex_workspace_bytes(max(rows), p, 1 if fit_intercept else 0, step), dev)
-    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    rc = lib.dlsa_irls_fit_ex_f64(_ptr(X), _rowmajor(X), _ptr(y), c_first, c_rows, step, K, p, 1 if fit_intercept else 0,
-                                  tol, max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(),
-                                  _stream())
-    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "rc": rc}
+    K, step, max_rows, c_first, c_rows = _strided_partitions("irls_fit_ex", part_first, part_rows, row_step, n)
+    icpt = 1 if fit_intercept else 0
+    out = _FitOut(K, p + icpt, X.device)
+    ws = _workspace(lib.dlsa_irls_ex_workspace_bytes(max_rows, p, icpt, step), X.device)
+    rc = lib.dlsa_irls_fit_ex_f64(_ptr(X), _rowmajor(X), _ptr(y), c_first, c_rows, step, K, p, icpt, tol, max_iter, *out.args,
+                                  _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def irls_fit(X, y, part_offsets, tol=1e-13, max_iter=100):
@@ -648,28 +718,11 @@ def irls_fit(X, y, part_offsets, tol=1e-13, max_iter=100):
     n, p = X.shape
     if y.numel() != n:
         raise ValueError("irls_fit: y must have n = %d elements" % n)
-    offs = [int(v) for v in part_offsets]
-    K = len(offs) - 1
-    if offs[0] < 0 or offs[-1] > n:
-        raise ValueError("part_offsets out of range")
-    dev = X.device
-    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    max_rows = max(offs[k + 1] - offs[k] for k in range(K))
-    nb = lib.dlsa_irls_workspace_bytes(max_rows, p)
-    ws = _workspace(nb, dev)
-    c_offs = (ctypes.c_int64 * (K + 1))(*offs)
-    n_iter = (ctypes.c_int * K)()
-    status = (ctypes.c_int * K)()
-    ll = (ctypes.c_double * K)()
-    rc = lib.dlsa_irls_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), c_offs, K, p, tol, max_iter,
-                               _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll,
-                               _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter),
-            "status": list(status), "loglik": list(ll), "rc": rc}
+    K, max_rows, c_offs = _offset_partitions("irls_fit", part_offsets, n)
+    out = _FitOut(K, p, X.device)
+    ws = _workspace(lib.dlsa_irls_workspace_bytes(max_rows, p), X.device)
+    rc = lib.dlsa_irls_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), c_offs, K, p, tol, max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def _cox_args(X, time, event, order):
@@ -736,15 +789,11 @@ def cox_pass(X, time, event, order, beta, want_w=False, ties="breslow", strata=N
     m = order.numel()
     if m < 1 or beta.numel() != p:
         raise ValueError("cox_pass: need at least one row and beta with p = %d entries" % p)
-    dev = X.device
-    H = torch.empty((p, p), dtype=torch.float64, device=dev)
-    g = torch.empty((p,), dtype=torch.float64, device=dev)
-    ll = torch.empty((1,), dtype=torch.float64, device=dev)
-    w = torch.empty((m,), dtype=torch.float64, device=dev) if want_w else None
-    ws = _workspace(lib.dlsa_cox_strata_workspace_bytes(m, p, code, 0 if strata is None else 1), dev)
+    H, g, ll, w = out = _pass_out(p, m, X.device, True, want_w)
+    ws = _workspace(lib.dlsa_cox_strata_workspace_bytes(m, p, code, 0 if strata is None else 1), X.device)
     check(lib.dlsa_cox_pass_strata_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(strata), _ptr(order), m, p, code, _ptr(beta),
                                        _ptr(H), p, _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
-    return H, g, ll, w
+    return out
 
 
 def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100, ties="breslow", strata=None):
@@ -756,24 +805,12 @@ def cox_fit(X, time, event, order, part_offsets, tol=1e-13, max_iter=100, ties="
     lib = _lib.load()
     p = _cox_args(X, time, event, order)
     strata = cox_strata_codes(strata, X.device)
-    offs = [int(v) for v in part_offsets]
-    K = len(offs) - 1
-    if K < 1 or offs[0] != 0 or offs[-1] > order.numel() or any(offs[k + 1] < offs[k] for k in range(K)):
-        raise ValueError("cox_fit: part_offsets must be K+1 non-decreasing ints from 0 within the order")
-    dev = X.device
-    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_cox_strata_workspace_bytes(max(offs[k + 1] - offs[k] for k in range(K)), p, code, 0 if strata is None else 1),
-                    dev)
-    c_offs = (ctypes.c_int64 * (K + 1))(*offs)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
+    K, max_rows, c_offs = _offset_partitions("cox_fit", part_offsets, order.numel(), ascending_from_zero=True)
+    out = _FitOut(K, p, X.device)
+    ws = _workspace(lib.dlsa_cox_strata_workspace_bytes(max_rows, p, code, 0 if strata is None else 1), X.device)
     rc = lib.dlsa_cox_fit_strata_f64(_ptr(X), _rowmajor(X), _ptr(time), _ptr(event), _ptr(strata), _ptr(order), c_offs, K, p, code, tol,
-                                     max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "rc": rc}
+                                     max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def poisson_pass(X, y, beta, offset=None, fit_intercept=False, want_H=True, want_w=False):
@@ -784,18 +821,15 @@ def poisson_pass(X, y, beta, offset=None, fit_intercept=False, want_H=True, want
     _require_gpu(X, y, beta, offset)
     _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
     n, p = X.shape
-    pe = p + (1 if fit_intercept else 0)
+    icpt = 1 if fit_intercept else 0
+    pe = p + icpt
     if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
         raise ValueError("poisson_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
-    dev = X.device
-    H = torch.empty((pe, pe), dtype=torch.float64, device=dev) if want_H else None
-    g = torch.empty((pe,), dtype=torch.float64, device=dev)
-    ll = torch.empty((1,), dtype=torch.float64, device=dev)
-    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
-    ws = _workspace(lib.dlsa_poisson_workspace_bytes(n, p, 1 if fit_intercept else 0, 1), dev)
-    check(lib.dlsa_poisson_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), n, p, 1 if fit_intercept else 0,
-                                    _ptr(H), pe, _ptr(g), _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
-    return H, g, ll, w
+    H, g, ll, w = out = _pass_out(pe, n, X.device, want_H, want_w)
+    ws = _workspace(lib.dlsa_poisson_workspace_bytes(n, p, icpt, 1), X.device)
+    check(lib.dlsa_poisson_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), n, p, icpt, _ptr(H), pe, _ptr(g), _ptr(ll),
+                                    _ptr(w), _ptr(ws), ws.numel(), _stream()))
+    return out
 
 
 def poisson_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, tol=1e-13, max_iter=100):
@@ -808,28 +842,13 @@ def poisson_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_int
     n, p = X.shape
     if y.numel() != n or (offset is not None and offset.numel() != n):
         raise ValueError("poisson_fit_ex: y and offset must have n = %d elements" % n)
-    first = [int(v) for v in part_first]
-    rows = [int(v) for v in part_rows]
-    K, step = len(first), int(row_step)
-    if len(rows) != K or K == 0 or step < 1:
-        raise ValueError("poisson_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
-    for f, r in zip(first, rows):
-        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
-            raise ValueError("poisson_fit_ex: partition outside the %d rows of X" % n)
-    pe = p + (1 if fit_intercept else 0)
-    dev = X.device
-    coef = torch.empty((K, pe), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, pe), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, pe, pe), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_poisson_workspace_bytes(max(rows), p, 1 if fit_intercept else 0, step), dev)
-    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    rc = lib.dlsa_poisson_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, 1 if fit_intercept else 0,
-                                  tol, max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "rc": rc}
+    K, step, max_rows, c_first, c_rows = _strided_partitions("poisson_fit_ex", part_first, part_rows, row_step, n)
+    icpt = 1 if fit_intercept else 0
+    out = _FitOut(K, p + icpt, X.device)
+    ws = _workspace(lib.dlsa_poisson_workspace_bytes(max_rows, p, icpt, step), X.device)
+    rc = lib.dlsa_poisson_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, tol, max_iter, *out.args,
+                                  _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def negbin_pass(X, y, beta, alpha, offset=None, fit_intercept=False, want_H=True, want_w=False, want_theta=False):
@@ -841,23 +860,16 @@ def negbin_pass(X, y, beta, alpha, offset=None, fit_intercept=False, want_H=True
     _require_gpu(X, y, beta, offset)
     _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
     n, p = X.shape
-    pe = p + (1 if fit_intercept else 0)
+    icpt = 1 if fit_intercept else 0
+    pe = p + icpt
     if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
         raise ValueError("negbin_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
-    alpha = float(alpha)
-    if not (alpha > 0.0 and alpha < float("inf")):
-        raise ValueError("negbin_pass: alpha must be positive and finite (alpha = 0 is poisson_pass)")
-    dev = X.device
-    H = torch.empty((pe, pe), dtype=torch.float64, device=dev) if want_H else None
-    g = torch.empty((pe,), dtype=torch.float64, device=dev)
-    ll = torch.empty((1,), dtype=torch.float64, device=dev)
-    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
-    mu = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
-    tt = torch.empty((3,), dtype=torch.float64, device=dev) if want_theta else None
-    ws = _workspace(lib.dlsa_negbin_workspace_bytes(n, p, 1 if fit_intercept else 0, 1), dev)
-    check(lib.dlsa_negbin_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), alpha, n, p, 1 if fit_intercept else 0,
-                                   _ptr(H), pe, _ptr(g), _ptr(ll), _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
-    return H, g, ll, w, mu, tt
+    alpha = _alpha_positive("negbin_pass", alpha, "poisson_pass")
+    H, g, ll, w, mu, tt = out = _pass_out(pe, n, X.device, want_H, want_w, negbin=True, want_theta=want_theta)
+    ws = _workspace(lib.dlsa_negbin_workspace_bytes(n, p, icpt, 1), X.device)
+    check(lib.dlsa_negbin_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), alpha, n, p, icpt, _ptr(H), pe, _ptr(g), _ptr(ll),
+                                   _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
+    return out
 
 
 def negbin_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, alpha=None, tol=1e-13, max_iter=100):
@@ -871,36 +883,14 @@ def negbin_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_inte
     n, p = X.shape
     if y.numel() != n or (offset is not None and offset.numel() != n):
         raise ValueError("negbin_fit_ex: y and offset must have n = %d elements" % n)
-    if alpha is not None:
-        alpha = float(alpha)
-        if alpha == 0.0:
-            raise ValueError("negbin_fit_ex: alpha = 0 is the Poisson model: use poisson_fit_ex")
-        if not (alpha > 0.0 and alpha < float("inf")):
-            raise ValueError("negbin_fit_ex: a fixed alpha must be positive and finite")
-    first = [int(v) for v in part_first]
-    rows = [int(v) for v in part_rows]
-    K, step = len(first), int(row_step)
-    if len(rows) != K or K == 0 or step < 1:
-        raise ValueError("negbin_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
-    for f, r in zip(first, rows):
-        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
-            raise ValueError("negbin_fit_ex: partition outside the %d rows of X" % n)
-    pe = p + (1 if fit_intercept else 0)
-    dev = X.device
-    coef = torch.empty((K, pe), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, pe), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, pe, pe), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_negbin_workspace_bytes(max(rows), p, 1 if fit_intercept else 0, step), dev)
-    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    al, info, pear = (ctypes.c_double * K)(), (ctypes.c_double * K)(), (ctypes.c_double * K)()
-    rc = lib.dlsa_negbin_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, 1 if fit_intercept else 0,
-                                 alpha if alpha is not None else 0.0, tol, max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll,
-                                 al, info, pear, _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "alpha": list(al), "alpha_info": list(info), "pearson": list(pear), "rc": rc}
+    alpha = _alpha_fixed("negbin_fit_ex", alpha, "poisson_fit_ex")
+    K, step, max_rows, c_first, c_rows = _strided_partitions("negbin_fit_ex", part_first, part_rows, row_step, n)
+    icpt = 1 if fit_intercept else 0
+    out = _FitOut(K, p + icpt, X.device, dispersion=True)
+    ws = _workspace(lib.dlsa_negbin_workspace_bytes(max_rows, p, icpt, step), X.device)
+    rc = lib.dlsa_negbin_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, alpha, tol, max_iter,
+                                 *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def negbin_special(theta, y):
@@ -1152,26 +1142,12 @@ def onehot_irls_fit(plan, num, codes, y, part_offsets, tol=1e-13, max_iter=100):
     lib = _lib.load()
     _require_gpu(y)
     _f64(y, "y")
-    p = plan.p
-    offs = [int(v) for v in part_offsets]
-    K = len(offs) - 1
-    if offs[0] < 0 or offs[-1] > y.numel():
-        raise ValueError("part_offsets out of range")
-    dev = y.device
-    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    max_rows = max(offs[k + 1] - offs[k] for k in range(K))
-    ws = _workspace(lib.dlsa_onehot_irls_workspace_bytes(plan._h, max_rows), dev)
-    c_offs = (ctypes.c_int64 * (K + 1))(*offs)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
-    rc = lib.dlsa_onehot_irls_fit_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), c_offs, K, tol, max_iter, _ptr(coef), _ptr(sig),
-                                      _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "rc": rc}
+    K, max_rows, c_offs = _offset_partitions("onehot_irls_fit", part_offsets, y.numel())
+    out = _FitOut(K, plan.p, y.device)
+    ws = _workspace(lib.dlsa_onehot_irls_workspace_bytes(plan._h, max_rows), y.device)
+    rc = lib.dlsa_onehot_irls_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), c_offs, K, tol, max_iter, *out.args,
+                                      _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def onehot_irls_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, tol=1e-13, max_iter=100):
@@ -1180,28 +1156,12 @@ def onehot_irls_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, t
     lib = _lib.load()
     _require_gpu(y)
     _f64(y, "y")
-    p = plan.p
-    first, rows = [int(v) for v in part_first], [int(v) for v in part_rows]
-    K, step, n = len(first), int(row_step), y.numel()
-    if len(rows) != K or K == 0 or step < 1:
-        raise ValueError("onehot_irls_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
-    for f, r in zip(first, rows):
-        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
-            raise ValueError("onehot_irls_fit_ex: partition outside the %d rows" % n)
-    dev = y.device
-    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_onehot_irls_ex_workspace_bytes(plan._h, max(rows), step), dev)
-    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
-    rc = lib.dlsa_onehot_irls_fit_ex_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), c_first, c_rows, step, K, tol, max_iter, _ptr(coef),
-                                         _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "rc": rc}
+    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_irls_fit_ex", part_first, part_rows, row_step, y.numel())
+    out = _FitOut(K, plan.p, y.device)
+    ws = _workspace(lib.dlsa_onehot_irls_ex_workspace_bytes(plan._h, max_rows, step), y.device)
+    rc = lib.dlsa_onehot_irls_fit_ex_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), c_first, c_rows, step, K, tol, max_iter, *out.args,
+                                         _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def _oh_poisson_rows(plan, num, codes, y, offset, who):
@@ -1226,16 +1186,11 @@ def onehot_poisson_pass(plan, num, codes, y, beta, offset=None, want_H=True, wan
     p = plan.p
     if n < 1 or beta.numel() != p:
         raise ValueError("onehot_poisson_pass: need n >= 1 rows and beta with %d elements" % p)
-    dev = y.device
-    H = torch.empty((p, p), dtype=torch.float64, device=dev) if want_H else None
-    g = torch.empty((p,), dtype=torch.float64, device=dev)
-    ll = torch.empty((1,), dtype=torch.float64, device=dev)
-    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
-    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, n, 1), dev)
-    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
-    check(lib.dlsa_onehot_poisson_pass_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), _ptr(beta), n, _ptr(H), p, _ptr(g),
+    H, g, ll, w = out = _pass_out(p, n, y.device, want_H, want_w)
+    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, n, 1), y.device)
+    check(lib.dlsa_onehot_poisson_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), n, _ptr(H), p, _ptr(g),
                                            _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
-    return H, g, ll, w
+    return out
 
 
 def onehot_poisson_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, tol=1e-13, max_iter=100):
@@ -1244,28 +1199,12 @@ def onehot_poisson_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1
     partition are gathered.  Same result dict as poisson_fit_ex, plan.p columns in the plan's order."""
     lib = _lib.load()
     n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_poisson_fit_ex")
-    p = plan.p
-    first, rows = [int(v) for v in part_first], [int(v) for v in part_rows]
-    K, step = len(first), int(row_step)
-    if len(rows) != K or K == 0 or step < 1:
-        raise ValueError("onehot_poisson_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
-    for f, r in zip(first, rows):
-        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
-            raise ValueError("onehot_poisson_fit_ex: partition outside the %d rows" % n)
-    dev = y.device
-    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, max(rows), step), dev)
-    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
-    rc = lib.dlsa_onehot_poisson_fit_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), c_first, c_rows, step, K, tol, max_iter,
-                                         _ptr(coef), _ptr(sig), _ptr(smc), n_iter, status, ll, _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "rc": rc}
+    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_poisson_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, plan.p, y.device)
+    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, max_rows, step), y.device)
+    rc = lib.dlsa_onehot_poisson_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, tol, max_iter,
+                                         *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def onehot_negbin_pass(plan, num, codes, y, beta, alpha, offset=None, want_H=True, want_w=False, want_theta=False):
@@ -1280,21 +1219,12 @@ def onehot_negbin_pass(plan, num, codes, y, beta, alpha, offset=None, want_H=Tru
     p = plan.p
     if n < 1 or beta.numel() != p:
         raise ValueError("onehot_negbin_pass: need n >= 1 rows and beta with %d elements" % p)
-    alpha = float(alpha)
-    if not (alpha > 0.0 and alpha < float("inf")):
-        raise ValueError("onehot_negbin_pass: alpha must be positive and finite (alpha = 0 is onehot_poisson_pass)")
-    dev = y.device
-    H = torch.empty((p, p), dtype=torch.float64, device=dev) if want_H else None
-    g = torch.empty((p,), dtype=torch.float64, device=dev)
-    ll = torch.empty((1,), dtype=torch.float64, device=dev)
-    w = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
-    mu = torch.empty((n,), dtype=torch.float64, device=dev) if want_w else None
-    tt = torch.empty((3,), dtype=torch.float64, device=dev) if want_theta else None
-    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, n, 1), dev)
-    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
-    check(lib.dlsa_onehot_negbin_pass_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), _ptr(beta), alpha, n, _ptr(H), p, _ptr(g),
-                                          _ptr(ll), _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
-    return H, g, ll, w, mu, tt
+    alpha = _alpha_positive("onehot_negbin_pass", alpha, "onehot_poisson_pass")
+    H, g, ll, w, mu, tt = out = _pass_out(p, n, y.device, want_H, want_w, negbin=True, want_theta=want_theta)
+    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, n, 1), y.device)
+    check(lib.dlsa_onehot_negbin_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), alpha, n, _ptr(H), p,
+                                          _ptr(g), _ptr(ll), _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
+    return out
 
 
 def onehot_negbin_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, alpha=None, tol=1e-13, max_iter=100):
@@ -1302,36 +1232,13 @@ def onehot_negbin_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1,
     onehot_poisson_fit_ex, alpha as negbin_fit_ex.  Same result dict as negbin_fit_ex, plan.p columns in the plan's order."""
     lib = _lib.load()
     n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_negbin_fit_ex")
-    p = plan.p
-    if alpha is not None:
-        alpha = float(alpha)
-        if alpha == 0.0:
-            raise ValueError("onehot_negbin_fit_ex: alpha = 0 is the Poisson model: use onehot_poisson_fit_ex")
-        if not (alpha > 0.0 and alpha < float("inf")):
-            raise ValueError("onehot_negbin_fit_ex: a fixed alpha must be positive and finite")
-    first, rows = [int(v) for v in part_first], [int(v) for v in part_rows]
-    K, step = len(first), int(row_step)
-    if len(rows) != K or K == 0 or step < 1:
-        raise ValueError("onehot_negbin_fit_ex: part_first / part_rows must have K >= 1 entries each, row_step >= 1")
-    for f, r in zip(first, rows):
-        if f < 0 or r < 0 or (r > 0 and f + (r - 1) * step >= n):
-            raise ValueError("onehot_negbin_fit_ex: partition outside the %d rows" % n)
-    dev = y.device
-    coef = torch.empty((K, p), dtype=torch.float64, device=dev)
-    smc = torch.empty((K, p), dtype=torch.float64, device=dev)
-    sig = torch.empty((K, p, p), dtype=torch.float64, device=dev)
-    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, max(rows), step), dev)
-    c_first, c_rows = (ctypes.c_int64 * K)(*first), (ctypes.c_int64 * K)(*rows)
-    n_iter, status, ll = (ctypes.c_int * K)(), (ctypes.c_int * K)(), (ctypes.c_double * K)()
-    al, info, pear = (ctypes.c_double * K)(), (ctypes.c_double * K)(), (ctypes.c_double * K)()
-    pn, ldn, pc, ldc = _oh_args(plan, num, codes)
-    rc = lib.dlsa_onehot_negbin_fit_f64(plan._h, pn, ldn, pc, ldc, _ptr(y), _ptr(offset), c_first, c_rows, step, K,
-                                        alpha if alpha is not None else 0.0, tol, max_iter, _ptr(coef), _ptr(sig), _ptr(smc), n_iter,
-                                        status, ll, al, info, pear, _ptr(ws), ws.numel(), _stream())
-    if rc not in (0, 4, 5, 6):     # per-partition soft failures are reported through `status`
-        check(rc)
-    return {"coef": coef, "Sig_invMcoef": smc, "Sig_inv": sig, "n_iter": list(n_iter), "status": list(status),
-            "loglik": list(ll), "alpha": list(al), "alpha_info": list(info), "pearson": list(pear), "rc": rc}
+    alpha = _alpha_fixed("onehot_negbin_fit_ex", alpha, "onehot_poisson_fit_ex")
+    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_negbin_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, plan.p, y.device, dispersion=True)
+    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, max_rows, step), y.device)
+    rc = lib.dlsa_onehot_negbin_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, alpha, tol,
+                                        max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 class RcclComm:

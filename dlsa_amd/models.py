@@ -54,6 +54,76 @@ class MappedBlocks:
         return pd.concat([self.block_frame(k) for k in range(self.coef.shape[0])], ignore_index=True)
 
 
+def _partitions(n, partition_num, part_offsets):
+    """The partitions of n rows as (first rows, row counts, common row step), the form the engine's fits take -- strided views,
+    nothing is gathered: `part_offsets` (K+1 ints) gives contiguous row ranges, else partition_id = i % partition_num (models.py:33;
+    None or 0: one partition) gives the rows k, k + K, ..."""
+    if part_offsets is None:
+        K = int(partition_num) if partition_num else 1
+        return list(range(K)), [len(range(k, n, K)) for k in range(K)], K
+    offs = [int(v) for v in part_offsets]
+    return offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+
+
+def _column_names(names, p, fit_intercept):
+    """The result's column names: `names` (default x0 .. x{p-1}), `intercept` first when the fit carries one."""
+    if names is None:
+        names = ["x" + str(i) for i in range(p)]
+    return (["intercept"] if fit_intercept else []) + list(names)
+
+
+def _blocks(r, names, n):
+    """MappedBlocks of an engine fit's result dict (the NB2 fits' dispersion lists go to `extra`)."""
+    extra = {k: r[k] for k in ("alpha", "alpha_info", "pearson")} if "alpha" in r else None
+    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n,
+                        extra=extra)
+
+
+def _fit_design(onehot_fit, dense_fit, num, codes, y, spec, partition_num, part_offsets, structured, **fit_args):
+    """The body of the fit_*_design functions: the family's structured engine fit on the raw columns when the design qualifies,
+    else its dense fit on the matrix the design kernel builds once; the same strided partitions either way."""
+    n = y.numel()
+    first, rows, step = _partitions(n, partition_num, part_offsets)
+    plan = spec.onehot_plan() if structured else None
+    if plan is not None:
+        r = onehot_fit(plan, engine.row_major(num) if num is not None else None, engine.row_major(codes) if codes is not None else None,
+                       y, first, rows, row_step=step, **fit_args)
+    else:
+        X, _ = spec.build(num, codes)
+        r = dense_fit(X, y, first, rows, row_step=step, **fit_args)
+    return _blocks(r, spec.names, n)
+
+
+def _to_device(sample_df, name):
+    """A frame's column as an fp64 device vector (None for no column)."""
+    return None if name is None else torch.from_numpy(np.ascontiguousarray(sample_df[name].to_numpy(dtype=np.float64))).cuda()
+
+
+def _zero_block(names):
+    """The all-zero block of a chunk that is skipped (models.py:84-91)."""
+    return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+
+
+def _warn_missing_levels(missing, rows, names, fit_intercept, skip):
+    """The reference's warning for a chunk that lacks expected dummy levels (models.py:80-91 / :187-194)."""
+    shape = (rows, len(names) - (1 if fit_intercept else 0) - len(missing))
+    warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape)
+                  + ("Skip modeling this part of data." if skip else ""))
+
+
+def _first_block_frame(mb, who=None, not_pd="information matrix not positive definite (collinear design)", hint=""):
+    """The frame of a one-partition map step, with the frame-level models' warnings: `who`'s soft failures by `status`, and the
+    reference's NA warning (models.py:144-145)."""
+    if who is not None and mb.status[0] == 1:
+        warnings.warn("%s: Newton iterations did not converge (max_iter reached%s)" % (who, hint))
+    elif who is not None and mb.status[0] == 2:
+        warnings.warn("%s: %s" % (who, not_pd))
+    out = mb.block_frame(0)
+    if out.isna().values.any():
+        warnings.warn("NAs appear in the final output")
+    return out
+
+
 def simulate_logistic(sample_size, p, partition_method, partition_num, seed=20260101, kind="uniform"):
     """models.py:6-40 with a seeded counter RNG on the GPU: features ~ U(-0.5,0.5) (:22), beta =
     ones on the first int(0.4p) coordinates (:12,18-19), label ~ Bernoulli(sigmoid(x.beta)) (:23,30),
@@ -79,13 +149,10 @@ def _device_design(sample_df, Y_name, fit_intercept, dummy_info, dummy_factors_b
     _, codes, unknown = spec.encode(sample_df, dummy_info, numeric=False)
     dev = torch.device("cuda")
     X, missing = spec.build(spec.numeric_to_device(sample_df, dev), torch.from_numpy(codes).to(dev))
-    if missing or unknown:          # models.py:80-91 / :187-194
-        shape = (len(sample_df), len(spec.names) - (1 if fit_intercept else 0) - len(missing))
+    if missing or unknown:
+        _warn_missing_levels(missing, len(sample_df), spec.names, fit_intercept, skip=not for_eval)
         if not for_eval:
-            warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape)
-                          + "Skip modeling this part of data.")
             return None, spec.names
-        warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape))
     return X, spec.names
 
 
@@ -95,7 +162,7 @@ def logistic_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_
     UDF does (models.py:42-147).  Returns the p x (3+p) frame `par_id, coef, Sig_invMcoef,
     [intercept,] <features>`; a chunk that lacks an expected dummy level returns the all-zero
     block with a warning (models.py:84-91)."""
-    yd = torch.from_numpy(np.ascontiguousarray(sample_df[Y_name].to_numpy(dtype=np.float64))).cuda()
+    yd = _to_device(sample_df, Y_name)
     r = None
     if len(dummy_info) > 0:
         # dummy path: fit on the raw numerics + level codes when the design qualifies (structured passes, the dense
@@ -108,26 +175,15 @@ def logistic_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_
             _, codes, unknown = spec.encode(sample_df, dummy_info, numeric=False)
             missing = spec.missing_levels(codes)
             if missing or unknown:
-                shape = (len(sample_df), len(names) - (1 if fit_intercept else 0) - len(missing))
-                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape)
-                              + "Skip modeling this part of data.")
-                return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+                _warn_missing_levels(missing, len(sample_df), names, fit_intercept, skip=True)
+                return _zero_block(names)
             r = engine.onehot_irls_fit(plan, spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, [0, len(sample_df)])
     if r is None:
         Xd, names = _device_design(sample_df, Y_name, fit_intercept, dummy_info, dummy_factors_baseline, data_info)
         if Xd is None:
-            return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
+            return _zero_block(names)
         r = engine.irls_fit(Xd, yd, [0, Xd.shape[0]])
-    st = r["status"][0]
-    if st == 1:
-        warnings.warn("logistic_model: Newton iterations did not converge (max_iter reached)")
-    elif st == 2:
-        warnings.warn("logistic_model: Hessian not positive definite (collinear or separable data)")
-    blocks = MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"])
-    out = blocks.block_frame(0)
-    if out.isna().values.any():
-        warnings.warn("NAs appear in the final output")     # models.py:144-145
-    return out
+    return _first_block_frame(_blocks(r, names, len(sample_df)), "logistic_model", "Hessian not positive definite (collinear or separable data)")
 
 
 def fit_logistic_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, names=None,
@@ -149,25 +205,15 @@ def fit_logistic_partitions(X, y, partition_num=None, part_offsets=None, fit_int
                         "fit_linear_partitions takes fp32 rows), got %s" % X.dtype)
     y = y.to(torch.float64)                 # labels may arrive as integers / bools / fp32
     n, p = X.shape
-    if names is None:
-        names = ["x" + str(i) for i in range(p)]
-    names = (["intercept"] if fit_intercept else []) + list(names)
+    names = _column_names(names, p, fit_intercept)
     # No copy of the shard either way: partition_id = i % K is the strided view rows k, k + K, ... (row pitch ldx K), and the
     # intercept's ones column (models.py:121-122) is implicit in the kernels.  At config-3 scale (2.5e7 x 500 fp64 = 100 GB
     # of a 288 GB part) a gathered copy plus a [1 | X] copy would not fit.
-    if part_offsets is None:
-        K = int(partition_num) if partition_num else 1
-        first = list(range(K))
-        rows = [len(range(k, n, K)) for k in range(K)]
-        step = K
-    else:
-        offs = [int(v) for v in part_offsets]
-        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+    first, rows, step = _partitions(n, partition_num, part_offsets)
     with engine.irls_options(options, **option_fields):
         r = engine.irls_fit_ex(engine.row_major(X), y.contiguous(), first, rows, row_step=step, fit_intercept=fit_intercept,
                                tol=tol, max_iter=max_iter)
-    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"],
-                        sample_size=n)
+    return _blocks(r, names, n)
 
 
 def fit_logistic_design(num, codes, y, spec, partition_num=None, part_offsets=None, structured=True, tol=1e-13,
@@ -183,26 +229,11 @@ def fit_logistic_design(num, codes, y, spec, partition_num=None, part_offsets=No
     y = y.to(torch.float64)
     if num is not None and num.dtype != torch.float64:
         raise TypeError("fit_logistic_design: num must be float64, got %s" % num.dtype)
-    n = y.numel()
     # partition_id = i % K (models.py:33) as strided views: nothing is gathered (the structured fit takes (first, rows, step); the
     # dense one builds the matrix once and hands the same views to dlsa_irls_fit_ex_f64)
-    if part_offsets is None:
-        K = int(partition_num) if partition_num else 1
-        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
-    else:
-        offs = [int(v) for v in part_offsets]
-        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
-    plan = spec.onehot_plan() if structured else None
     with engine.irls_options(options, **option_fields):       # (the IRLS driver's policy for this call: see fit_logistic_partitions)
-        if plan is not None:
-            r = engine.onehot_irls_fit_ex(plan, engine.row_major(num) if num is not None else None,
-                                          engine.row_major(codes) if codes is not None else None, y.contiguous(), first, rows,
-                                          row_step=step, tol=tol, max_iter=max_iter)
-        else:
-            X, _ = spec.build(num, codes)
-            r = engine.irls_fit_ex(X, y.contiguous(), first, rows, row_step=step, tol=tol, max_iter=max_iter)
-    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], spec.names, r["status"], r["n_iter"], r["loglik"],
-                        sample_size=n)
+        return _fit_design(engine.onehot_irls_fit_ex, engine.irls_fit_ex, num, codes, y.contiguous(), spec, partition_num, part_offsets,
+                           structured, tol=tol, max_iter=max_iter)
 
 
 def logistic_model_eval(sample_df, Y_name, par, fit_intercept=False, dummy_info=[], dummy_factors_baseline=[],
@@ -210,7 +241,7 @@ def logistic_model_eval(sample_df, Y_name, par, fit_intercept=False, dummy_info=
     """Log-likelihood of every estimator column of `par` on one partition (models.py:151-225)."""
     Xd, _ = _device_design(sample_df, Y_name, fit_intercept, dummy_info, dummy_factors_baseline, data_info,
                            for_eval=True)
-    yd = torch.from_numpy(np.ascontiguousarray(sample_df[Y_name].to_numpy(dtype=np.float64))).cuda()
+    yd = _to_device(sample_df, Y_name)
     pard = torch.from_numpy(np.ascontiguousarray(np.asarray(par, dtype=np.float64))).cuda()
     ll = engine.loglik(Xd, yd, pard).cpu().numpy()
     return pd.DataFrame({par.columns[i]: [ll[i]] for i in range(par.shape[1])})
@@ -299,9 +330,7 @@ def fit_linear_partitions(X, y, partition_num=None, part_offsets=None, fit_inter
         yc = y.contiguous()
         views = [(X[offs[k]:offs[k + 1]], yc[offs[k]:offs[k + 1]]) for k in range(K)]
     pp = p + (1 if fit_intercept else 0)
-    if names is None:
-        names = ["x" + str(i) for i in range(p)]
-    names = (["intercept"] if fit_intercept else []) + list(names)
+    names = _column_names(names, p, fit_intercept)
     coef = torch.zeros((K, pp), dtype=torch.float64, device=X.device)
     smc = torch.zeros((K, pp), dtype=torch.float64, device=X.device)
     sig = torch.zeros((K, pp, pp), dtype=torch.float64, device=X.device)
@@ -340,9 +369,7 @@ def fit_linear_streaming(n, p, partition_num=1, chunk_rows=1 << 22, seed=2026010
         raise ValueError("fit_linear_streaming: kind='gaussian32' is the fp32-native stream (dtype=torch.float32)")
     kind_id = 0 if native32 else ({"uniform": engine.SYNTH_UNIFORM, "gaussian": engine.SYNTH_GAUSSIAN}[kind] if isinstance(kind, str) else int(kind))
     pp = p + (1 if fit_intercept else 0)
-    if names is None:
-        names = ["x" + str(i) for i in range(p)]
-    names = (["intercept"] if fit_intercept else []) + list(names)
+    names = _column_names(names, p, fit_intercept)
     coef = torch.zeros((K, pp), dtype=torch.float64, device=device)
     smc = torch.zeros((K, pp), dtype=torch.float64, device=device)
     sig = torch.zeros((K, pp, pp), dtype=torch.float64, device=device)
@@ -412,9 +439,7 @@ def fit_linear_chunks(chunks, p, partition_num=1, fit_intercept=False, dtype=Non
     if not torch.cuda.is_available():
         raise RuntimeError("fit_linear_chunks runs on the GPU only (no CPU fallback)")
     pp = p + (1 if fit_intercept else 0)
-    if names is None:
-        names = ["x" + str(i) for i in range(p)]
-    names = (["intercept"] if fit_intercept else []) + list(names)
+    names = _column_names(names, p, fit_intercept)
     coef = torch.zeros((K, pp), dtype=torch.float64, device=device)
     smc = torch.zeros((K, pp), dtype=torch.float64, device=device)
     sig = torch.zeros((K, pp, pp), dtype=torch.float64, device=device)
@@ -475,13 +500,9 @@ def linear_model(sample_df, Y_name, fit_intercept=False, dummy_info=[], dummy_fa
     p x (3+p) output frame `par_id, coef, Sig_invMcoef, [intercept,] <features>`."""
     Xd, names = _device_design(sample_df, Y_name, fit_intercept, dummy_info, dummy_factors_baseline, data_info)
     if Xd is None:
-        return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-    yd = torch.from_numpy(np.ascontiguousarray(sample_df[Y_name].to_numpy(dtype=np.float64))).cuda()
-    mb = fit_linear_partitions(Xd, yd, fit_intercept=False, names=names)      # the ones column is already in Xd
-    out = mb.block_frame(0)
-    if out.isna().values.any():
-        warnings.warn("NAs appear in the final output")
-    return out
+        return _zero_block(names)
+    mb = fit_linear_partitions(Xd, _to_device(sample_df, Y_name), fit_intercept=False, names=names)      # the ones column is already in Xd
+    return _first_block_frame(mb)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -582,10 +603,8 @@ def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, na
     offs = [0]
     for c in counts:
         offs.append(offs[-1] + int(c))
-    if names is None:
-        names = ["x" + str(i) for i in range(p)]
     r = engine.cox_fit(X, time, event, order, offs, tol=tol, max_iter=max_iter, ties=ties, strata=strata)
-    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
+    return _blocks(r, _column_names(names, p, False), n)
 
 
 def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_baseline=[], data_info=[], ties="breslow", strata=None):
@@ -606,20 +625,10 @@ def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_bas
     features_df = sample_df.drop(columns=[event_name])
     Xd, names = _device_design(features_df, time_name, False, dummy_info, dummy_factors_baseline, data_info)
     if Xd is None:
-        return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-    td = torch.from_numpy(np.ascontiguousarray(sample_df[time_name].to_numpy(dtype=np.float64))).cuda()
-    ed = torch.from_numpy(np.ascontiguousarray(sample_df[event_name].to_numpy(dtype=np.float64))).cuda()
+        return _zero_block(names)
     sd = torch.from_numpy(np.ascontiguousarray(codes)).cuda() if codes is not None else None
-    mb = fit_cox_partitions(Xd, td, ed, names=names, ties=ties, strata=sd)
-    st = mb.status[0]
-    if st == 1:
-        warnings.warn("cox_model: Newton iterations did not converge (max_iter reached: monotone likelihood?)")
-    elif st == 2:
-        warnings.warn("cox_model: information matrix not positive definite (collinear design)")
-    out = mb.block_frame(0)
-    if out.isna().values.any():
-        warnings.warn("NAs appear in the final output")
-    return out
+    mb = fit_cox_partitions(Xd, _to_device(sample_df, time_name), _to_device(sample_df, event_name), names=names, ties=ties, strata=sd)
+    return _first_block_frame(mb, "cox_model", hint=": monotone likelihood?")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -662,6 +671,17 @@ def _poisson_offset(offset, exposure, n, device):
     return offset
 
 
+def _count_rows(who, y, n, offset, exposure, device):
+    """The counts and the offset of a count fit of n rows as the engine takes them: (y fp64 contiguous, offset fp64 or None), on
+    `device`; ValueError for a wrong length, a negative count or a bad offset / exposure."""
+    y = torch.as_tensor(y, device=device).to(torch.float64).contiguous()
+    if y.numel() != n:
+        raise ValueError("%s: y must have n = %d elements" % (who, n))
+    if bool((y < 0).any()):
+        raise ValueError("%s: counts must be non-negative" % who)
+    return y, _poisson_offset(offset, exposure, n, device)
+
+
 def fit_poisson_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, names=None,
                            tol=1e-13, max_iter=100):
     """Poisson map step for the partitions of one device-resident shard: X [n, p] fp64 row-major, y [n] counts on the GPU.
@@ -674,24 +694,12 @@ def fit_poisson_partitions(X, y, partition_num=None, part_offsets=None, fit_inte
     if X.dtype != torch.float64:
         raise TypeError("fit_poisson_partitions: X must be float64, got %s" % X.dtype)
     n, p = X.shape
-    y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
-    if y.numel() != n:
-        raise ValueError("fit_poisson_partitions: y must have n = %d elements" % n)
-    if bool((y < 0).any()):
-        raise ValueError("fit_poisson_partitions: counts must be non-negative")
-    offset = _poisson_offset(offset, exposure, n, X.device)
-    if names is None:
-        names = ["x" + str(i) for i in range(p)]
-    names = (["intercept"] if fit_intercept else []) + list(names)
-    if part_offsets is None:
-        K = int(partition_num) if partition_num else 1
-        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
-    else:
-        offs = [int(v) for v in part_offsets]
-        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+    y, offset = _count_rows("fit_poisson_partitions", y, n, offset, exposure, X.device)
+    names = _column_names(names, p, fit_intercept)
+    first, rows, step = _partitions(n, partition_num, part_offsets)
     r = engine.poisson_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept,
                               tol=tol, max_iter=max_iter)
-    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
+    return _blocks(r, names, n)
 
 
 def fit_poisson_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, structured=True,
@@ -706,57 +714,86 @@ def fit_poisson_design(num, codes, y, spec, partition_num=None, part_offsets=Non
         raise RuntimeError("fit_poisson_design runs on the GPU only (no CPU fallback)")
     if num is not None and num.dtype != torch.float64:
         raise TypeError("fit_poisson_design: num must be float64, got %s" % num.dtype)
-    y = y.to(torch.float64).contiguous()
-    n = y.numel()
-    if bool((y < 0).any()):
-        raise ValueError("fit_poisson_design: counts must be non-negative")
-    offset = _poisson_offset(offset, exposure, n, y.device)
-    if part_offsets is None:
-        K = int(partition_num) if partition_num else 1
-        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
-    else:
-        offs = [int(v) for v in part_offsets]
-        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
-    plan = spec.onehot_plan() if structured else None
-    if plan is not None:
-        r = engine.onehot_poisson_fit_ex(plan, engine.row_major(num) if num is not None else None,
-                                         engine.row_major(codes) if codes is not None else None, y, first, rows, row_step=step,
-                                         offset=offset, tol=tol, max_iter=max_iter)
-    else:
-        X, _ = spec.build(num, codes)
-        r = engine.poisson_fit_ex(X, y, first, rows, row_step=step, offset=offset, tol=tol, max_iter=max_iter)
-    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], spec.names, r["status"], r["n_iter"], r["loglik"], sample_size=n)
+    y, offset = _count_rows("fit_poisson_design", y, y.numel(), offset, exposure, y.device)
+    return _fit_design(engine.onehot_poisson_fit_ex, engine.poisson_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
+                       offset=offset, tol=tol, max_iter=max_iter)
 
 
-def _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info):
-    """The raw representation of one chunk for the structured Poisson path: (spec, plan or None when the design does not qualify,
+def _count_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info):
+    """The raw representation of one chunk for the structured count paths: (spec, plan or None when the design does not qualify,
     codes host array, unknown, y, offset column, exposure column).  The intercept is the plan's constant column."""
-    drop = [c for c in (offset_name, exposure_name) if c is not None]
-    frame = sample_df.drop(columns=drop)
+    frame = sample_df.drop(columns=[c for c in (offset_name, exposure_name) if c is not None])
     spec = DesignSpec.from_reference(list(frame.columns), Y_name, fit_intercept, dummy_info, dummy_factors_baseline, data_info)
     plan = spec.onehot_plan()
     if plan is None:
         return spec, None, None, False, None, None, None
     _, codes, unknown = spec.encode(frame, dummy_info, numeric=False)
-    yd = torch.from_numpy(np.ascontiguousarray(sample_df[Y_name].to_numpy(dtype=np.float64))).cuda()
-
-    def col(name):
-        return None if name is None else torch.from_numpy(np.ascontiguousarray(sample_df[name].to_numpy(dtype=np.float64))).cuda()
-    return spec, plan, codes, unknown, yd, col(offset_name), col(exposure_name)
+    return spec, plan, codes, unknown, _to_device(sample_df, Y_name), _to_device(sample_df, offset_name), _to_device(sample_df, exposure_name)
 
 
-def _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info,
-                   for_eval=False):
-    """(X device design WITHOUT the ones column -- the kernels carry the intercept -- or None, names, y, offset) of one chunk."""
-    drop = [c for c in (offset_name, exposure_name) if c is not None]
-    Xd, names = _device_design(sample_df.drop(columns=drop), Y_name, False, dummy_info, dummy_factors_baseline, data_info,
-                               for_eval=for_eval)
-    names = (["intercept"] if fit_intercept else []) + list(names)
-    yd = torch.from_numpy(np.ascontiguousarray(sample_df[Y_name].to_numpy(dtype=np.float64))).cuda()
+def _count_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info,
+                 for_eval=False):
+    """(X device design WITHOUT the ones column -- the kernels carry the intercept -- or None, names, y, offset, exposure) of one chunk."""
+    frame = sample_df.drop(columns=[c for c in (offset_name, exposure_name) if c is not None])
+    Xd, names = _device_design(frame, Y_name, False, dummy_info, dummy_factors_baseline, data_info, for_eval=for_eval)
+    return (Xd, _column_names(names, len(names), fit_intercept), _to_device(sample_df, Y_name), _to_device(sample_df, offset_name),
+            _to_device(sample_df, exposure_name))
 
-    def col(name):
-        return None if name is None else torch.from_numpy(np.ascontiguousarray(sample_df[name].to_numpy(dtype=np.float64))).cuda()
-    return Xd, names, yd, col(offset_name), col(exposure_name)
+
+def _count_model(who, fit_design, fit_partitions, structured, chunk, **fit_args):
+    """The body of poisson_model / negbin_model: `chunk` is (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+    dummy_factors_baseline, data_info), fit_args the family's own keywords.  Returns (the block's frame, the MappedBlocks or None for
+    the all-zero block of a skipped chunk)."""
+    sample_df, fit_intercept, dummy_info = chunk[0], chunk[2], chunk[5]
+    mb = None
+    if structured and len(dummy_info) > 0:
+        spec, plan, codes, unknown, yd, od, ed = _count_raw_frame(*chunk)
+        if plan is not None:
+            names = spec.names
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                _warn_missing_levels(missing, len(sample_df), names, fit_intercept, skip=True)
+                return _zero_block(names), None
+            mb = fit_design(spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, spec, offset=od, exposure=ed, **fit_args)
+    if mb is None:
+        Xd, names, yd, od, ed = _count_frame(*chunk)
+        if Xd is None:
+            return _zero_block(names), None
+        mb = fit_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, names=names[1:] if fit_intercept else names,
+                            **fit_args)
+    return _first_block_frame(mb, who), mb
+
+
+def _count_model_eval(dense_pass, onehot_pass, par, structured, chunk):
+    """The body of poisson_model_eval / negbin_model_eval, `chunk` as in _count_model: the log-likelihood of every column of `par` by
+    one pass without the information per column -- dense_pass(X, y, beta, ...) or, on the raw representation,
+    onehot_pass(plan, num, codes, y, beta, ...)."""
+    sample_df, fit_intercept, dummy_info = chunk[0], chunk[2], chunk[5]
+    pard = np.asarray(par, dtype=np.float64)
+    run = None
+    if structured and len(dummy_info) > 0:
+        spec, plan, codes, unknown, yd, od, ed = _count_raw_frame(*chunk)
+        if plan is not None:
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                _warn_missing_levels(missing, len(sample_df), spec.names, fit_intercept, skip=False)
+            od = _poisson_offset(od, ed, yd.numel(), yd.device)
+            num, cd = spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda()
+
+            def run(b):
+                return onehot_pass(plan, num, cd, yd, b, offset=od, want_H=False)
+    if run is None:
+        Xd, _, yd, od, ed = _count_frame(*chunk, for_eval=True)
+        od = _poisson_offset(od, ed, yd.numel(), yd.device)
+        X = engine.row_major(Xd)
+
+        def run(b):
+            return dense_pass(X, yd, b, offset=od, fit_intercept=fit_intercept, want_H=False)
+    out = {}
+    for i in range(pard.shape[1]):
+        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+        out[par.columns[i]] = [float(run(b)[2].item())]
+    return pd.DataFrame(out)
 
 
 def poisson_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
@@ -766,34 +803,8 @@ def poisson_model(sample_df, Y_name, fit_intercept=False, offset_name=None, expo
     [intercept,] <features>`; a chunk that lacks an expected dummy level returns the all-zero block with a warning.
     structured=True with a dummy_info and a qualifying design fits on the raw numerics + level codes (fit_poisson_design; the
     dense one-hot matrix is never built, the missing-level check runs on the codes); the default is the dense path."""
-    mb = None
-    if structured and len(dummy_info) > 0:
-        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
-                                                                    dummy_info, dummy_factors_baseline, data_info)
-        if plan is not None:
-            names = spec.names
-            missing = spec.missing_levels(codes)
-            if missing or unknown:
-                shape = (len(sample_df), len(names) - (1 if fit_intercept else 0) - len(missing))
-                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape)
-                              + "Skip modeling this part of data.")
-                return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-            mb = fit_poisson_design(spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, spec, offset=od, exposure=ed)
-    if mb is None:
-        Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
-                                               dummy_factors_baseline, data_info)
-        if Xd is None:
-            return pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-        mb = fit_poisson_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, names=names[1:] if fit_intercept else names)
-    st = mb.status[0]
-    if st == 1:
-        warnings.warn("poisson_model: Newton iterations did not converge (max_iter reached)")
-    elif st == 2:
-        warnings.warn("poisson_model: information matrix not positive definite (collinear design)")
-    out = mb.block_frame(0)
-    if out.isna().values.any():
-        warnings.warn("NAs appear in the final output")
-    return out
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    return _count_model("poisson_model", fit_poisson_design, fit_poisson_partitions, structured, chunk)[0]
 
 
 def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
@@ -801,33 +812,8 @@ def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=
     """Log-likelihood (sum y eta - mu - lgamma(y + 1)) of every estimator column of `par` on one partition, shaped like
     logistic_model_eval's output: one row, a column per estimator.  structured=True with a dummy_info and a qualifying design
     evaluates on the raw numerics + level codes (one structured pass per estimator column); the default is the dense path."""
-    pard = np.asarray(par, dtype=np.float64)
-    if structured and len(dummy_info) > 0:
-        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
-                                                                    dummy_info, dummy_factors_baseline, data_info)
-        if plan is not None:
-            missing = spec.missing_levels(codes)
-            if missing or unknown:
-                shape = (len(sample_df), len(spec.names) - (1 if fit_intercept else 0) - len(missing))
-                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape))
-            od = _poisson_offset(od, ed, yd.numel(), yd.device)
-            num, cd = spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda()
-            out = {}
-            for i in range(pard.shape[1]):
-                b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
-                _, _, ll, _ = engine.onehot_poisson_pass(plan, num, cd, yd, b, offset=od, want_H=False)
-                out[par.columns[i]] = [float(ll.item())]
-            return pd.DataFrame(out)
-    Xd, _, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
-                                       dummy_factors_baseline, data_info, for_eval=True)
-    od = _poisson_offset(od, ed, yd.numel(), yd.device)
-    X = engine.row_major(Xd)
-    out = {}
-    for i in range(pard.shape[1]):
-        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
-        _, _, ll, _ = engine.poisson_pass(X, yd, b, offset=od, fit_intercept=fit_intercept, want_H=False)
-        out[par.columns[i]] = [float(ll.item())]
-    return pd.DataFrame(out)
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    return _count_model_eval(engine.poisson_pass, engine.onehot_poisson_pass, par, structured, chunk)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -870,25 +856,12 @@ def fit_negbin_partitions(X, y, partition_num=None, part_offsets=None, fit_inter
     if alpha is not None and float(alpha) == 0.0:
         raise ValueError("fit_negbin_partitions: alpha = 0 is the Poisson model: use fit_poisson_partitions")
     n, p = X.shape
-    y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
-    if y.numel() != n:
-        raise ValueError("fit_negbin_partitions: y must have n = %d elements" % n)
-    if bool((y < 0).any()):
-        raise ValueError("fit_negbin_partitions: counts must be non-negative")
-    offset = _poisson_offset(offset, exposure, n, X.device)
-    if names is None:
-        names = ["x" + str(i) for i in range(p)]
-    names = (["intercept"] if fit_intercept else []) + list(names)
-    if part_offsets is None:
-        K = int(partition_num) if partition_num else 1
-        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
-    else:
-        offs = [int(v) for v in part_offsets]
-        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
+    y, offset = _count_rows("fit_negbin_partitions", y, n, offset, exposure, X.device)
+    names = _column_names(names, p, fit_intercept)
+    first, rows, step = _partitions(n, partition_num, part_offsets)
     r = engine.negbin_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept, alpha=alpha,
                              tol=tol, max_iter=max_iter)
-    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n,
-                        extra={"alpha": r["alpha"], "alpha_info": r["alpha_info"], "pearson": r["pearson"]})
+    return _blocks(r, names, n)
 
 
 def fit_negbin_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, alpha=None,
@@ -905,27 +878,9 @@ def fit_negbin_design(num, codes, y, spec, partition_num=None, part_offsets=None
         raise TypeError("fit_negbin_design: num must be float64, got %s" % num.dtype)
     if alpha is not None and float(alpha) == 0.0:
         raise ValueError("fit_negbin_design: alpha = 0 is the Poisson model: use fit_poisson_design")
-    y = y.to(torch.float64).contiguous()
-    n = y.numel()
-    if bool((y < 0).any()):
-        raise ValueError("fit_negbin_design: counts must be non-negative")
-    offset = _poisson_offset(offset, exposure, n, y.device)
-    if part_offsets is None:
-        K = int(partition_num) if partition_num else 1
-        first, rows, step = list(range(K)), [len(range(k, n, K)) for k in range(K)], K
-    else:
-        offs = [int(v) for v in part_offsets]
-        first, rows, step = offs[:-1], [offs[k + 1] - offs[k] for k in range(len(offs) - 1)], 1
-    plan = spec.onehot_plan() if structured else None
-    if plan is not None:
-        r = engine.onehot_negbin_fit_ex(plan, engine.row_major(num) if num is not None else None,
-                                        engine.row_major(codes) if codes is not None else None, y, first, rows, row_step=step,
-                                        offset=offset, alpha=alpha, tol=tol, max_iter=max_iter)
-    else:
-        X, _ = spec.build(num, codes)
-        r = engine.negbin_fit_ex(X, y, first, rows, row_step=step, offset=offset, alpha=alpha, tol=tol, max_iter=max_iter)
-    return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], spec.names, r["status"], r["n_iter"], r["loglik"], sample_size=n,
-                        extra={"alpha": r["alpha"], "alpha_info": r["alpha_info"], "pearson": r["pearson"]})
+    y, offset = _count_rows("fit_negbin_design", y, y.numel(), offset, exposure, y.device)
+    return _fit_design(engine.onehot_negbin_fit_ex, engine.negbin_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
+                       offset=offset, alpha=alpha, tol=tol, max_iter=max_iter)
 
 
 def combine_dispersion(mb):
@@ -948,40 +903,9 @@ def negbin_model(sample_df, Y_name, fit_intercept=False, offset_name=None, expos
     returns the all-zero block with a warning.  structured=True with a dummy_info and a qualifying design fits on the raw numerics +
     level codes (fit_negbin_design; the dense one-hot matrix is never built, the missing-level check runs on the codes); the
     default is the dense path."""
-    mb = None
-    if structured and len(dummy_info) > 0:
-        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
-                                                                    dummy_info, dummy_factors_baseline, data_info)
-        if plan is not None:
-            names = spec.names
-            missing = spec.missing_levels(codes)
-            if missing or unknown:
-                shape = (len(sample_df), len(names) - (1 if fit_intercept else 0) - len(missing))
-                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape)
-                              + "Skip modeling this part of data.")
-                out = pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-                out.attrs["alpha"] = 0.0
-                return out
-            mb = fit_negbin_design(spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, spec, offset=od, exposure=ed,
-                                   alpha=alpha)
-    if mb is None:
-        Xd, names, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
-                                               dummy_factors_baseline, data_info)
-        if Xd is None:
-            out = pd.DataFrame(0, index=np.arange(len(names)), columns=["par_id", "coef", "Sig_invMcoef"] + names)
-            out.attrs["alpha"] = 0.0
-            return out
-        mb = fit_negbin_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, alpha=alpha,
-                                   names=names[1:] if fit_intercept else names)
-    st = mb.status[0]
-    if st == 1:
-        warnings.warn("negbin_model: Newton iterations did not converge (max_iter reached)")
-    elif st == 2:
-        warnings.warn("negbin_model: information matrix not positive definite (collinear design)")
-    out = mb.block_frame(0)
-    if out.isna().values.any():
-        warnings.warn("NAs appear in the final output")
-    out.attrs["alpha"] = mb.extra["alpha"][0]
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    out, mb = _count_model("negbin_model", fit_negbin_design, fit_negbin_partitions, structured, chunk, alpha=alpha)
+    out.attrs["alpha"] = mb.extra["alpha"][0] if mb is not None else 0.0         # (a skipped chunk's all-zero block: 0)
     return out
 
 
@@ -991,30 +915,10 @@ def negbin_model_eval(sample_df, Y_name, par, alpha, fit_intercept=False, offset
     poisson_model_eval's output: one row, a column per estimator (one pass without the information per column).  structured=True
     with a dummy_info and a qualifying design evaluates on the raw numerics + level codes (one structured pass per estimator
     column); the default is the dense path."""
-    pard = np.asarray(par, dtype=np.float64)
-    if structured and len(dummy_info) > 0:
-        spec, plan, codes, unknown, yd, od, ed = _poisson_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name,
-                                                                    dummy_info, dummy_factors_baseline, data_info)
-        if plan is not None:
-            missing = spec.missing_levels(codes)
-            if missing or unknown:
-                shape = (len(sample_df), len(spec.names) - (1 if fit_intercept else 0) - len(missing))
-                warnings.warn("Dummies:" + str(set(missing)) + "missing in this data chunk " + str(shape))
-            od = _poisson_offset(od, ed, yd.numel(), yd.device)
-            num, cd = spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda()
-            out = {}
-            for i in range(pard.shape[1]):
-                b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
-                ll = engine.onehot_negbin_pass(plan, num, cd, yd, b, alpha, offset=od, want_H=False)[2]
-                out[par.columns[i]] = [float(ll.item())]
-            return pd.DataFrame(out)
-    Xd, _, yd, od, ed = _poisson_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
-                                       dummy_factors_baseline, data_info, for_eval=True)
-    od = _poisson_offset(od, ed, yd.numel(), yd.device)
-    X = engine.row_major(Xd)
-    out = {}
-    for i in range(pard.shape[1]):
-        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
-        ll = engine.negbin_pass(X, yd, b, alpha, offset=od, fit_intercept=fit_intercept, want_H=False)[2]
-        out[par.columns[i]] = [float(ll.item())]
-    return pd.DataFrame(out)
+    def dense_pass(X, y, b, **kw):
+        return engine.negbin_pass(X, y, b, alpha, **kw)
+
+    def onehot_pass(plan, num, codes, y, b, **kw):
+        return engine.onehot_negbin_pass(plan, num, codes, y, b, alpha, **kw)
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)
