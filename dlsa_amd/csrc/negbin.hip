@@ -243,18 +243,9 @@ int nb_fit_core(const char* who, const double* y, const double* offset, const in
         if (rc && rc != DLSA_ERR_NOT_CONVERGED && rc != DLSA_ERR_NOT_SPD && rc != DLSA_ERR_NAN) return rc;
         if (st_k == DLSA_PART_OK) {
             c.nk = nk;
-            c.yk = y + part_first_host[k];
-            c.ok = offset ? offset + part_first_host[k] : nullptr;
-            if (row_step > 1) {                               // the partition's counts and offsets, gathered once
-                rc = pois_gather(y, part_first_host[k], row_step, nk, b.ybuf, s);
-                if (rc) return rc;
-                c.yk = b.ybuf;
-                if (offset) {
-                    rc = pois_gather(offset, part_first_host[k], row_step, nk, b.obuf, s);
-                    if (rc) return rc;
-                    c.ok = b.obuf;
-                }
-            }
+            // the partition's counts and offsets, gathered once when it is strided
+            rc = pois_gather_rows(y, offset, part_first_host[k], row_step, nk, b.ybuf, b.obuf, c.yk, c.ok, s);
+            if (rc) return rc;
             DLSA_HIP_CHECK(hipMemcpyAsync(c.beta, ck, (size_t)pe * sizeof(double), hipMemcpyDeviceToDevice, s));
             // mu at the Poisson MLE (alpha = 0: the Poisson limit; no H, no g), then the moment sums
             rc = evalk(k, c.yk, c.ok, nk, c.beta, 0.0, nullptr, nullptr, nullptr, nullptr, c.mu);

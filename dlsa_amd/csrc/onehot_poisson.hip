@@ -70,7 +70,7 @@ static int oh_pois_ldn_min(const dlsa_onehot_plan* pl) {       // columns of num
     return m;
 }
 
-static int oh_pois_icpt_col(const dlsa_onehot_plan* pl) {      // the plan's constant column, -1 without one
+int oh_pois_icpt_col(const dlsa_onehot_plan* pl) {      // the plan's constant column, -1 without one
     for (int a = 0; a < pl->desc.D; ++a)
         if (pl->desc.dense_kind[a] == 0) return pl->desc.dense_col[a];
     return -1;

@@ -128,6 +128,12 @@ int pois_ll_fix(double* ll, const double* cst, hipStream_t s) {
     return DLSA_OK;
 }
 
+int pois_start(double* beta, int pe, int icpt_col, double b0, hipStream_t s) {
+    hipLaunchKernelGGL(poisson_start_kernel, dim3((pe + 255) / 256), dim3(256), 0, s, beta, pe, icpt_col, b0);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
 int pois_gather(const double* v, int64_t first, int64_t step, int64_t n, double* out, hipStream_t s) {
     hipLaunchKernelGGL(poisson_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, first, step, n, out);
     DLSA_HIP_CHECK(hipGetLastError());
@@ -160,17 +166,9 @@ int pois_fit_core(const char* who, const double* y, const double* offset, const 
         int st_k = DLSA_PART_EMPTY, iters = 0;
         double ll = 0.0, cst[4] = {0.0, 0.0, 0.0, 0.0};
         if (nk > 0) {
-            int rc = DLSA_OK;
-            if (row_step > 1) {                               // the partition's counts and offsets, gathered once (8 bytes per row each)
-                rc = pois_gather(y, part_first_host[k], row_step, nk, b.ybuf, s);
-                if (rc) return rc;
-                yk = b.ybuf;
-                if (offset) {
-                    rc = pois_gather(offset, part_first_host[k], row_step, nk, b.obuf, s);
-                    if (rc) return rc;
-                    ok = b.obuf;
-                }
-            }
+            // a strided partition's counts and offsets are gathered once (8 bytes per row each)
+            int rc = pois_gather_rows(y, offset, part_first_host[k], row_step, nk, b.ybuf, b.obuf, yk, ok, s);
+            if (rc) return rc;
             rc = pois_const(yk, ok, nk, b.cpart, b.cst, s);
             if (rc) return rc;
             DLSA_HIP_CHECK(hipMemcpyAsync(cst, b.cst, sizeof(cst), hipMemcpyDeviceToHost, s));
@@ -184,8 +182,8 @@ int pois_fit_core(const char* who, const double* y, const double* offset, const 
         if (nk > 0 && cst[1] > 0.0) {
             // the intercept starts at log(sum y / sum e^o), the exact MLE of the intercept-only model
             const double b0 = (icpt_col >= 0 && cst[2] > 0.0 && isfinite(cst[2])) ? log(cst[1] / cst[2]) : 0.0;
-            hipLaunchKernelGGL(poisson_start_kernel, dim3((pe + 255) / 256), dim3(256), 0, s, b.st.beta, pe, icpt_col, b0);
-            DLSA_HIP_CHECK(hipGetLastError());
+            const int rcs = pois_start(b.st.beta, pe, icpt_col, b0, s);
+            if (rcs) return rcs;
             const NewtonDevice dev{b.st, Hk, pe, s};
             NewtonOutcome o;
             const int rcl = newton_fit_loop(NEWTON_POISSON, tol, max_iter + 1,

@@ -1,6 +1,6 @@
-// What is Poisson's among the things the count-model translation units (poisson.hip, onehot_poisson.hip, negbin.hip,
-// onehot_negbin.hip) share: the constant-term, log-likelihood-fix and gather launchers of poisson.hip, the fit driver that takes
-// the evaluation as a callable, and the structured pass of onehot_poisson.hip.  The Newton state, loop and epilogue are newton_fit.h; the prototypes of the rest of the library are host_calls.h.
+// What is Poisson's among the things the log-link translation units (poisson.hip, onehot_poisson.hip, negbin.hip,
+// onehot_negbin.hip, gamma.hip, onehot_gamma.hip) share: the constant-term, log-likelihood-fix, start and gather launchers of
+// poisson.hip, the fit driver that takes the evaluation as a callable, and the structured pass and plan helpers of onehot_poisson.hip.  The Newton state, loop and epilogue are newton_fit.h; the prototypes of the rest of the library are host_calls.h.
 #pragma once
 #include "common.h"
 #include "newton_fit.h"
@@ -17,6 +17,25 @@ int pois_const(const double* y, const double* off, int64_t n, double* cpart, dou
 int pois_ll_fix(double* ll, const double* cst, hipStream_t s);
 // out[j] = v[first + j * step], j < n: a strided partition's counts or offsets, gathered once (8 bytes per row)
 int pois_gather(const double* v, int64_t first, int64_t step, int64_t n, double* out, hipStream_t s);
+// the Newton start of the log-link fits: beta = 0, entry icpt_col (-1: none) at b0
+int pois_start(double* beta, int pe, int icpt_col, double b0, hipStream_t s);
+// yk / ok = the n > 0 responses and offsets (nullable) of the partition rows first, first + step, ...: in place when step == 1,
+// else gathered into ybuf / obuf
+static inline int pois_gather_rows(const double* y, const double* offset, int64_t first, int64_t step, int64_t n, double* ybuf,
+                                   double* obuf, const double*& yk, const double*& ok, hipStream_t s) {
+    yk = y + first;
+    ok = offset ? offset + first : nullptr;
+    if (step <= 1) return DLSA_OK;
+    int rc = pois_gather(y, first, step, n, ybuf, s);
+    if (rc) return rc;
+    yk = ybuf;
+    if (offset) {
+        rc = pois_gather(offset, first, step, n, obuf, s);
+        if (rc) return rc;
+        ok = obuf;
+    }
+    return DLSA_OK;
+}
 
 // device scratch of the fit loop
 struct PoisFitBufs {
@@ -48,5 +67,7 @@ int oh_pois_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn
                       void* ws_oh, size_t ws_oh_bytes, hipStream_t s);
 // num / codes against what the plan reads (null pointers, ldn, ldc); `who` prefixes the message
 int oh_pois_check_rows(const char* who, const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc);
+// the plan's constant column (where the intercept's start value goes), -1 without one
+int oh_pois_icpt_col(const dlsa_onehot_plan* pl);
 
 }  // namespace dlsa

@@ -642,8 +642,9 @@ def _offset_partitions(who, part_offsets, n, ascending_from_zero=False):
 
 class _FitOut:
     """What a per-partition fit of K partitions with pe coefficients writes: coef / Sig_invMcoef [K, pe] and Sig_inv [K, pe, pe] on the
-    device, n_iter / status / loglik on the host, and with `dispersion` (NB2) alpha / alpha_info / pearson.  `args` is the run of
-    output arguments every dlsa_*_fit_* entry takes, in the C ABI's order; result(rc) is the wrappers' result dict."""
+    device, n_iter / status / loglik on the host, and with `dispersion` the family's own host lists: True (NB2) alpha / alpha_info /
+    pearson, or their names (Gamma: GAMMA_LISTS).  `args` is the run of output arguments every dlsa_*_fit_* entry takes, in the C
+    ABI's order; result(rc) is the wrappers' result dict."""
 
     def __init__(self, K, pe, device, dispersion=False):
         self.coef = torch.empty((K, pe), dtype=torch.float64, device=device)
@@ -651,7 +652,7 @@ class _FitOut:
         self.sig = torch.empty((K, pe, pe), dtype=torch.float64, device=device)
         self.host = {"n_iter": (ctypes.c_int * K)(), "status": (ctypes.c_int * K)(), "loglik": (ctypes.c_double * K)()}
         if dispersion:
-            self.host.update({k: (ctypes.c_double * K)() for k in ("alpha", "alpha_info", "pearson")})
+            self.host.update({k: (ctypes.c_double * K)() for k in (("alpha", "alpha_info", "pearson") if dispersion is True else dispersion)})
         self.args = (_ptr(self.coef), _ptr(self.sig), _ptr(self.smc)) + tuple(self.host.values())
 
     def result(self, rc):
@@ -660,12 +661,15 @@ class _FitOut:
         return {"coef": self.coef, "Sig_invMcoef": self.smc, "Sig_inv": self.sig, **{k: list(v) for k, v in self.host.items()}, "rc": rc}
 
 
-def _pass_out(pe, n, device, want_H, want_w, negbin=False, want_theta=False):
+def _pass_out(pe, n, device, want_H, want_w, negbin=False, want_theta=False, want_stats=None):
     """The outputs of one pass at a fixed beta, in the order the pass wrappers return them: (H [pe, pe] or None, g [pe], loglik [1],
-    w [n] or None) and for NB2 (..., mu [n] or None -- with want_w --, theta_terms [3] or None)."""
+    w [n] or None), for NB2 (..., mu [n] or None -- with want_w --, theta_terms [3] or None) and for Gamma (want_stats not None:
+    ..., stats [2] or None)."""
     def new(shape, want=True):
         return torch.empty(shape, dtype=torch.float64, device=device) if want else None
     out = (new((pe, pe), want_H), new((pe,)), new((1,)), new((n,), want_w))
+    if want_stats is not None:
+        return out + (new((2,), want_stats),)
     return out + (new((n,), want_w), new((3,), want_theta)) if negbin else out
 
 
@@ -891,6 +895,71 @@ def negbin_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_inte
     rc = lib.dlsa_negbin_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, alpha, tol, max_iter,
                                  *out.args, _ptr(ws), ws.numel(), _stream())
     return out.result(rc)
+
+
+def _dispersion_positive(who, dispersion):
+    """The dispersion of a Gamma pass: a positive finite float."""
+    dispersion = float(dispersion)
+    if not 0.0 < dispersion < float("inf"):
+        raise ValueError("%s: dispersion must be positive and finite" % who)
+    return dispersion
+
+
+def _dispersion_fixed(who, dispersion):
+    """The dispersion argument of a Gamma fit as the C ABI takes it: 0.0 for None (estimate it), else a positive finite float."""
+    return 0.0 if dispersion is None else _dispersion_positive(who, dispersion)
+
+
+GAMMA_LISTS = ("dispersion", "pearson", "deviance")
+
+
+def _gamma_result(out, rc, rows, pe):
+    """A Gamma fit's result dict: the lists of GAMMA_LISTS plus `df` = rows - pe per partition (what the Pearson estimate divides by)."""
+    r = out.result(rc)
+    r["df"] = [int(m) - pe for m in rows]
+    return r
+
+
+def gamma_pass(X, y, beta, dispersion=1.0, offset=None, fit_intercept=False, want_H=True, want_w=False, want_stats=False):
+    """One Gamma partition (log link) at a fixed beta and dispersion > 0 (dlsa_gamma_pass_f64): eta = [1 | X] beta + offset, mu = exp(eta),
+    r = y / mu.  Arguments as poisson_pass.  Returns (H [pe,pe] = [1 | X]' diag(r) [1 | X] / dispersion or None, g [pe] = [1 | X]'(r - 1)
+    / dispersion, loglik [1] = the full log-likelihood at that dispersion, w [n] = r or None, stats [2] = (Pearson sum (r - 1)^2,
+    deviance 2 sum (r - 1 - log r)) or None (with want_stats))."""
+    lib = _lib.load()
+    _require_gpu(X, y, beta, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
+    n, p = X.shape
+    icpt = 1 if fit_intercept else 0
+    pe = p + icpt
+    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
+        raise ValueError("gamma_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
+    dispersion = _dispersion_positive("gamma_pass", dispersion)
+    H, g, ll, w, st = out = _pass_out(pe, n, X.device, want_H, want_w, want_stats=want_stats)
+    ws = _workspace(lib.dlsa_gamma_workspace_bytes(n, p, icpt, 1), X.device)
+    check(lib.dlsa_gamma_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), dispersion, n, p, icpt, _ptr(H), pe, _ptr(g),
+                                  _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def gamma_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, dispersion=None, tol=1e-13, max_iter=100):
+    """Per-partition Gamma fit with a log link (dlsa_gamma_fit_f64): partitions, offset and intercept as poisson_fit_ex.
+    dispersion=None estimates every partition's own dispersion (Pearson: P / (rows - pe)); dispersion > 0 gives every block that
+    fixed dispersion.  The result dict of poisson_fit_ex -- Sig_inv is the information divided by the dispersion used, `loglik` the
+    full log-likelihood at (coef, that dispersion) -- plus the per-partition lists `dispersion`, `pearson`, `deviance` and `df`."""
+    lib = _lib.load()
+    _require_gpu(X, y, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
+    n, p = X.shape
+    if y.numel() != n or (offset is not None and offset.numel() != n):
+        raise ValueError("gamma_fit_ex: y and offset must have n = %d elements" % n)
+    dispersion = _dispersion_fixed("gamma_fit_ex", dispersion)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("gamma_fit_ex", part_first, part_rows, row_step, n)
+    icpt = 1 if fit_intercept else 0
+    out = _FitOut(K, p + icpt, X.device, dispersion=GAMMA_LISTS)
+    ws = _workspace(lib.dlsa_gamma_workspace_bytes(max_rows, p, icpt, step), X.device)
+    rc = lib.dlsa_gamma_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, dispersion, tol, max_iter,
+                                *out.args, _ptr(ws), ws.numel(), _stream())
+    return _gamma_result(out, rc, c_rows, p + icpt)
 
 
 def negbin_special(theta, y):
@@ -1239,6 +1308,40 @@ def onehot_negbin_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1,
     rc = lib.dlsa_onehot_negbin_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, alpha, tol,
                                         max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
     return out.result(rc)
+
+
+def onehot_gamma_pass(plan, num, codes, y, beta, dispersion=1.0, offset=None, want_H=True, want_w=False, want_stats=False):
+    """gamma_pass on the raw representation of a one-hot design (dlsa_onehot_gamma_pass_f64): rows and beta as onehot_poisson_pass,
+    dispersion > 0 as gamma_pass.  Returns (H [p,p] = X' diag(r) X / dispersion or None, g [p], loglik [1] = the full log-likelihood,
+    w [n] = r or None, stats [2] = (Pearson, deviance) or None (with want_stats)) of the matrix dlsa_design_f64 would build -- which is
+    never built."""
+    lib = _lib.load()
+    _require_gpu(beta)
+    _f64(beta, "beta")
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_gamma_pass")
+    p = plan.p
+    if n < 1 or beta.numel() != p:
+        raise ValueError("onehot_gamma_pass: need n >= 1 rows and beta with %d elements" % p)
+    dispersion = _dispersion_positive("onehot_gamma_pass", dispersion)
+    H, g, ll, w, st = out = _pass_out(p, n, y.device, want_H, want_w, want_stats=want_stats)
+    ws = _workspace(lib.dlsa_onehot_gamma_workspace_bytes(plan._h, n, 1), y.device)
+    check(lib.dlsa_onehot_gamma_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), dispersion, n, _ptr(H), p,
+                                         _ptr(g), _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def onehot_gamma_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, dispersion=None, tol=1e-13, max_iter=100):
+    """gamma_fit_ex on the raw representation of a one-hot design (dlsa_onehot_gamma_fit_f64): partitions as onehot_poisson_fit_ex,
+    dispersion as gamma_fit_ex.  Same result dict as gamma_fit_ex, plan.p columns in the plan's order."""
+    lib = _lib.load()
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_gamma_fit_ex")
+    dispersion = _dispersion_fixed("onehot_gamma_fit_ex", dispersion)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_gamma_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, plan.p, y.device, dispersion=GAMMA_LISTS)
+    ws = _workspace(lib.dlsa_onehot_gamma_workspace_bytes(plan._h, max_rows, step), y.device)
+    rc = lib.dlsa_onehot_gamma_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, dispersion, tol,
+                                       max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
+    return _gamma_result(out, rc, c_rows, plan.p)
 
 
 class RcclComm:

@@ -73,8 +73,10 @@ def _column_names(names, p, fit_intercept):
 
 
 def _blocks(r, names, n):
-    """MappedBlocks of an engine fit's result dict (the NB2 fits' dispersion lists go to `extra`)."""
+    """MappedBlocks of an engine fit's result dict (the NB2 and Gamma fits' dispersion lists go to `extra`)."""
     extra = {k: r[k] for k in ("alpha", "alpha_info", "pearson")} if "alpha" in r else None
+    if "dispersion" in r:
+        extra = {k: r[k] for k in ("dispersion", "pearson", "deviance", "df")}
     return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n,
                         extra=extra)
 
@@ -920,5 +922,118 @@ def negbin_model_eval(sample_df, Y_name, par, alpha, fit_intercept=False, offset
 
     def onehot_pass(plan, num, codes, y, b, **kw):
         return engine.onehot_negbin_pass(plan, num, codes, y, b, alpha, **kw)
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)
+
+
+# ---------------------------------------------------------------------------------------------
+# Gamma regression map step (log link) for positive, right-skewed continuous responses: claim severity, cost, duration, delay --
+# the severity half of the frequency / severity pair whose frequency half is the Poisson / NB2 step above.  Var y = phi mu^2.  beta^
+# does not depend on the dispersion phi, the information does: Sig_inv = [1 | X]' diag(y / mu) [1 | X] / phi.  So every partition
+# estimates its own phi (Pearson: P / (n - p)) for its block, the combine's weights and the AIC / BIC choice then carry the right
+# scale, and dlsa_mapred / dlsa apply unchanged.
+# ---------------------------------------------------------------------------------------------
+def simulate_gamma(sample_size, p, partition_num, shape, seed=20260101, base_mean=1.0, coef_value=0.5, exposure=False):
+    """simulate_poisson's rows and frame with a positive continuous response: y ~ Gamma(shape, scale mu / shape) (mean mu, dispersion
+    1 / shape) with mu = base_mean * exposure * exp(x beta*)."""
+    n, p, shape = int(sample_size), int(p), float(shape)
+    if not shape > 0:
+        raise ValueError("simulate_gamma: shape must be positive")
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    X = X.cpu().numpy()
+    beta = np.zeros(p)
+    beta[:int(0.4 * p)] = float(coef_value)
+    rng = np.random.default_rng(seed)
+    e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
+    mu = float(base_mean) * e * np.exp(X @ beta)
+    y = rng.gamma(shape, mu / shape)
+    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
+    return pd.DataFrame(np.concatenate(cols, 1),
+                        columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
+
+
+def _gamma_rows(who, y, n, offset, exposure, dispersion, device):
+    """The responses and the offset of a Gamma fit of n rows as the engine takes them: (y fp64 contiguous, offset fp64 or None), on
+    `device`; ValueError for a wrong length, a response that is not positive, a bad offset / exposure or a bad `dispersion=`."""
+    if dispersion is not None and not 0.0 < float(dispersion) < float("inf"):
+        raise ValueError("%s: dispersion must be positive and finite (None estimates it)" % who)
+    y = torch.as_tensor(y, device=device).to(torch.float64).contiguous()
+    if y.numel() != n:
+        raise ValueError("%s: y must have n = %d elements" % (who, n))
+    if not bool(((y > 0) & torch.isfinite(y)).all()):                 # (NaN fails y > 0)
+        raise ValueError("%s: the response must be positive and finite" % who)
+    return y, _poisson_offset(offset, exposure, n, device)
+
+
+def fit_gamma_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, dispersion=None,
+                         names=None, tol=1e-13, max_iter=100):
+    """Gamma (log link) map step for the partitions of one device-resident shard; arguments as fit_poisson_partitions, y > 0.
+    dispersion=None estimates every partition's own dispersion (Pearson) for its block; dispersion > 0 gives every block that common
+    dispersion (e.g. combine_gamma_dispersion of a first map step).  Returns MappedBlocks with `loglik` = the full log-likelihood per
+    partition at the dispersion used and `extra` = {"dispersion", "pearson", "deviance", "df"} per partition."""
+    if not X.is_cuda:
+        raise RuntimeError("fit_gamma_partitions runs on the GPU only (no CPU fallback)")
+    if X.dtype != torch.float64:
+        raise TypeError("fit_gamma_partitions: X must be float64, got %s" % X.dtype)
+    n, p = X.shape
+    y, offset = _gamma_rows("fit_gamma_partitions", y, n, offset, exposure, dispersion, X.device)
+    names = _column_names(names, p, fit_intercept)
+    first, rows, step = _partitions(n, partition_num, part_offsets)
+    r = engine.gamma_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept,
+                            dispersion=dispersion, tol=tol, max_iter=max_iter)
+    return _blocks(r, names, n)
+
+
+def fit_gamma_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, dispersion=None,
+                     structured=True, tol=1e-13, max_iter=100):
+    """Gamma map step for a design given by its RAW columns, the sibling of fit_poisson_design: num [n, q] fp64, codes [n, f] int32
+    level codes and responses y [n] > 0, all on the GPU.  With structured=True and a qualifying design (spec.onehot_plan()) the fit
+    runs on the raw representation -- the dense [n, p] matrix is never built; otherwise the matrix is built once by the design kernel
+    and the dense Gamma fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and `exposure` as
+    fit_poisson_partitions, dispersion as fit_gamma_partitions.  Same MappedBlocks either way (names = spec.names)."""
+    if not torch.is_tensor(y) or not y.is_cuda:
+        raise RuntimeError("fit_gamma_design runs on the GPU only (no CPU fallback)")
+    if num is not None and num.dtype != torch.float64:
+        raise TypeError("fit_gamma_design: num must be float64, got %s" % num.dtype)
+    y, offset = _gamma_rows("fit_gamma_design", y, y.numel(), offset, exposure, dispersion, y.device)
+    return _fit_design(engine.onehot_gamma_fit_ex, engine.gamma_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
+                       offset=offset, dispersion=dispersion, tol=tol, max_iter=max_iter)
+
+
+def combine_gamma_dispersion(mb):
+    """The common dispersion of a Gamma map step: the pooled Pearson estimate sum_k P_k / sum_k (n_k - p) over the partitions with
+    status OK -- the exact one-round combine of the dispersion, to be passed as `dispersion=` to a second map step.  NaN when no
+    partition qualifies."""
+    P, df = mb.extra["pearson"], mb.extra["df"]
+    use = [k for k in range(len(P)) if mb.status[k] == 0 and df[k] > 0]
+    if not use:
+        return float("nan")
+    return float(sum(P[k] for k in use) / sum(df[k] for k in use))
+
+
+def gamma_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, dispersion=None, dummy_info=[],
+                dummy_factors_baseline=[], data_info=[], structured=False):
+    """Frame-level sibling of poisson_model for a positive continuous response: one partition (a pandas frame) with the response
+    column Y_name and optionally an offset or an exposure column; dispersion as fit_gamma_partitions.  Returns the p x (3+p) frame
+    `par_id, coef, Sig_invMcoef, [intercept,] <features>` with the dispersion used in `out.attrs["dispersion"]`; a chunk that lacks an
+    expected dummy level returns the all-zero block with a warning.  structured=True with a dummy_info and a qualifying design fits
+    on the raw numerics + level codes (fit_gamma_design); the default is the dense path."""
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    out, mb = _count_model("gamma_model", fit_gamma_design, fit_gamma_partitions, structured, chunk, dispersion=dispersion)
+    out.attrs["dispersion"] = mb.extra["dispersion"][0] if mb is not None else 0.0      # (a skipped chunk's all-zero block: 0)
+    return out
+
+
+def gamma_model_eval(sample_df, Y_name, par, dispersion, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                     dummy_factors_baseline=[], data_info=[], structured=False):
+    """Gamma log-likelihood at dispersion > 0 of every estimator column of `par` on one partition, shaped like poisson_model_eval's
+    output: one row, a column per estimator (one pass without the information per column).  structured=True with a dummy_info and a
+    qualifying design evaluates on the raw numerics + level codes; the default is the dense path."""
+    def dense_pass(X, y, b, **kw):
+        return engine.gamma_pass(X, y, b, dispersion, **kw)
+
+    def onehot_pass(plan, num, codes, y, b, **kw):
+        return engine.onehot_gamma_pass(plan, num, codes, y, b, dispersion, **kw)
     chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
     return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)

@@ -364,6 +364,39 @@ int dlsa_negbin_fit_f64(const double* X, int64_t ldx, const double* y, const dou
                         void* ws, size_t ws_bytes, void* stream);
 int dlsa_negbin_special_f64(const double* theta, const double* y, int64_t n, double* out, void* stream);
 
+/* ---- Gamma regression map step (log link; positive, right-skewed continuous responses: severity, cost, duration) ---------
+ * y_i ~ Gamma(shape nu = 1 / phi, mean mu_i), Var y = phi mu^2, log mu_i = eta_i = [1 | x_i]' beta + o_i.  intercept and offset as
+ * the Poisson entries; responses are doubles, y > 0.  With r = y / mu: loglik(beta, phi) = nu sum(-r - eta) + n (nu log nu -
+ * lgamma nu) + (nu - 1) sum log y, g = nu [1 | X]'(r - 1), H = nu [1 | X]' diag(r) [1 | X] (the observed information, positive
+ * semi-definite everywhere: the negative log-likelihood is convex in beta).  Pearson sum P = sum (r - 1)^2, deviance Dev =
+ * 2 sum (r - 1 - log r); the estimated dispersion of a partition of n rows and pe coefficients is P / (n - pe).
+ * dlsa_gamma_pass_f64 at a fixed beta and dispersion > 0 (finite; otherwise DLSA_ERR_INVALID), one read of the rows (+ the Gram when
+ * H is wanted): H (nullable, ldh >= p + intercept, both triangles), g (nullable) and loglik (1 value, nullable; NaN when a response
+ * is not positive or a response / offset is not finite) of loglik(beta, phi) at that dispersion -- 1.0 gives the unit-dispersion
+ * quantities --, w_out = r (n, nullable), stats_out (2 device doubles, nullable) = [P, Dev] at this beta.  The data of the pass are
+ * not checked otherwise.  mu overflows to +inf above eta = 709.78 (r = 0) and is 0 below eta = -746 (r = +inf, loglik = -inf).
+ * dlsa_gamma_fit_f64: partitions as dlsa_poisson_fit_f64 (strided i % K partitions read in place, their responses and offsets
+ * gathered into the workspace).  Newton from beta = 0 with the intercept at log(sum y e^-o / n), the safeguards and the stopping
+ * rule of dlsa_poisson_fit_f64; beta does not depend on the dispersion.  dispersion_fixed > 0 (finite): every partition's block
+ * uses it; dispersion_fixed <= 0: each partition's own P / (n - pe), from the mu of the evaluation that produced the returned H.
+ * Outputs as dlsa_poisson_fit_f64 with Sig_inv = H at coef divided by the dispersion used (a dispersion that is not positive and
+ * finite leaves the unit-dispersion block), loglik_host the full log-likelihood at (coef, the dispersion used); dispersion_host,
+ * pearson_host and deviance_host are host arrays of K (each nullable): the dispersion used, P and Dev at coef (0 for a partition
+ * without rows).  A response <= 0 or not finite, or a non-finite offset, returns DLSA_ERR_INVALID naming the partition; so does,
+ * with the dispersion estimated, a partition of 0 < n <= p + intercept rows (no degrees of freedom), before any partition is
+ * fitted.  A partition without rows is DLSA_PART_EMPTY with the all-zero block; a collinear column gives DLSA_PART_NOT_SPD, an
+ * exhausted budget DLSA_PART_NOT_CONVERGED with the evaluated iterate, its information and its dispersion.  Workspace:
+ * dlsa_gamma_workspace_bytes(max rows, p, intercept, row_step); the pass takes the same query with row_step = 1. */
+size_t dlsa_gamma_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step);
+int dlsa_gamma_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, double dispersion,
+                        int64_t n, int p, int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w_out,
+                        double* stats_out, void* ws, size_t ws_bytes, void* stream);
+int dlsa_gamma_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
+                       const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double dispersion_fixed,
+                       double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host,
+                       int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
+                       double* deviance_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a9: local sum of partition blocks before the one-round all-reduce (dlsa.py:30-34) -
  * out = [ sum_k Sig_inv (p*p) | sum_k Sig_invMcoef (p) | sum_k coef (p) ] contiguous,
  * the message a rank contributes to the RCCL all-reduce.  Blocks whose status is not OK may
@@ -564,6 +597,32 @@ int dlsa_onehot_negbin_fit_f64(const dlsa_onehot_plan* plan, const double* num, 
                                double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                                double* loglik_host, double* alpha_host, double* alpha_info_host, double* pearson_host, void* ws,
                                size_t ws_bytes, void* stream);
+
+/* ---- Gamma map step on the raw representation of a one-hot design (the structured sibling of dlsa_gamma_*_f64) ----------
+ * Rows, plan, column order and unknown codes as dlsa_onehot_poisson_*_f64; the model, the outputs and their meaning as
+ * dlsa_gamma_*_f64 (intercept = 0) on the matrix dlsa_design_f64 would build, which is never built.
+ * dlsa_onehot_gamma_pass_f64 at a fixed beta and dispersion > 0 (finite; otherwise DLSA_ERR_INVALID), n >= 1: H (nullable,
+ * ldh >= p), g (nullable) and loglik (1 value, nullable; NaN for an invalid response or offset) at that dispersion, w_out = r =
+ * y / mu (n, nullable), stats_out = [P, Dev] (2 values, nullable).  One read of the raw rows (8q + 4f + 32 bytes per row with an
+ * offset), the sums over (y, mu) when stats_out is wanted, and the structured Gram when H is wanted, which sums r in ordered
+ * floating point; g, loglik, H, P and Dev are bit-reproducible.
+ * dlsa_onehot_gamma_fit_f64: partitions as dlsa_onehot_poisson_fit_f64 (num and codes of a strided partition read in place, its
+ * responses and offsets gathered once), the fit of dlsa_gamma_fit_f64 -- the intercept that starts at log(sum y e^-o / n) is the
+ * plan's constant column, if it has one; dispersion_fixed as there --, the same outputs, statuses and refusals (DLSA_ERR_INVALID
+ * naming the partition for an invalid response or offset, or 0 < n <= plan.p rows under an estimated dispersion).
+ * Workspace: dlsa_onehot_gamma_workspace_bytes(plan, max rows, row_step) (0 for a null plan, max_rows < 0 or row_step < 1); the
+ * pass takes the same query with row_step = 1. */
+size_t dlsa_onehot_gamma_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows, int64_t row_step);
+int dlsa_onehot_gamma_pass_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                               const double* y, const double* offset, const double* beta, double dispersion, int64_t n, double* H,
+                               int64_t ldh, double* g, double* loglik, double* w_out, double* stats_out, void* ws, size_t ws_bytes,
+                               void* stream);
+int dlsa_onehot_gamma_fit_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                              const double* y, const double* offset, const int64_t* part_first_host,
+                              const int64_t* part_rows_host, int64_t row_step, int K, double dispersion_fixed, double tol,
+                              int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
+                              double* loglik_host, double* dispersion_host, double* pearson_host, double* deviance_host, void* ws,
+                              size_t ws_bytes, void* stream);
 
 /* test hook: host-only validation of the Gram tile plan for p (0 = every tile on/above the diagonal
  * is stored exactly once; outputs: workgroup items, tile slots computed, tiles stored). */
