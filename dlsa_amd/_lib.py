@@ -108,6 +108,13 @@ SIGNATURES = {
                                    c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                    ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
                                    c_vp, c_sz, c_vp]),
+    "dlsa_tweedie_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
+    "dlsa_tweedie_pass_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_sz, c_vp]),
+    "dlsa_tweedie_fit_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_i64, c_int, c_int, c_int,
+                                     c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                     ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
+                                     c_vp, c_sz, c_vp]),
     "dlsa_sum_blocks_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp]),
     "dlsa_comm_unique_id": (c_int, [ctypes.c_char_p]),
     "dlsa_comm_init_rank": (c_int, [ctypes.POINTER(c_vp), c_int, ctypes.c_char_p, c_int]),
@@ -165,6 +172,13 @@ SIGNATURES = {
                                           c_i64, c_int, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int),
                                           ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
                                           ctypes.POINTER(c_dbl), c_vp, c_sz, c_vp]),
+    "dlsa_onehot_tweedie_workspace_bytes": (c_sz, [c_vp, c_i64, c_i64]),
+    "dlsa_onehot_tweedie_pass_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                             c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "dlsa_onehot_tweedie_fit_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                                            c_i64, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int),
+                                            ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
+                                            ctypes.POINTER(c_dbl), c_vp, c_sz, c_vp]),
     "dlsa_gram_plan_check": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "dlsa_gram_wide_plan_check": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "dlsa_newton_solve_probe_workspace_bytes": (c_sz, [c_int, c_int, c_int]),

@@ -121,22 +121,24 @@ __global__ void gamma_ll_fix_kernel(double* __restrict__ ll, const double* __res
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static int gamma_sum_blocks(int64_t n) { return (int)std::min<int64_t>(GAMMA_SUM_BLOCKS, std::max<int64_t>(1, (n + 255) / 256)); }
+int gamma_sum_blocks(int64_t n) { return (int)std::min<int64_t>(GAMMA_SUM_BLOCKS, std::max<int64_t>(1, (n + 255) / 256)); }
+
+int gamma_sum_finish(const double* part, int nblocks, int nq, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(gamma_sum_finish_kernel, dim3(1), dim3(256), 0, s, part, nblocks, nq, out);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
 
 int gamma_const(const double* y, const double* off, int64_t n, double* cpart, double* cst, hipStream_t s) {
     const int blocks = gamma_sum_blocks(n);
     hipLaunchKernelGGL(gamma_const_kernel, dim3(blocks), dim3(256), 0, s, y, off, n, cpart);
-    hipLaunchKernelGGL(gamma_sum_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cpart, blocks, GAMMA_NC, cst);
-    DLSA_HIP_CHECK(hipGetLastError());
-    return DLSA_OK;
+    return gamma_sum_finish(cpart, blocks, GAMMA_NC, cst, s);
 }
 
 int gamma_disp(const double* y, const double* mu, int64_t n, double* dpart, double* dst, hipStream_t s) {
     const int blocks = gamma_sum_blocks(n);
     hipLaunchKernelGGL(gamma_disp_kernel, dim3(blocks), dim3(256), 0, s, y, mu, n, dpart);
-    hipLaunchKernelGGL(gamma_sum_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)dpart, blocks, GAMMA_ND, dst);
-    DLSA_HIP_CHECK(hipGetLastError());
-    return DLSA_OK;
+    return gamma_sum_finish(dpart, blocks, GAMMA_ND, dst, s);
 }
 
 int gamma_scale(double* H, int64_t ldh, int pe, double* g, double nu, hipStream_t s) {

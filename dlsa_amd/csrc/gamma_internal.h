@@ -22,6 +22,11 @@ enum { GAMMA_PEARSON = 0, GAMMA_DEV = 1 };
 int gamma_const(const double* y, const double* off, int64_t n, double* cpart, double* cst, hipStream_t s);
 // dst[0..1] = the GAMMA_ND sums of n rows; dpart: GAMMA_ND * GAMMA_SUM_BLOCKS doubles of scratch.  Fixed-order: bit-reproducible
 int gamma_disp(const double* y, const double* mu, int64_t n, double* dpart, double* dst, hipStream_t s);
+// out[j] = the sum over b < nblocks of part[b * nq + j], j < nq <= 4, in a fixed order: the finish of gamma_const / gamma_disp and
+// of the Tweedie family's per-block sums (tweedie.hip)
+int gamma_sum_finish(const double* part, int nblocks, int nq, double* out, hipStream_t s);
+// the blocks of a per-block sum kernel over n rows: at most GAMMA_SUM_BLOCKS workgroups of 256 threads
+int gamma_sum_blocks(int64_t n);
 // H (pe x pe, pitch ldh; nullable) and g (pe; nullable) times nu: the unit-dispersion quantities taken to dispersion 1 / nu
 int gamma_scale(double* H, int64_t ldh, int pe, double* g, double nu, hipStream_t s);
 // n (nu log nu - lgamma nu): the beta-free part of the log-likelihood that does not depend on y

@@ -643,7 +643,7 @@ def _offset_partitions(who, part_offsets, n, ascending_from_zero=False):
 class _FitOut:
     """What a per-partition fit of K partitions with pe coefficients writes: coef / Sig_invMcoef [K, pe] and Sig_inv [K, pe, pe] on the
     device, n_iter / status / loglik on the host, and with `dispersion` the family's own host lists: True (NB2) alpha / alpha_info /
-    pearson, or their names (Gamma: GAMMA_LISTS).  `args` is the run of output arguments every dlsa_*_fit_* entry takes, in the C
+    pearson, or their names (Gamma and Tweedie: GAMMA_LISTS).  `args` is the run of output arguments every dlsa_*_fit_* entry takes, in the C
     ABI's order; result(rc) is the wrappers' result dict."""
 
     def __init__(self, K, pe, device, dispersion=False):
@@ -663,7 +663,7 @@ class _FitOut:
 
 def _pass_out(pe, n, device, want_H, want_w, negbin=False, want_theta=False, want_stats=None):
     """The outputs of one pass at a fixed beta, in the order the pass wrappers return them: (H [pe, pe] or None, g [pe], loglik [1],
-    w [n] or None), for NB2 (..., mu [n] or None -- with want_w --, theta_terms [3] or None) and for Gamma (want_stats not None:
+    w [n] or None), for NB2 (..., mu [n] or None -- with want_w --, theta_terms [3] or None) and for Gamma and Tweedie (want_stats not None:
     ..., stats [2] or None)."""
     def new(shape, want=True):
         return torch.empty(shape, dtype=torch.float64, device=device) if want else None
@@ -959,6 +959,60 @@ def gamma_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_inter
     ws = _workspace(lib.dlsa_gamma_workspace_bytes(max_rows, p, icpt, step), X.device)
     rc = lib.dlsa_gamma_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, dispersion, tol, max_iter,
                                 *out.args, _ptr(ws), ws.numel(), _stream())
+    return _gamma_result(out, rc, c_rows, p + icpt)
+
+
+def tweedie_power(who, power):
+    """The variance power of a Tweedie entry: a float strictly between 1 and 2 (ValueError otherwise; NaN fails)."""
+    power = float(power)
+    if not 1.0 < power < 2.0:
+        raise ValueError("%s: power must lie strictly between 1 and 2, got %r" % (who, power))
+    return power
+
+
+def tweedie_pass(X, y, beta, power, dispersion=1.0, offset=None, fit_intercept=False, want_H=True, want_w=False, want_stats=False):
+    """One Tweedie partition (log link, Var y = dispersion * mu^power, 1 < power < 2) at a fixed beta and dispersion > 0
+    (dlsa_tweedie_pass_f64): eta = [1 | X] beta + offset, mu = exp(eta), a = mu^(1 - power), b = mu^(2 - power).  Arguments as
+    poisson_pass, y >= 0.  Returns (H [pe,pe] = [1 | X]' diag(w) [1 | X] / dispersion or None, g [pe] = [1 | X]'(y a - b) / dispersion,
+    loglik [1] = the QUASI-log-likelihood sum (y a / (1 - power) - b / (2 - power)) / dispersion -- the series factor of the density
+    is not computed, so it compares values of beta at one (power, dispersion) only --, w [n] = (power - 1) y a + (2 - power) b or
+    None, stats [2] = (Pearson sum (y - mu)^2 mu^-power, deviance) or None (with want_stats))."""
+    lib = _lib.load()
+    _require_gpu(X, y, beta, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
+    n, p = X.shape
+    icpt = 1 if fit_intercept else 0
+    pe = p + icpt
+    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
+        raise ValueError("tweedie_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
+    power = tweedie_power("tweedie_pass", power)
+    dispersion = _dispersion_positive("tweedie_pass", dispersion)
+    H, g, ll, w, st = out = _pass_out(pe, n, X.device, want_H, want_w, want_stats=want_stats)
+    ws = _workspace(lib.dlsa_tweedie_workspace_bytes(n, p, icpt, 1), X.device)
+    check(lib.dlsa_tweedie_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), power, dispersion, n, p, icpt, _ptr(H), pe,
+                                    _ptr(g), _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def tweedie_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, power=1.5, dispersion=None, tol=1e-13,
+                   max_iter=100):
+    """Per-partition Tweedie fit with a log link at the variance power `power` (dlsa_tweedie_fit_f64; 1 < power < 2, given, not
+    estimated): partitions, offset and intercept as poisson_fit_ex, dispersion as gamma_fit_ex.  The result dict of gamma_fit_ex
+    (`dispersion`, `pearson`, `deviance`, `df`); `loglik` is the quasi-log-likelihood at (coef, the dispersion used)."""
+    lib = _lib.load()
+    _require_gpu(X, y, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
+    n, p = X.shape
+    if y.numel() != n or (offset is not None and offset.numel() != n):
+        raise ValueError("tweedie_fit_ex: y and offset must have n = %d elements" % n)
+    power = tweedie_power("tweedie_fit_ex", power)
+    dispersion = _dispersion_fixed("tweedie_fit_ex", dispersion)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("tweedie_fit_ex", part_first, part_rows, row_step, n)
+    icpt = 1 if fit_intercept else 0
+    out = _FitOut(K, p + icpt, X.device, dispersion=GAMMA_LISTS)
+    ws = _workspace(lib.dlsa_tweedie_workspace_bytes(max_rows, p, icpt, step), X.device)
+    rc = lib.dlsa_tweedie_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, power, dispersion, tol,
+                                  max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
     return _gamma_result(out, rc, c_rows, p + icpt)
 
 
@@ -1341,6 +1395,44 @@ def onehot_gamma_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, 
     ws = _workspace(lib.dlsa_onehot_gamma_workspace_bytes(plan._h, max_rows, step), y.device)
     rc = lib.dlsa_onehot_gamma_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, dispersion, tol,
                                        max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
+    return _gamma_result(out, rc, c_rows, plan.p)
+
+
+def onehot_tweedie_pass(plan, num, codes, y, beta, power, dispersion=1.0, offset=None, want_H=True, want_w=False, want_stats=False):
+    """tweedie_pass on the raw representation of a one-hot design (dlsa_onehot_tweedie_pass_f64): rows and beta as
+    onehot_poisson_pass, power and dispersion as tweedie_pass.  Returns (H [p,p] or None, g [p], loglik [1] = the
+    quasi-log-likelihood, w [n] or None, stats [2] = (Pearson, deviance) or None (with want_stats)) of the matrix dlsa_design_f64
+    would build -- which is never built."""
+    lib = _lib.load()
+    _require_gpu(beta)
+    _f64(beta, "beta")
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_tweedie_pass")
+    p = plan.p
+    if n < 1 or beta.numel() != p:
+        raise ValueError("onehot_tweedie_pass: need n >= 1 rows and beta with %d elements" % p)
+    power = tweedie_power("onehot_tweedie_pass", power)
+    dispersion = _dispersion_positive("onehot_tweedie_pass", dispersion)
+    H, g, ll, w, st = out = _pass_out(p, n, y.device, want_H, want_w, want_stats=want_stats)
+    ws = _workspace(lib.dlsa_onehot_tweedie_workspace_bytes(plan._h, n, 1), y.device)
+    check(lib.dlsa_onehot_tweedie_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), power, dispersion, n,
+                                           _ptr(H), p, _ptr(g), _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def onehot_tweedie_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, power=1.5, dispersion=None, tol=1e-13,
+                          max_iter=100):
+    """tweedie_fit_ex on the raw representation of a one-hot design (dlsa_onehot_tweedie_fit_f64): partitions as
+    onehot_poisson_fit_ex, power and dispersion as tweedie_fit_ex.  Same result dict as tweedie_fit_ex, plan.p columns in the plan's
+    order."""
+    lib = _lib.load()
+    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_tweedie_fit_ex")
+    power = tweedie_power("onehot_tweedie_fit_ex", power)
+    dispersion = _dispersion_fixed("onehot_tweedie_fit_ex", dispersion)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_tweedie_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, plan.p, y.device, dispersion=GAMMA_LISTS)
+    ws = _workspace(lib.dlsa_onehot_tweedie_workspace_bytes(plan._h, max_rows, step), y.device)
+    rc = lib.dlsa_onehot_tweedie_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, power,
+                                         dispersion, tol, max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
     return _gamma_result(out, rc, c_rows, plan.p)
 
 

@@ -73,7 +73,7 @@ def _column_names(names, p, fit_intercept):
 
 
 def _blocks(r, names, n):
-    """MappedBlocks of an engine fit's result dict (the NB2 and Gamma fits' dispersion lists go to `extra`)."""
+    """MappedBlocks of an engine fit's result dict (the NB2, Gamma and Tweedie fits' dispersion lists go to `extra`)."""
     extra = {k: r[k] for k in ("alpha", "alpha_info", "pearson")} if "alpha" in r else None
     if "dispersion" in r:
         extra = {k: r[k] for k in ("dispersion", "pearson", "deviance", "df")}
@@ -1005,6 +1005,12 @@ def combine_gamma_dispersion(mb):
     """The common dispersion of a Gamma map step: the pooled Pearson estimate sum_k P_k / sum_k (n_k - p) over the partitions with
     status OK -- the exact one-round combine of the dispersion, to be passed as `dispersion=` to a second map step.  NaN when no
     partition qualifies."""
+    return _pooled_pearson_dispersion(mb)
+
+
+def _pooled_pearson_dispersion(mb):
+    """sum_k P_k / sum_k df_k over the partitions with status OK and df_k > 0 (NaN without one), from a map step whose `extra` holds
+    `pearson` and `df`: the Gamma and the Tweedie fits'."""
     P, df = mb.extra["pearson"], mb.extra["df"]
     use = [k for k in range(len(P)) if mb.status[k] == 0 and df[k] > 0]
     if not use:
@@ -1035,5 +1041,133 @@ def gamma_model_eval(sample_df, Y_name, par, dispersion, fit_intercept=False, of
 
     def onehot_pass(plan, num, codes, y, b, **kw):
         return engine.onehot_gamma_pass(plan, num, codes, y, b, dispersion, **kw)
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)
+
+
+# ---------------------------------------------------------------------------------------------
+# Tweedie (compound Poisson-Gamma) map step, log link, variance power 1 < xi < 2: a response that is exactly zero for many rows and
+# positive, right-skewed for the rest -- pure premium, cost per policy, rainfall, spend per visitor: the frequency / severity pair
+# above as one model.  Var y = phi mu^xi.  xi is given by the caller.  beta^ does not depend on phi, the information does: Sig_inv =
+# [1 | X]' diag((xi - 1) y mu^(1 - xi) + (2 - xi) mu^(2 - xi)) [1 | X] / phi, so every partition estimates its own phi (Pearson) for its
+# block, as the Gamma step does, and dlsa_mapred / dlsa apply unchanged.  `loglik` is the quasi-log-likelihood (the part of the log
+# density that depends on beta): the series factor of the Tweedie density is out of scope, and with it a full likelihood, AIC
+# across xi and a profile estimate of xi.
+# ---------------------------------------------------------------------------------------------
+def simulate_tweedie(sample_size, p, partition_num, power, dispersion, seed=20260101, base_mean=1.0, coef_value=0.5, exposure=False):
+    """simulate_poisson's rows and frame with a compound Poisson-Gamma response of mean mu = base_mean * exposure * exp(x beta*) and
+    variance dispersion * mu^power: N ~ Poisson(mu^(2 - power) / (dispersion (2 - power))), y = the sum of N Gamma draws = Gamma(shape
+    N (2 - power) / (power - 1), scale dispersion (power - 1) mu^(power - 1)), y = 0 at N = 0."""
+    n, p = int(sample_size), int(p)
+    xi, phi = engine.tweedie_power("simulate_tweedie", power), float(dispersion)
+    if not 0.0 < phi < float("inf"):
+        raise ValueError("simulate_tweedie: dispersion must be positive and finite")
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    X = X.cpu().numpy()
+    beta = np.zeros(p)
+    beta[:int(0.4 * p)] = float(coef_value)
+    rng = np.random.default_rng(seed)
+    e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
+    mu = float(base_mean) * e * np.exp(X @ beta)
+    y = _tweedie_draw(rng, mu, xi, phi)
+    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
+    return pd.DataFrame(np.concatenate(cols, 1),
+                        columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
+
+
+def _tweedie_draw(rng, mu, power, dispersion):
+    """Compound Poisson-Gamma draws with mean mu (an array) and variance dispersion * mu^power, 1 < power < 2."""
+    N = rng.poisson(mu ** (2.0 - power) / (dispersion * (2.0 - power)))
+    draws = rng.gamma(np.maximum(N, 1) * ((2.0 - power) / (power - 1.0)), dispersion * (power - 1.0) * mu ** (power - 1.0))
+    return np.where(N > 0, draws, 0.0)
+
+
+def _tweedie_rows(who, y, n, offset, exposure, power, dispersion, device):
+    """The responses and the offset of a Tweedie fit of n rows as the engine takes them: (y fp64 contiguous, offset fp64 or None), on
+    `device`; ValueError for a wrong length, a response that is negative or not finite, no positive response at all, a bad offset /
+    exposure, a `power=` outside (1, 2) or a bad `dispersion=`."""
+    engine.tweedie_power(who, power)
+    if dispersion is not None and not 0.0 < float(dispersion) < float("inf"):
+        raise ValueError("%s: dispersion must be positive and finite (None estimates it)" % who)
+    y = torch.as_tensor(y, device=device).to(torch.float64).contiguous()
+    if y.numel() != n:
+        raise ValueError("%s: y must have n = %d elements" % (who, n))
+    if not bool(((y >= 0) & torch.isfinite(y)).all()):                # (NaN fails y >= 0)
+        raise ValueError("%s: the response must be non-negative and finite" % who)
+    if n > 0 and not bool((y > 0).any()):
+        raise ValueError("%s: no response is positive: the fit runs off to mu = 0" % who)
+    return y, _poisson_offset(offset, exposure, n, device)
+
+
+def fit_tweedie_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, power=1.5,
+                           dispersion=None, names=None, tol=1e-13, max_iter=100):
+    """Tweedie (log link, Var y = dispersion * mu^power, 1 < power < 2 given) map step for the partitions of one device-resident
+    shard; arguments as fit_poisson_partitions, y >= 0 with at least one positive response in every partition.  dispersion as
+    fit_gamma_partitions (None: every partition's own Pearson estimate; > 0: that common one, e.g. combine_tweedie_dispersion of a
+    first map step).  Returns MappedBlocks with `loglik` = the quasi-log-likelihood per partition at the dispersion used (the density's
+    series factor is not computed) and `extra` = {"dispersion", "pearson", "deviance", "df"} per partition."""
+    if not X.is_cuda:
+        raise RuntimeError("fit_tweedie_partitions runs on the GPU only (no CPU fallback)")
+    if X.dtype != torch.float64:
+        raise TypeError("fit_tweedie_partitions: X must be float64, got %s" % X.dtype)
+    n, p = X.shape
+    y, offset = _tweedie_rows("fit_tweedie_partitions", y, n, offset, exposure, power, dispersion, X.device)
+    names = _column_names(names, p, fit_intercept)
+    first, rows, step = _partitions(n, partition_num, part_offsets)
+    r = engine.tweedie_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept, power=power,
+                              dispersion=dispersion, tol=tol, max_iter=max_iter)
+    return _blocks(r, names, n)
+
+
+def fit_tweedie_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, power=1.5,
+                       dispersion=None, structured=True, tol=1e-13, max_iter=100):
+    """Tweedie map step for a design given by its RAW columns, the sibling of fit_gamma_design: num [n, q] fp64, codes [n, f] int32
+    level codes and responses y [n] >= 0, all on the GPU.  With structured=True and a qualifying design (spec.onehot_plan()) the fit
+    runs on the raw representation -- the dense [n, p] matrix is never built; otherwise the matrix is built once by the design kernel
+    and the dense Tweedie fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and `exposure` as
+    fit_poisson_partitions, power and dispersion as fit_tweedie_partitions.  Same MappedBlocks either way (names = spec.names)."""
+    if not torch.is_tensor(y) or not y.is_cuda:
+        raise RuntimeError("fit_tweedie_design runs on the GPU only (no CPU fallback)")
+    if num is not None and num.dtype != torch.float64:
+        raise TypeError("fit_tweedie_design: num must be float64, got %s" % num.dtype)
+    y, offset = _tweedie_rows("fit_tweedie_design", y, y.numel(), offset, exposure, power, dispersion, y.device)
+    return _fit_design(engine.onehot_tweedie_fit_ex, engine.tweedie_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
+                       offset=offset, power=power, dispersion=dispersion, tol=tol, max_iter=max_iter)
+
+
+def combine_tweedie_dispersion(mb):
+    """The common dispersion of a Tweedie map step: the pooled Pearson estimate sum_k P_k / sum_k (n_k - p) over the partitions with
+    status OK, as combine_gamma_dispersion -- to be passed as `dispersion=` to a second map step.  NaN when no partition qualifies."""
+    return _pooled_pearson_dispersion(mb)
+
+
+def tweedie_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, power=1.5, dispersion=None,
+                  dummy_info=[], dummy_factors_baseline=[], data_info=[], structured=False):
+    """Frame-level sibling of gamma_model for a non-negative response with exact zeros: one partition (a pandas frame) with the
+    response column Y_name and optionally an offset or an exposure column; power and dispersion as fit_tweedie_partitions.  Returns
+    the p x (3+p) frame `par_id, coef, Sig_invMcoef, [intercept,] <features>` with the dispersion used in `out.attrs["dispersion"]`
+    and the power in `out.attrs["power"]`; a chunk that lacks an expected dummy level returns the all-zero block with a warning.
+    structured=True with a dummy_info and a qualifying design fits on the raw numerics + level codes (fit_tweedie_design); the
+    default is the dense path."""
+    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
+    out, mb = _count_model("tweedie_model", fit_tweedie_design, fit_tweedie_partitions, structured, chunk, power=power,
+                           dispersion=dispersion)
+    out.attrs["dispersion"] = mb.extra["dispersion"][0] if mb is not None else 0.0      # (a skipped chunk's all-zero block: 0)
+    out.attrs["power"] = float(power)
+    return out
+
+
+def tweedie_model_eval(sample_df, Y_name, par, power, dispersion, fit_intercept=False, offset_name=None, exposure_name=None,
+                       dummy_info=[], dummy_factors_baseline=[], data_info=[], structured=False):
+    """Tweedie quasi-log-likelihood at (power, dispersion > 0) of every estimator column of `par` on one partition, shaped like
+    poisson_model_eval's output: one row, a column per estimator (one pass without the information per column).  The values compare
+    estimators at this (power, dispersion) only.  structured=True with a dummy_info and a qualifying design evaluates on the raw
+    numerics + level codes; the default is the dense path."""
+    def dense_pass(X, y, b, **kw):
+        return engine.tweedie_pass(X, y, b, power, dispersion, **kw)
+
+    def onehot_pass(plan, num, codes, y, b, **kw):
+        return engine.onehot_tweedie_pass(plan, num, codes, y, b, power, dispersion, **kw)
     chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
     return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)

@@ -397,6 +397,41 @@ int dlsa_gamma_fit_f64(const double* X, int64_t ldx, const double* y, const doub
                        int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
                        double* deviance_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Tweedie (compound Poisson-Gamma) regression map step (log link; responses that are exactly zero for many rows and
+ * positive, right-skewed for the rest: pure premium, cost per policy, rainfall) ---------
+ * Var y = phi mu^xi with the variance power xi = `power` given by the caller, 1 < xi < 2 (anything else, NaN included, is
+ * DLSA_ERR_INVALID; xi is not estimated), log mu_i = eta_i = [1 | x_i]' beta + o_i.  intercept and offset as the Poisson entries;
+ * responses are doubles, y >= 0.  With a = mu^(1 - xi), b = mu^(2 - xi), nu = 1 / phi: loglik(beta, phi) = nu sum (y a / (1 - xi) -
+ * b / (2 - xi)), g = nu [1 | X]'(y a - b), H = nu [1 | X]' diag((xi - 1) y a + (2 - xi) b) [1 | X] (the observed information; every
+ * weight is positive, so the negative log-likelihood is convex in beta).  loglik is the QUASI-log-likelihood, the part of the log
+ * density that depends on beta: the series factor log a(y, phi, xi) of the Tweedie density is not computed, so loglik compares
+ * values of beta at one (xi, phi) only.  Pearson sum P = sum (y - mu)^2 mu^-xi, deviance Dev = 2 sum (y^(2 - xi) / ((1 - xi)(2 - xi)) -
+ * y a / (1 - xi) + b / (2 - xi)) with the first term exactly 0 at y = 0; the estimated dispersion of a partition of n rows and pe
+ * coefficients is P / (n - pe).
+ * dlsa_tweedie_pass_f64 at a fixed beta, power and dispersion > 0 (finite; otherwise DLSA_ERR_INVALID), one read of the rows (+ the
+ * Gram when H is wanted): H (nullable, ldh >= p + intercept, both triangles), g (nullable) and loglik (1 value, nullable; NaN when
+ * a response is negative or a response / offset is not finite) at that dispersion -- 1.0 gives the unit-dispersion quantities --,
+ * w_out = (xi - 1) y a + (2 - xi) b (n, nullable), stats_out (2 device doubles, nullable) = [P, Dev] at this beta.  The data of the
+ * pass are not checked otherwise.
+ * dlsa_tweedie_fit_f64: partitions as dlsa_poisson_fit_f64 (strided i % K partitions read in place, their responses and offsets
+ * gathered into the workspace).  Newton from beta = 0 with the intercept at log(sum y e^((1 - xi) o) / sum e^((2 - xi) o)) (the MLE
+ * of the intercept-only model; log mean y without offsets), the safeguards and the stopping rule of dlsa_poisson_fit_f64; beta
+ * does not depend on the dispersion, it does on the power.  dispersion_fixed and the outputs as dlsa_gamma_fit_f64, with loglik_host
+ * the quasi-log-likelihood at (coef, the dispersion used).  DLSA_ERR_INVALID naming the partition: a response < 0 or not finite, a
+ * non-finite offset, a partition with rows but no positive response (its fit runs off to mu = 0) and, with the dispersion
+ * estimated, a partition of 0 < n <= p + intercept rows, before any partition is fitted.  DLSA_PART_EMPTY, DLSA_PART_NOT_SPD and
+ * DLSA_PART_NOT_CONVERGED as dlsa_gamma_fit_f64.  Workspace: dlsa_tweedie_workspace_bytes(max rows, p, intercept, row_step); the
+ * pass takes the same query with row_step = 1. */
+size_t dlsa_tweedie_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step);
+int dlsa_tweedie_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, double power,
+                          double dispersion, int64_t n, int p, int intercept, double* H, int64_t ldh, double* g, double* loglik,
+                          double* w_out, double* stats_out, void* ws, size_t ws_bytes, void* stream);
+int dlsa_tweedie_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
+                         const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double power,
+                         double dispersion_fixed, double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef,
+                         int* n_iter_host, int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
+                         double* deviance_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a9: local sum of partition blocks before the one-round all-reduce (dlsa.py:30-34) -
  * out = [ sum_k Sig_inv (p*p) | sum_k Sig_invMcoef (p) | sum_k coef (p) ] contiguous,
  * the message a rank contributes to the RCCL all-reduce.  Blocks whose status is not OK may
@@ -623,6 +658,29 @@ int dlsa_onehot_gamma_fit_f64(const dlsa_onehot_plan* plan, const double* num, i
                               int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host,
                               double* loglik_host, double* dispersion_host, double* pearson_host, double* deviance_host, void* ws,
                               size_t ws_bytes, void* stream);
+
+/* ---- Tweedie map step on the raw representation of a one-hot design (the structured sibling of dlsa_tweedie_*_f64) ----------
+ * Rows, plan, column order and unknown codes as dlsa_onehot_poisson_*_f64; the model, `power`, the outputs and their meaning
+ * (loglik is the quasi-log-likelihood) as dlsa_tweedie_*_f64 (intercept = 0) on the matrix dlsa_design_f64 would build, which is
+ * never built.  The argument lists are the one-hot Gamma entries' with `power` in front of the dispersion.
+ * dlsa_onehot_tweedie_pass_f64: one read of the raw rows (8q + 4f + 32 bytes per row with an offset), the sums over (y, mu) when
+ * stats_out is wanted, and the structured Gram when H is wanted, which sums the unbounded weight in ordered floating point; g,
+ * loglik, H, P and Dev are bit-reproducible.
+ * dlsa_onehot_tweedie_fit_f64: partitions as dlsa_onehot_poisson_fit_f64, the fit of dlsa_tweedie_fit_f64 -- the intercept that
+ * starts at the intercept-only MLE is the plan's constant column, if it has one --, the same outputs, statuses and refusals.
+ * Workspace: dlsa_onehot_tweedie_workspace_bytes(plan, max rows, row_step) (0 for a null plan, max_rows < 0 or row_step < 1); the
+ * pass takes the same query with row_step = 1. */
+size_t dlsa_onehot_tweedie_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows, int64_t row_step);
+int dlsa_onehot_tweedie_pass_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                 const double* y, const double* offset, const double* beta, double power, double dispersion, int64_t n,
+                                 double* H, int64_t ldh, double* g, double* loglik, double* w_out, double* stats_out, void* ws,
+                                 size_t ws_bytes, void* stream);
+int dlsa_onehot_tweedie_fit_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                const double* y, const double* offset, const int64_t* part_first_host,
+                                const int64_t* part_rows_host, int64_t row_step, int K, double power, double dispersion_fixed,
+                                double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef, int* n_iter_host,
+                                int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
+                                double* deviance_host, void* ws, size_t ws_bytes, void* stream);
 
 /* test hook: host-only validation of the Gram tile plan for p (0 = every tile on/above the diagonal
  * is stored exactly once; outputs: workgroup items, tile slots computed, tiles stored). */
