@@ -108,6 +108,12 @@ SIGNATURES = {
                                    c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                    ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
                                    c_vp, c_sz, c_vp]),
+    "dlsa_multinomial_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_int, c_i64]),
+    "dlsa_multinomial_pass_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                          c_vp, c_sz, c_vp]),
+    "dlsa_multinomial_fit_f64": (c_int, [c_vp, c_i64, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_i64, c_int, c_int, c_int,
+                                         c_int, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                         ctypes.POINTER(c_dbl), c_vp, c_sz, c_vp]),
     "dlsa_tweedie_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_i64]),
     "dlsa_tweedie_pass_f64": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_sz, c_vp]),

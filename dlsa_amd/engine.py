@@ -1016,6 +1016,68 @@ def tweedie_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_int
     return _gamma_result(out, rc, c_rows, p + icpt)
 
 
+MULTINOMIAL_MAX_CLASSES = 8
+
+
+def multinomial_classes(who, classes, pe):
+    """The class count of a multinomial entry: an int in 2 .. 8 with (classes - 1) * pe <= 2048 coefficients (ValueError otherwise)."""
+    if isinstance(classes, bool) or int(classes) != classes:
+        raise ValueError("%s: classes must be an integer, got %r" % (who, classes))
+    classes = int(classes)
+    if not 2 <= classes <= MULTINOMIAL_MAX_CLASSES:
+        raise ValueError("%s: classes must lie in 2 .. %d, got %d" % (who, MULTINOMIAL_MAX_CLASSES, classes))
+    if (classes - 1) * pe > 2048:
+        raise ValueError("%s: (classes - 1) * (p + intercept) = %d coefficients exceed the solver's 2048" % (who, (classes - 1) * pe))
+    return classes
+
+
+def multinomial_pass(X, y, theta, classes, fit_intercept=False, want_H=True, want_prob=False):
+    """One multinomial logistic (softmax) partition at a fixed theta (dlsa_multinomial_pass_f64): y [n] holds the class codes
+    0 .. classes - 1 as fp64, class 0 is the reference (eta_0 = 0), J = classes - 1.  theta [J * pe] is class-major, [beta_1 | ... |
+    beta_J], intercept first in each with fit_intercept (pe = p + 1).  Returns (H [J pe, J pe] with the blocks H_jk = [1 | X]'
+    diag(p_j (delta_jk - p_k)) [1 | X] or None, g [J pe] with g_j = [1 | X]'(1[y = j] - p_j), loglik [1] = sum log p_y -- NaN when a
+    response is no class code --, P [J, n] the probabilities of the non-reference classes or None)."""
+    lib = _lib.load()
+    _require_gpu(X, y, theta)
+    _f64(X, "X"); _f64(y, "y"); _f64(theta, "theta")
+    n, p = X.shape
+    icpt = 1 if fit_intercept else 0
+    classes = multinomial_classes("multinomial_pass", classes, p + icpt)
+    d = (classes - 1) * (p + icpt)
+    if n < 1 or y.numel() != n or theta.numel() != d:
+        raise ValueError("multinomial_pass: need n >= 1 rows, y with n = %d and theta with %d elements" % (n, d))
+    H, g, ll, _ = _pass_out(d, n, X.device, want_H, False)
+    ld = (n + 31) // 32 * 32                      # 256-byte aligned class rows
+    P = torch.empty((classes - 1, ld), dtype=torch.float64, device=X.device) if want_prob else None
+    ws = _workspace(lib.dlsa_multinomial_workspace_bytes(n, p, icpt, classes, 1), X.device)
+    check(lib.dlsa_multinomial_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(theta), classes, n, p, icpt, _ptr(H), d, _ptr(g), _ptr(ll),
+                                        _ptr(P), ld, _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, (P[:, :n] if want_prob else None)
+
+
+def multinomial_fit_ex(X, y, part_first, part_rows, row_step=1, classes=None, fit_intercept=False, tol=1e-13, max_iter=100):
+    """Per-partition multinomial logistic fit (dlsa_multinomial_fit_f64): partitions and intercept as poisson_fit_ex, y and the
+    class-major layout as multinomial_pass; `classes` (2 .. 8) is required -- a partition cannot discover the classes it lacks, and one
+    that lacks a class is refused with the partition and the class named, as is a response that is no class code.  Same result dict
+    as irls_fit_ex with J * pe columns; `loglik` is the log-likelihood at coef.  classes = 2 is the logistic fit."""
+    lib = _lib.load()
+    _require_gpu(X, y)
+    _f64(X, "X"); _f64(y, "y")
+    n, p = X.shape
+    if y.numel() != n:
+        raise ValueError("multinomial_fit_ex: y must have n = %d elements" % n)
+    if classes is None:
+        raise ValueError("multinomial_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
+    icpt = 1 if fit_intercept else 0
+    classes = multinomial_classes("multinomial_fit_ex", classes, p + icpt)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("multinomial_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, (classes - 1) * (p + icpt), X.device)
+    ws = _workspace(lib.dlsa_multinomial_workspace_bytes(max_rows, p, icpt, classes, step), X.device)
+    rc = lib.dlsa_multinomial_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), c_first, c_rows, step, K, p, icpt, classes, tol, max_iter, *out.args,
+                                      _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
+
+
 def negbin_special(theta, y):
     """The dispersion kernel's special functions (dlsa_negbin_special_f64, a test entry): theta [m] > 0, y [m] >= 0 on the GPU;
     returns [m, 4] = psi(theta), psi'(theta), psi(y + theta) - psi(theta), lgamma(y + theta) - lgamma(theta) - y log(theta)."""

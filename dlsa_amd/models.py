@@ -1171,3 +1171,100 @@ def tweedie_model_eval(sample_df, Y_name, par, power, dispersion, fit_intercept=
         return engine.onehot_tweedie_pass(plan, num, codes, y, b, power, dispersion, **kw)
     chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
     return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)
+
+
+# ---------------------------------------------------------------------------------------------
+# Multinomial logistic (softmax) map step for a response with C unordered classes (delay cause, product chosen, diagnosis group).
+# Class 0 is the reference class; the parameter is class-major, theta = [beta_1 | ... | beta_J] with J = C - 1, so a partition's block
+# is [coef | Sig_inv coef | Sig_inv] over J * pe coefficients named "<name>:<j>", and dlsa_mapred applies unchanged.  dlsa() knows
+# one unpenalised intercept at position 0: multinomial blocks go through dlsa(..., fit_intercept=False).
+# ---------------------------------------------------------------------------------------------
+def simulate_multinomial(sample_size, p, partition_num, classes, seed=20260101, coef_value=1.0):
+    """Seeded rows with a class response: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), beta*_j = +-coef_value
+    (the sign alternating with the class j = 1 .. classes - 1) on the first int(0.4p) coefficients, y ~ softmax(0, x beta*_1, ...)
+    drawn with numpy as class codes 0 .. classes - 1.  partition_id = i % partition_num.  Returns the frame partition_id, y,
+    x0 .. x{p-1}."""
+    n, p, C = int(sample_size), int(p), int(classes)
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    X = X.cpu().numpy()
+    B = np.zeros((p, C))
+    for j in range(1, C):
+        B[:int(0.4 * p), j] = float(coef_value) * (1.0 if j % 2 else -1.0)
+    eta = X @ B
+    pr = np.exp(eta - eta.max(1, keepdims=True))
+    cdf = np.cumsum(pr / pr.sum(1, keepdims=True), 1)
+    rng = np.random.default_rng(seed)
+    y = np.minimum((rng.random(n)[:, None] > cdf).sum(1), C - 1).astype(np.float64)
+    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    return pd.DataFrame(np.concatenate([pid[:, None], y[:, None], X], 1), columns=["partition_id", "y"] + ["x" + str(i) for i in range(p)])
+
+
+def multinomial_column_names(names, classes):
+    """The J * pe column names of a multinomial block: "<name>:<j>" for j = 1 .. classes - 1, class-major (`names` = one class
+    block's names, `intercept` first when the fit carries one)."""
+    return ["%s:%d" % (nm, j) for j in range(1, int(classes)) for nm in names]
+
+
+def fit_multinomial_partitions(X, y, classes, partition_num=None, part_offsets=None, fit_intercept=False, names=None, tol=1e-13,
+                               max_iter=100):
+    """Multinomial logistic map step for the partitions of one device-resident shard: X [n, p] fp64 row-major, y [n] class codes
+    0 .. classes - 1 on the GPU (class 0 is the reference).  Partitions and the implicit intercept as fit_poisson_partitions.  Every
+    partition with rows must hold every class.  Returns MappedBlocks over the (classes - 1) * pe coefficients "<name>:<j>",
+    "intercept:<j>" first in each class block, with `loglik` = the log-likelihood per partition."""
+    if not X.is_cuda:
+        raise RuntimeError("fit_multinomial_partitions runs on the GPU only (no CPU fallback)")
+    if X.dtype != torch.float64:
+        raise TypeError("fit_multinomial_partitions: X must be float64, got %s" % X.dtype)
+    n, p = X.shape
+    y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
+    if y.numel() != n:
+        raise ValueError("fit_multinomial_partitions: y must have n = %d elements" % n)
+    classes = engine.multinomial_classes("fit_multinomial_partitions", classes, p + (1 if fit_intercept else 0))
+    names = multinomial_column_names(_column_names(names, p, fit_intercept), classes)
+    first, rows, step = _partitions(n, partition_num, part_offsets)
+    r = engine.multinomial_fit_ex(engine.row_major(X), y, first, rows, row_step=step, classes=classes, fit_intercept=fit_intercept,
+                                  tol=tol, max_iter=max_iter)
+    return _blocks(r, names, n)
+
+
+def _multinomial_frame(who, sample_df, Y_name, classes, fit_intercept, dummy_info, dummy_factors_baseline, data_info, for_eval=False):
+    """(X device design without the ones column or None, the J * pe names, the class codes on the device, C) of one chunk whose
+    response column holds the labels `classes` (reference first)."""
+    labels = list(classes)
+    if len(set(labels)) != len(labels):
+        raise ValueError("%s: classes must be distinct labels, reference first" % who)
+    codes = sample_df[Y_name].map({lab: float(i) for i, lab in enumerate(labels)})
+    if codes.isna().any():
+        raise ValueError("%s: column %r holds values that are not among classes=%r" % (who, Y_name, labels))
+    frame = sample_df.assign(**{Y_name: codes.astype(np.float64)})
+    Xd, names = _device_design(frame, Y_name, False, dummy_info, dummy_factors_baseline, data_info, for_eval=for_eval)
+    return Xd, _column_names(names, len(names), fit_intercept), _to_device(frame, Y_name), len(labels)
+
+
+def multinomial_model(sample_df, Y_name, classes, fit_intercept=False, dummy_info=[], dummy_factors_baseline=[], data_info=[],
+                      tol=1e-13, max_iter=100):
+    """Frame-level sibling of logistic_model for a response with more than two unordered classes: one partition (a pandas frame)
+    whose column Y_name holds the labels listed in `classes`, the reference class first.  `classes` is required: a partition cannot
+    discover the classes it lacks.  Returns the stacked (J pe) x (3 + J pe) frame `par_id, coef, Sig_invMcoef, <name>:<j> ...`; a
+    chunk that lacks an expected dummy level returns the all-zero block with a warning."""
+    Xd, names, yd, C = _multinomial_frame("multinomial_model", sample_df, Y_name, classes, fit_intercept, dummy_info,
+                                          dummy_factors_baseline, data_info)
+    if Xd is None:
+        return _zero_block(multinomial_column_names(names, C))
+    mb = fit_multinomial_partitions(Xd, yd, C, fit_intercept=fit_intercept, names=names[1:] if fit_intercept else names, tol=tol,
+                                    max_iter=max_iter)
+    return _first_block_frame(mb, "multinomial_model")
+
+
+def multinomial_model_eval(sample_df, Y_name, par, classes, fit_intercept=False, dummy_info=[], dummy_factors_baseline=[], data_info=[]):
+    """Log-likelihood (sum log p_y) of every estimator column of `par` (J * pe rows, class-major) on one partition, shaped like
+    logistic_model_eval's output: one row, a column per estimator (one pass without the information per column)."""
+    Xd, _, yd, C = _multinomial_frame("multinomial_model_eval", sample_df, Y_name, classes, fit_intercept, dummy_info,
+                                      dummy_factors_baseline, data_info, for_eval=True)
+    X = engine.row_major(Xd)
+    pard = np.asarray(par, dtype=np.float64)
+    out = {}
+    for i in range(pard.shape[1]):
+        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+        out[par.columns[i]] = [float(engine.multinomial_pass(X, yd, b, C, fit_intercept=fit_intercept, want_H=False)[2].item())]
+    return pd.DataFrame(out)

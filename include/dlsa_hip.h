@@ -432,6 +432,37 @@ int dlsa_tweedie_fit_f64(const double* X, int64_t ldx, const double* y, const do
                          int* n_iter_host, int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
                          double* deviance_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Multinomial logistic (softmax) regression map step (a response with C unordered classes: delay cause, product chosen,
+ * diagnosis group) ---------
+ * y holds the class codes 0 .. C - 1 as doubles; C = `classes` is given by the caller, 2 <= C <= 8.  Class 0 is the reference class
+ * (eta_0 = 0; the convention of nnet::multinom and statsmodels MNLogit), J = C - 1, pe = p + intercept, and J pe <= 2048 (the
+ * solver's limit); anything else is DLSA_ERR_INVALID.  The parameter is class-major: theta = [beta_1 | ... | beta_J], every beta_j
+ * with pe entries, intercept first.  eta_j = [1 | x]' beta_j, p_j = e^eta_j / sum_k e^eta_k.  g, coef and Sig_invMcoef have J pe
+ * entries, H and Sig_inv are (J pe) x (J pe) with both triangles.  No offsets, no dispersion.  C = 2 is the logistic model.
+ * dlsa_multinomial_pass_f64 at a fixed theta, one read of the rows (+ J (J + 1) / 2 Grams when H is wanted): loglik = sum_i
+ * log p_{y_i} (1 value, nullable; NaN when a response is not finite, not integral, < 0 or >= C), g_j = [1 | X]'(1[y = j] - p_j)
+ * (nullable), H_jk = [1 | X]' diag(p_j (delta_jk - p_k)) [1 | X] (nullable, ldh >= J pe; the observed = expected information),
+ * prob_out (nullable) = the probabilities of the non-reference classes, class-major: prob_out[(j - 1) ldprob + i] = p_j of row i,
+ * ldprob >= n a multiple of 32 and prob_out 256-byte aligned (so is every class row).  A class without rows is legal in a pass; the
+ * data of the pass are not checked otherwise.  g and loglik are bit-reproducible.
+ * dlsa_multinomial_fit_f64: partitions as dlsa_poisson_fit_f64 (strided i % K partitions read in place, their responses gathered
+ * into the workspace).  Before any partition is fitted, every partition with rows is checked: a response that is no class code, or
+ * a class 0 .. C - 1 without a row (that fit runs off to eta = -inf, and the blocks of different partitions must mean the same
+ * parameter), returns DLSA_ERR_INVALID naming the partition (and the class).  Newton from theta = 0 with class j's intercept at
+ * log(n_j / n_0) (the MLE of the intercept-only model), the safeguards and the stopping rule of dlsa_poisson_fit_f64; outputs as
+ * dlsa_poisson_fit_f64 on J pe coefficients, Sig_inv = H at coef, loglik_host the log-likelihood at coef.  A partition without rows
+ * is DLSA_PART_EMPTY with the all-zero block; DLSA_PART_NOT_SPD, DLSA_PART_NOT_CONVERGED and DLSA_PART_NAN as
+ * dlsa_poisson_fit_f64.  Workspace: dlsa_multinomial_workspace_bytes(max rows, p, intercept, classes, row_step) (0 for a shape the
+ * entries refuse); the pass takes the same query with row_step = 1. */
+size_t dlsa_multinomial_workspace_bytes(int64_t max_rows, int p, int intercept, int classes, int64_t row_step);
+int dlsa_multinomial_pass_f64(const double* X, int64_t ldx, const double* y, const double* theta, int classes, int64_t n,
+                              int p, int intercept, double* H, int64_t ldh, double* g, double* loglik,
+                              double* prob_out, int64_t ldprob, void* ws, size_t ws_bytes, void* stream);
+int dlsa_multinomial_fit_f64(const double* X, int64_t ldx, const double* y, const int64_t* part_first_host,
+                             const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, int classes,
+                             double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef,
+                             int* n_iter_host, int* status_host, double* loglik_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a9: local sum of partition blocks before the one-round all-reduce (dlsa.py:30-34) -
  * out = [ sum_k Sig_inv (p*p) | sum_k Sig_invMcoef (p) | sum_k coef (p) ] contiguous,
  * the message a rank contributes to the RCCL all-reduce.  Blocks whose status is not OK may
