@@ -29,6 +29,7 @@
 // intercept-only model, and the rows whose response is no class code).
 #include "common.h"
 #include "poisson_internal.h"
+#include "multinomial_internal.h"   // the limits, mn_softmax_row, mn_fit_core, the launchers the structured sibling shares
 #include <math.h>
 #include <algorithm>
 #include <vector>
@@ -36,13 +37,7 @@
 namespace dlsa {
 
 #include "rowdot.h"       // merged_reduce, row_of_lane, rep_mask, rank1_update
-#include "poisson_exp.h"  // exp_full
 #include "count_pass.h"   // count_ld2, count_nc, count_rb, count_blocks, COUNT_*
-
-constexpr int MN_MAX_CLASSES = 8;
-constexpr int MN_NQ = MN_MAX_CLASSES + 1;       // the check's sums: the rows of class 0 .. 7, then the bad rows
-constexpr int MN_BAD = MN_MAX_CLASSES;
-constexpr int MN_CHECK_BLOCKS = 512;
 
 struct MnArgs {
     const double* X;
@@ -126,28 +121,12 @@ __global__ __launch_bounds__(COUNT_THREADS) void mn_pass_kernel(MnArgs a) {
             }
             eta[j] = merged_reduce<RB>(dot, lane) + b0[j];
         }
-        // the softmax of the lane's row: T = the sum of all terms but the first that attains M (which is exactly 1)
-        double M = 0.0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) M = eta[j] > M ? eta[j] : M;
-        bool found = M == 0.0;                                        // the reference class attains it
-        double T = found ? 0.0 : exp_full(-M);
-        double e[J];
+        double pr[J];                                                 // the softmax of the lane's row (multinomial_internal.h)
+        const double term = mn_softmax_row<J>(eta, yraw, pr);
+        if (valid && rep) ll += term;
 #pragma unroll
         for (int j = 0; j < J; ++j) {
-            e[j] = exp_full(eta[j] - M);
-            const bool hit = !found && eta[j] == M;
-            T += hit ? 0.0 : e[j];
-            found = found || hit;
-        }
-        const double inv = 1.0 / (1.0 + T);
-        double eta_y = 0.0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) eta_y = yraw == (double)(j + 1) ? eta[j] : eta_y;
-        if (valid && rep) ll += eta_y - M - log1p(T);
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const double pj = e[j] * inv;
+            const double pj = pr[j];
             const double resid = valid ? (yraw == (double)(j + 1) ? 1.0 : 0.0) - pj : 0.0;
             if (valid && rep) {
                 if (a.prob) a.prob[j * a.ldprob + r] = pj;
@@ -253,11 +232,10 @@ __global__ void mn_ll_fix_kernel(double* __restrict__ ll, const double* __restri
     if (threadIdx.x == 0 && cst[MN_BAD] > 0.0) ll[0] = NAN;
 }
 
-struct MnStart { double b0[MN_MAX_CLASSES - 1]; };
-// Newton start: theta = 0, class j's intercept (entry j * pe; icpt only) at b0[j]
-__global__ void mn_start_kernel(double* __restrict__ theta, int J, int pe, int icpt, MnStart st) {
+// Newton start: theta = 0, the constant column of class block j (entry j * pe + icpt_col; -1: none) at b0[j]
+__global__ void mn_start_kernel(double* __restrict__ theta, int J, int pe, int icpt_col, MnStart st) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < J * pe) theta[i] = (icpt && i % pe == 0) ? st.b0[i / pe] : 0.0;
+    if (i < J * pe) theta[i] = (icpt_col >= 0 && i % pe == icpt_col) ? st.b0[i / pe] : 0.0;
 }
 
 // w = p_j (delta_jk - p_k): the weights of the block (j, k) of the information
@@ -300,8 +278,6 @@ struct MnLayout {
     int64_t ldprob;
 };
 
-static int64_t mn_ldprob(int64_t n) { return (int64_t)align_up((size_t)std::max<int64_t>(n, 1), 32); }      // 256-byte class rows
-
 // pass scratch; row_step > 1: room for the gathered responses of a strided partition
 static MnLayout mn_layout(int64_t max_rows, int p, int J, int64_t row_step) {
     MnLayout l{};
@@ -325,10 +301,35 @@ static MnLayout mn_layout(int64_t max_rows, int p, int J, int64_t row_step) {
 }
 
 // cst[0 .. 8] = the class counts and the bad rows of n responses
-static int mn_check(const double* y, int64_t n, int classes, double* cpart, double* cst, hipStream_t s) {
+int mn_check(const double* y, int64_t n, int classes, double* cpart, double* cst, hipStream_t s) {
     const int blocks = (int)std::min<int64_t>(MN_CHECK_BLOCKS, std::max<int64_t>(1, (n + 255) / 256));
     hipLaunchKernelGGL(mn_check_kernel, dim3(blocks), dim3(256), 0, s, y, n, classes, cpart);
     hipLaunchKernelGGL(mn_check_finish_kernel, dim3(1), dim3(64 * MN_NQ), 0, s, (const double*)cpart, blocks, cst);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int mn_ll_fix(double* ll, const double* cst, hipStream_t s) {
+    hipLaunchKernelGGL(mn_ll_fix_kernel, dim3(1), dim3(64), 0, s, ll, cst);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int mn_start(double* theta, int J, int pe, int icpt_col, const MnStart& st, hipStream_t s) {
+    hipLaunchKernelGGL(mn_start_kernel, dim3((J * pe + 255) / 256), dim3(256), 0, s, theta, J, pe, icpt_col, st);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int mn_weight(const double* pj, const double* pk, int same, int64_t n, double* w, hipStream_t s) {
+    hipLaunchKernelGGL(mn_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pj, pk, same, n, w);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int mn_mirror(double* H, int64_t ldh, int J, int pe, hipStream_t s) {
+    if (J <= 1) return DLSA_OK;                  // one block: nothing below the block diagonal
+    hipLaunchKernelGGL(mn_mirror_kernel, dim3((J * pe + 255) / 256, J * pe), dim3(256), 0, s, H, ldh, J, pe);
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
@@ -368,100 +369,27 @@ static int mn_pass_impl(const double* X, int64_t ldx, const double* y, const dou
     double* w = (double*)(ws + l.off_w);
     for (int j = 0; j < J; ++j) {
         for (int k = j; k < J; ++k) {
-            hipLaunchKernelGGL(mn_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double*)(prob + j * ldprob),
-                               (const double*)(prob + k * ldprob), j == k ? 1 : 0, n, w);
-            DLSA_HIP_CHECK(hipGetLastError());
+            rc = mn_weight(prob + j * ldprob, prob + k * ldprob, j == k ? 1 : 0, n, w, s);
+            if (rc) return rc;
             double* Hjk = H + (size_t)j * pe * ldh + (size_t)k * pe;
             rc = icpt ? gram_icpt_impl(X, ldx, w, n, p, Hjk, ldh, ws + l.off_gram, l.gram_bytes, s)
                       : gram_impl_f64(X, ldx, w, n, p, Hjk, ldh, 0, ws + l.off_gram, l.gram_bytes, s);
             if (rc) return rc;
         }
     }
-    if (J > 1) {
-        hipLaunchKernelGGL(mn_mirror_kernel, dim3((J * pe + 255) / 256, J * pe), dim3(256), 0, s, H, ldh, J, pe);
-        DLSA_HIP_CHECK(hipGetLastError());
-    }
-    return DLSA_OK;
+    return mn_mirror(H, ldh, J, pe, s);
 }
 
-// device scratch of the fit loop
-struct MnFitBufs {
-    double* cpart;     // MN_NQ * MN_CHECK_BLOCKS
-    double* cst;       // MN_NQ
-    double* ybuf;      // max_rows when row_step > 1: the gathered responses
-    NewtonState st;
-};
-
-// The per-partition driver of the multinomial fit, beside pois_fit_core: the data check of EVERY partition first (a partition
-// that lacks a class has no finite MLE, and the blocks of different partitions must mean the same parameter), then per partition
-// the start at theta = 0 with class j's intercept at log(n_j / n_0), newton_fit_loop with the policy NEWTON_POISSON on J pe
-// coefficients and newton_fit_finish.  eval(k, yk, nk, theta, H, g, ll) is the only part that knows the representation of the design.
-template <class Eval>
-static int mn_fit_core(const char* who, const double* y, const int64_t* part_first_host, const int64_t* part_rows_host, int64_t row_step,
-                       int K, int pe, int icpt, int classes, double tol, int max_iter, double* coef, double* Sig_inv,
-                       double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, const MnFitBufs& b, Eval&& eval,
-                       hipStream_t s) {
-    const int J = classes - 1, d = J * pe;
-    std::vector<double> counts((size_t)K * MN_NQ, 0.0);
-    const double* yk = nullptr;
-    const double* none = nullptr;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        if (nk <= 0) continue;
-        int rc = pois_gather_rows(y, nullptr, part_first_host[k], row_step, nk, b.ybuf, nullptr, yk, none, s);
-        if (rc) return rc;
-        rc = mn_check(yk, nk, classes, b.cpart, b.cst, s);
-        if (rc) return rc;
-        double* cst = counts.data() + (size_t)k * MN_NQ;
-        DLSA_HIP_CHECK(hipMemcpyAsync(cst, b.cst, MN_NQ * sizeof(double), hipMemcpyDeviceToHost, s));
-        DLSA_HIP_CHECK(hipStreamSynchronize(s));
-        if (cst[MN_BAD] > 0.0) {
-            set_error("%s: partition %d has %.0f rows whose response is not a class code 0 .. %d", who, k, cst[MN_BAD], classes - 1);
-            return DLSA_ERR_INVALID;
-        }
-        for (int c = 0; c < classes; ++c) {
-            if (!(cst[c] > 0.0)) {
-                set_error("%s: partition %d has no row of class %d: its maximum-likelihood fit runs off to eta = -inf", who, k, c);
-                return DLSA_ERR_INVALID;
-            }
-        }
-    }
-    int overall = DLSA_OK;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        double* Hk = Sig_inv + (size_t)k * d * d;
-        double* ck = coef + (size_t)k * d;
-        double* sk = Sig_invMcoef + (size_t)k * d;
-        int st_k = DLSA_PART_EMPTY, iters = 0;
-        double ll = 0.0;
-        if (nk > 0) {
-            int rc = pois_gather_rows(y, nullptr, part_first_host[k], row_step, nk, b.ybuf, nullptr, yk, none, s);
-            if (rc) return rc;
-            const double* cst = counts.data() + (size_t)k * MN_NQ;
-            MnStart start{};
-            for (int j = 0; j < J; ++j) start.b0[j] = log(cst[j + 1] / cst[0]);
-            hipLaunchKernelGGL(mn_start_kernel, dim3((d + 255) / 256), dim3(256), 0, s, b.st.beta, J, pe, icpt, start);
-            DLSA_HIP_CHECK(hipGetLastError());
-            const NewtonDevice dev{b.st, Hk, d, s};
-            NewtonOutcome o;
-            rc = newton_fit_loop(NEWTON_POISSON, tol, max_iter + 1, [&](bool&) { return eval(k, yk, nk, b.st.beta, Hk, b.st.g, b.st.stats + 3); },
-                                 dev, newton_no_hook, o);
-            if (rc) return rc;
-            st_k = o.status; iters = o.n_iter; ll = o.ll;
-        }
-        const int rcf = newton_fit_finish(st_k, iters, ll, b.st.beta, d, Hk, ck, sk, k, n_iter_host, status_host, loglik_host, overall, s);
-        if (rcf) return rcf;
-    }
-    DLSA_HIP_CHECK(hipStreamSynchronize(s));
-    return overall;
+int mn_coef_ok(const char* who, int pe, int classes) {
+    DLSA_REQUIRE(classes >= 2 && classes <= MN_MAX_CLASSES, "%s: classes must lie in 2 .. %d, got %d", who, MN_MAX_CLASSES, classes);
+    const int64_t d = (int64_t)(classes - 1) * pe;
+    DLSA_REQUIRE(d <= 2048, "%s: (classes - 1) * (p + intercept) = %lld coefficients exceed the solver's 2048", who, (long long)d);
+    return DLSA_OK;
 }
 
 static int mn_shape_ok(const char* who, int p, int intercept, int classes) {
-    DLSA_REQUIRE(classes >= 2 && classes <= MN_MAX_CLASSES, "%s: classes must lie in 2 .. %d, got %d", who, MN_MAX_CLASSES, classes);
-    DLSA_REQUIRE(p > 0, "%s: bad shape p=%d", who, p);
-    const int64_t d = (int64_t)(classes - 1) * (p + (intercept ? 1 : 0));
-    DLSA_REQUIRE(d <= 2048, "%s: (classes - 1) * (p + intercept) = %lld coefficients exceed the solver's 2048", who, (long long)d);
-    return DLSA_OK;
+    DLSA_REQUIRE(p > 0 || classes < 2 || classes > MN_MAX_CLASSES, "%s: bad shape p=%d", who, p);      // (the class count is judged first)
+    return mn_coef_ok(who, p + (intercept ? 1 : 0), classes);
 }
 
 }  // namespace dlsa
@@ -498,9 +426,7 @@ int dlsa_multinomial_pass_f64(const double* X, int64_t ldx, const double* y, con
     if (rc || !loglik) return rc;
     rc = mn_check(y, n, classes, (double*)(wsc + l.off_cpart), (double*)(wsc + l.off_cst), s);
     if (rc) return rc;
-    hipLaunchKernelGGL(mn_ll_fix_kernel, dim3(1), dim3(64), 0, s, loglik, (const double*)(wsc + l.off_cst));
-    DLSA_HIP_CHECK(hipGetLastError());
-    return DLSA_OK;
+    return mn_ll_fix(loglik, (const double*)(wsc + l.off_cst), s);
 }
 
 int dlsa_multinomial_fit_f64(const double* X, int64_t ldx, const double* y, const int64_t* part_first_host,
@@ -535,7 +461,7 @@ int dlsa_multinomial_fit_f64(const double* X, int64_t ldx, const double* y, cons
         return mn_pass_impl(X + part_first_host[k] * ldx, pitch, yk, theta, classes, nk, p, intercept, Hk, d, g, ll,
                             (double*)(wsc + l.off_prob), l.ldprob, wsc, l, s);
     };
-    return mn_fit_core("multinomial_fit", y, part_first_host, part_rows_host, row_step, K, pe, icpt, classes, tol, max_iter, coef, Sig_inv,
+    return mn_fit_core("multinomial_fit", y, part_first_host, part_rows_host, row_step, K, pe, icpt ? 0 : -1, classes, tol, max_iter, coef, Sig_inv,
                        Sig_invMcoef, n_iter_host, status_host, loglik_host, b, eval, s);
 }
 

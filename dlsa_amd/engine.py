@@ -1498,6 +1498,46 @@ def onehot_tweedie_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1
     return _gamma_result(out, rc, c_rows, plan.p)
 
 
+def onehot_multinomial_pass(plan, num, codes, y, theta, classes, want_H=True, want_prob=False):
+    """multinomial_pass on the raw representation of a one-hot design (dlsa_onehot_multinomial_pass_f64): rows as
+    onehot_poisson_pass, y and `classes` as multinomial_pass.  theta [J * plan.p] is class-major, theta[j * p + c] the coefficient of
+    class j + 1 on the plan's column c (an intercept is the plan's constant column, one column of every class block).  Returns
+    (H [J p, J p] or None, g [J p], loglik [1] -- NaN when a response is no class code --, P [J, n] or None) of the matrix
+    dlsa_design_f64 would build -- which is never built."""
+    lib = _lib.load()
+    _require_gpu(theta)
+    _f64(theta, "theta")
+    n = _oh_poisson_rows(plan, num, codes, y, None, "onehot_multinomial_pass")
+    classes = multinomial_classes("onehot_multinomial_pass", classes, plan.p)
+    d = (classes - 1) * plan.p
+    if n < 1 or theta.numel() != d:
+        raise ValueError("onehot_multinomial_pass: need n >= 1 rows and theta with %d elements" % d)
+    H, g, ll, _ = _pass_out(d, n, y.device, want_H, False)
+    ld = (n + 31) // 32 * 32                      # 256-byte aligned class rows
+    P = torch.empty((classes - 1, ld), dtype=torch.float64, device=y.device) if want_prob else None
+    ws = _workspace(lib.dlsa_onehot_multinomial_workspace_bytes(plan._h, n, classes, 1), y.device)
+    check(lib.dlsa_onehot_multinomial_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(theta), classes, n, _ptr(H), d, _ptr(g),
+                                               _ptr(ll), _ptr(P), ld, _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, (P[:, :n] if want_prob else None)
+
+
+def onehot_multinomial_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, classes=None, tol=1e-13, max_iter=100):
+    """multinomial_fit_ex on the raw representation of a one-hot design (dlsa_onehot_multinomial_fit_f64): partitions as
+    onehot_poisson_fit_ex, `classes` (2 .. 8, required) and the refusals as multinomial_fit_ex.  Same result dict as
+    multinomial_fit_ex with J * plan.p columns, class-major in the plan's column order."""
+    lib = _lib.load()
+    n = _oh_poisson_rows(plan, num, codes, y, None, "onehot_multinomial_fit_ex")
+    if classes is None:
+        raise ValueError("onehot_multinomial_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
+    classes = multinomial_classes("onehot_multinomial_fit_ex", classes, plan.p)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_multinomial_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, (classes - 1) * plan.p, y.device)
+    ws = _workspace(lib.dlsa_onehot_multinomial_workspace_bytes(plan._h, max_rows, classes, step), y.device)
+    rc = lib.dlsa_onehot_multinomial_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), c_first, c_rows, step, K, classes, tol, max_iter,
+                                             *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
+
+
 class RcclComm:
     """An RCCL communicator opened through the C ABI (dlsa_comm_unique_id / dlsa_comm_init_rank), for hosts that do not
     use torch.distributed: rank 0 creates `RcclComm.unique_id()`, ships the 128 bytes to the other ranks out of band, every

@@ -81,9 +81,10 @@ def _blocks(r, names, n):
                         extra=extra)
 
 
-def _fit_design(onehot_fit, dense_fit, num, codes, y, spec, partition_num, part_offsets, structured, **fit_args):
+def _fit_design(onehot_fit, dense_fit, num, codes, y, spec, partition_num, part_offsets, structured, names=None, **fit_args):
     """The body of the fit_*_design functions: the family's structured engine fit on the raw columns when the design qualifies,
-    else its dense fit on the matrix the design kernel builds once; the same strided partitions either way."""
+    else its dense fit on the matrix the design kernel builds once; the same strided partitions either way.  `names`: the blocks'
+    column names when they are not spec.names (the multinomial family's J class blocks)."""
     n = y.numel()
     first, rows, step = _partitions(n, partition_num, part_offsets)
     plan = spec.onehot_plan() if structured else None
@@ -93,7 +94,7 @@ def _fit_design(onehot_fit, dense_fit, num, codes, y, spec, partition_num, part_
     else:
         X, _ = spec.build(num, codes)
         r = dense_fit(X, y, first, rows, row_step=step, **fit_args)
-    return _blocks(r, spec.names, n)
+    return _blocks(r, spec.names if names is None else names, n)
 
 
 def _to_device(sample_df, name):
@@ -1227,26 +1228,64 @@ def fit_multinomial_partitions(X, y, classes, partition_num=None, part_offsets=N
     return _blocks(r, names, n)
 
 
-def _multinomial_frame(who, sample_df, Y_name, classes, fit_intercept, dummy_info, dummy_factors_baseline, data_info, for_eval=False):
-    """(X device design without the ones column or None, the J * pe names, the class codes on the device, C) of one chunk whose
-    response column holds the labels `classes` (reference first)."""
+def fit_multinomial_design(num, codes, y, spec, classes, partition_num=None, part_offsets=None, structured=True, tol=1e-13,
+                           max_iter=100):
+    """Multinomial logistic map step for a design given by its RAW columns, the sibling of fit_poisson_design: num [n, q] fp64, codes
+    [n, f] int32 level codes (DesignSpec.encode) and the class codes y [n] (0 .. classes - 1, class 0 the reference), all on the
+    GPU.  With structured=True and a qualifying design (spec.onehot_plan()) the fit runs on the raw representation -- the dense
+    [n, p] matrix is never built; otherwise the matrix is built once by the design kernel and the dense multinomial fit runs on it
+    without an implicit intercept.  An intercept is the spec's own constant column, one column of every class block.  Partitions as
+    fit_poisson_partitions; every partition with rows must hold every class.  Same MappedBlocks either way over the
+    (classes - 1) * p coefficients multinomial_column_names(spec.names, classes)."""
+    if not torch.is_tensor(y) or not y.is_cuda:
+        raise RuntimeError("fit_multinomial_design runs on the GPU only (no CPU fallback)")
+    if num is not None and num.dtype != torch.float64:
+        raise TypeError("fit_multinomial_design: num must be float64, got %s" % num.dtype)
+    y = y.to(torch.float64).contiguous()
+    classes = engine.multinomial_classes("fit_multinomial_design", classes, len(spec.names))
+    return _fit_design(engine.onehot_multinomial_fit_ex, engine.multinomial_fit_ex, num, codes, y, spec, partition_num, part_offsets,
+                       structured, names=multinomial_column_names(spec.names, classes), classes=classes, tol=tol, max_iter=max_iter)
+
+
+def _multinomial_codes_frame(who, sample_df, Y_name, classes):
+    """(the chunk with its response column Y_name turned from the labels `classes` -- reference first -- into class codes, C)."""
     labels = list(classes)
     if len(set(labels)) != len(labels):
         raise ValueError("%s: classes must be distinct labels, reference first" % who)
     codes = sample_df[Y_name].map({lab: float(i) for i, lab in enumerate(labels)})
     if codes.isna().any():
         raise ValueError("%s: column %r holds values that are not among classes=%r" % (who, Y_name, labels))
-    frame = sample_df.assign(**{Y_name: codes.astype(np.float64)})
+    return sample_df.assign(**{Y_name: codes.astype(np.float64)}), len(labels)
+
+
+def _multinomial_frame(who, sample_df, Y_name, classes, fit_intercept, dummy_info, dummy_factors_baseline, data_info, for_eval=False):
+    """(X device design without the ones column or None, the J * pe names, the class codes on the device, C) of one chunk whose
+    response column holds the labels `classes` (reference first)."""
+    frame, C = _multinomial_codes_frame(who, sample_df, Y_name, classes)
     Xd, names = _device_design(frame, Y_name, False, dummy_info, dummy_factors_baseline, data_info, for_eval=for_eval)
-    return Xd, _column_names(names, len(names), fit_intercept), _to_device(frame, Y_name), len(labels)
+    return Xd, _column_names(names, len(names), fit_intercept), _to_device(frame, Y_name), C
 
 
 def multinomial_model(sample_df, Y_name, classes, fit_intercept=False, dummy_info=[], dummy_factors_baseline=[], data_info=[],
-                      tol=1e-13, max_iter=100):
+                      tol=1e-13, max_iter=100, structured=False):
     """Frame-level sibling of logistic_model for a response with more than two unordered classes: one partition (a pandas frame)
     whose column Y_name holds the labels listed in `classes`, the reference class first.  `classes` is required: a partition cannot
     discover the classes it lacks.  Returns the stacked (J pe) x (3 + J pe) frame `par_id, coef, Sig_invMcoef, <name>:<j> ...`; a
-    chunk that lacks an expected dummy level returns the all-zero block with a warning."""
+    chunk that lacks an expected dummy level returns the all-zero block with a warning.
+    structured=True with a dummy_info and a qualifying design fits on the raw numerics + level codes (fit_multinomial_design; the
+    dense one-hot matrix is never built, the missing-level check runs on the codes); the default is the dense path."""
+    if structured and len(dummy_info) > 0:
+        frame, C = _multinomial_codes_frame("multinomial_model", sample_df, Y_name, classes)
+        spec, plan, codes, unknown, yd, _, _ = _count_raw_frame(frame, Y_name, fit_intercept, None, None, dummy_info,
+                                                                dummy_factors_baseline, data_info)
+        if plan is not None:
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                _warn_missing_levels(missing, len(sample_df), spec.names, fit_intercept, skip=True)
+                return _zero_block(multinomial_column_names(spec.names, C))
+            mb = fit_multinomial_design(spec.numeric_to_device(frame), torch.from_numpy(codes).cuda(), yd, spec, C, tol=tol,
+                                        max_iter=max_iter)
+            return _first_block_frame(mb, "multinomial_model")
     Xd, names, yd, C = _multinomial_frame("multinomial_model", sample_df, Y_name, classes, fit_intercept, dummy_info,
                                           dummy_factors_baseline, data_info)
     if Xd is None:
@@ -1256,13 +1295,29 @@ def multinomial_model(sample_df, Y_name, classes, fit_intercept=False, dummy_inf
     return _first_block_frame(mb, "multinomial_model")
 
 
-def multinomial_model_eval(sample_df, Y_name, par, classes, fit_intercept=False, dummy_info=[], dummy_factors_baseline=[], data_info=[]):
+def multinomial_model_eval(sample_df, Y_name, par, classes, fit_intercept=False, dummy_info=[], dummy_factors_baseline=[], data_info=[],
+                           structured=False):
     """Log-likelihood (sum log p_y) of every estimator column of `par` (J * pe rows, class-major) on one partition, shaped like
-    logistic_model_eval's output: one row, a column per estimator (one pass without the information per column)."""
+    logistic_model_eval's output: one row, a column per estimator (one pass without the information per column).  structured=True
+    with a dummy_info and a qualifying design runs the passes on the raw numerics + level codes."""
+    pard = np.asarray(par, dtype=np.float64)
+    if structured and len(dummy_info) > 0:
+        frame, C = _multinomial_codes_frame("multinomial_model_eval", sample_df, Y_name, classes)
+        spec, plan, codes, unknown, yd, _, _ = _count_raw_frame(frame, Y_name, fit_intercept, None, None, dummy_info,
+                                                                dummy_factors_baseline, data_info)
+        if plan is not None:
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                _warn_missing_levels(missing, len(sample_df), spec.names, fit_intercept, skip=False)
+            num, cd = spec.numeric_to_device(frame), torch.from_numpy(codes).cuda()
+            out = {}
+            for i in range(pard.shape[1]):
+                b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+                out[par.columns[i]] = [float(engine.onehot_multinomial_pass(plan, num, cd, yd, b, C, want_H=False)[2].item())]
+            return pd.DataFrame(out)
     Xd, _, yd, C = _multinomial_frame("multinomial_model_eval", sample_df, Y_name, classes, fit_intercept, dummy_info,
                                       dummy_factors_baseline, data_info, for_eval=True)
     X = engine.row_major(Xd)
-    pard = np.asarray(par, dtype=np.float64)
     out = {}
     for i in range(pard.shape[1]):
         b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()

@@ -713,6 +713,35 @@ int dlsa_onehot_tweedie_fit_f64(const dlsa_onehot_plan* plan, const double* num,
                                 int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
                                 double* deviance_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Multinomial logistic map step on the raw representation of a one-hot design (the structured sibling of
+ * dlsa_multinomial_*_f64) ----------
+ * Rows, plan, column order and unknown codes as dlsa_onehot_poisson_*_f64; the model, `classes`, the class-major layout, the outputs
+ * and their meaning as dlsa_multinomial_*_f64 with intercept = 0 and p = the plan's p on the matrix dlsa_design_f64 would build,
+ * which is never built: theta[j p + c] is the coefficient of class j + 1 on the plan's column c, and an intercept is the plan's
+ * constant column, one column of every class block.  2 <= classes <= 8 and (classes - 1) p <= 2048, else DLSA_ERR_INVALID.  No
+ * offsets.
+ * dlsa_onehot_multinomial_pass_f64: one read of the raw rows (8q + 4f + 8 bytes per row, + 8 (classes - 1) when the probabilities
+ * are stored) and, when H is wanted (ldh >= (classes - 1) p), one weight kernel and one structured Gram per block pair j <= k, each
+ * written straight into its p x p window of H in ordered floating point, and the mirror of the blocks below the block diagonal.
+ * loglik is NaN when a response is no class code; prob_out (nullable) as dlsa_multinomial_pass_f64 (class-major, ldprob >= n a
+ * multiple of 32, 256-byte aligned).  g, loglik, H and prob_out are bit-reproducible (unless dlsa_kernel_options sets
+ * onehot_ordered = 0).
+ * dlsa_onehot_multinomial_fit_f64: partitions as dlsa_onehot_poisson_fit_f64 (num / codes of a strided partition read in place,
+ * its responses gathered), the fit of dlsa_multinomial_fit_f64 -- every partition is checked before any is fitted, a response
+ * that is no class code or a class without a row is DLSA_ERR_INVALID naming the partition; the start puts the plan's constant
+ * column, if it has one, at log(n_j / n_0) in class block j --, the same outputs on (classes - 1) p coefficients and the same
+ * statuses.
+ * Workspace: dlsa_onehot_multinomial_workspace_bytes(plan, max rows, classes, row_step) (0 for a null plan, classes outside
+ * 2 .. 8, (classes - 1) p > 2048, max_rows < 0 or row_step < 1); the pass takes the same query with row_step = 1. */
+size_t dlsa_onehot_multinomial_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows, int classes, int64_t row_step);
+int dlsa_onehot_multinomial_pass_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                     const double* y, const double* theta, int classes, int64_t n, double* H, int64_t ldh, double* g,
+                                     double* loglik, double* prob_out, int64_t ldprob, void* ws, size_t ws_bytes, void* stream);
+int dlsa_onehot_multinomial_fit_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
+                                    const double* y, const int64_t* part_first_host, const int64_t* part_rows_host, int64_t row_step,
+                                    int K, int classes, double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef,
+                                    int* n_iter_host, int* status_host, double* loglik_host, void* ws, size_t ws_bytes, void* stream);
+
 /* test hook: host-only validation of the Gram tile plan for p (0 = every tile on/above the diagonal
  * is stored exactly once; outputs: workgroup items, tile slots computed, tiles stored). */
 int dlsa_gram_plan_check(int p, int* nitems, int* nslots, int* ntiles);
