@@ -899,7 +899,8 @@ int dlsa_cox_pass_strata_f64(const double* X, int64_t ldx, const double* time, c
                  (long long)n, p, (long long)ldx, (long long)ldh);
     DLSA_REQUIRE(ties == DLSA_COX_TIES_BRESLOW || ties == DLSA_COX_TIES_EFRON, "cox_pass: unknown ties method %d", ties);
     const CoxWs w = cox_workspace((char*)ws, n, p, ties, strata != nullptr);
-    int rc = newton_check_ws("cox", ws, ws_bytes, w.total);
+    // (the pass carves w.total of it; the contract is the query, which also holds a fit's Newton state)
+    int rc = newton_check_ws("cox", ws, ws_bytes, dlsa_cox_strata_workspace_bytes(n, p, ties, strata ? 1 : 0));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     CoxRows rows;

@@ -300,7 +300,8 @@ int dlsa_gamma_pass_f64(const double* X, int64_t ldx, const double* y, const dou
                  (long long)n, p, (long long)ldx, (long long)ldh);
     DLSA_REQUIRE(dispersion > 0 && isfinite(dispersion), "gamma_pass: the dispersion must be positive and finite");
     const GammaLayout l = gamma_layout(n, p, 1);
-    int rc = newton_check_ws("gamma_pass", ws, ws_bytes, l.total);
+    // (the pass carves l.total of it; the contract is the query, which also holds a fit's Newton state)
+    int rc = newton_check_ws("gamma_pass", ws, ws_bytes, dlsa_gamma_workspace_bytes(n, p, intercept, 1));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;

@@ -417,7 +417,8 @@ int dlsa_multinomial_pass_f64(const double* X, int64_t ldx, const double* y, con
                  "multinomial_pass: prob_out needs 256-byte aligned class rows (ldprob >= n, a multiple of 32), got ldprob=%lld",
                  (long long)ldprob);
     const MnLayout l = mn_layout(n, p, J, 1);
-    rc = newton_check_ws("multinomial_pass", ws, ws_bytes, l.total);
+    // (the pass carves l.total of it; the contract is the query, which also holds a fit's Newton state)
+    rc = newton_check_ws("multinomial_pass", ws, ws_bytes, dlsa_multinomial_workspace_bytes(n, p, intercept, classes, 1));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;

@@ -216,7 +216,8 @@ int dlsa_poisson_pass_f64(const double* X, int64_t ldx, const double* y, const d
     DLSA_REQUIRE(n >= 1 && p > 0 && pe <= 2048 && ldx >= p && (!H || ldh >= pe), "poisson_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
                  (long long)n, p, (long long)ldx, (long long)ldh);
     const PoisLayout l = pois_layout(n, p, 1);
-    int rc = newton_check_ws("poisson_pass", ws, ws_bytes, l.total);
+    // (the pass carves l.total of it; the contract is the query, which also holds a fit's Newton state)
+    int rc = newton_check_ws("poisson_pass", ws, ws_bytes, dlsa_poisson_workspace_bytes(n, p, intercept, 1));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;

@@ -294,7 +294,8 @@ int dlsa_tweedie_pass_f64(const double* X, int64_t ldx, const double* y, const d
     DLSA_REQUIRE(tweedie_power_ok(power), "tweedie_pass: the variance power must lie strictly between 1 and 2");
     DLSA_REQUIRE(dispersion > 0 && isfinite(dispersion), "tweedie_pass: the dispersion must be positive and finite");
     const TweedieLayout l = tweedie_layout(n, p, 1);
-    int rc = newton_check_ws("tweedie_pass", ws, ws_bytes, l.total);
+    // (the pass carves l.total of it; the contract is the query, which also holds a fit's Newton state)
+    int rc = newton_check_ws("tweedie_pass", ws, ws_bytes, dlsa_tweedie_workspace_bytes(n, p, intercept, 1));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;

@@ -11,7 +11,12 @@
  *   - matrices are row-major; `ld*` are leading dimensions in ELEMENTS;
  *   - the caller owns all memory; the library never allocates what it returns.  Scratch
  *     comes from a caller-provided device workspace (`ws`, `ws_bytes`), sized by the
- *     matching *_workspace_bytes() query; the workspace must be 256-byte aligned;
+ *     matching *_workspace_bytes() query; the workspace must be 256-byte aligned.  An entry refuses fewer bytes than its
+ *     query with DLSA_ERR_WORKSPACE (the exceptions, stated where they are declared: the dlsa_gram_* entries, dlsa_loglik*_f64
+ *     and dlsa_xtv_f32 check the need of the kernel the shape takes, which is at most the query, and the logistic fits accept
+ *     one chain's slice), writes nothing outside [ws, ws + ws_bytes) and its results do not depend on what the workspace
+ *     held before the call (tests/test_gpu_workspace_contract.py runs every entry on exactly the query, poisoned, between
+ *     guards);
  *   - all device work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the
  *     default stream).  Functions that return host scalars synchronise that stream;
  *   - return value: 0 = DLSA_OK, otherwise a dlsa_status; dlsa_last_error() has the text.
@@ -82,7 +87,10 @@ int dlsa_synth_linear_f32(uint64_t seed, int64_t row0, int64_t n, int p, int one
 /* ---- K3: weighted tall-skinny Gram  H = X' diag(w) X  (dlsa/models.py:130) ------------
  * X: n x p, w: n (NULL = all ones, the linear-model X'X), H: p x p (ldh >= p), both
  * triangles written (exactly symmetric).  accumulate != 0 adds into H.
- * fp64 uses v_mfma_f64_16x16x4_f64; fp32 uses v_mfma_f32_16x16x4_f32. */
+ * fp64 uses v_mfma_f64_16x16x4_f64; fp32 uses v_mfma_f32_16x16x4_f32.
+ * Workspace: the query bounds every kernel the dispatch may take for (n, p) and is non-decreasing in n; an entry checks the
+ * need of the kernel it takes (named in the error text), so fewer bytes than the query may pass for one shape and not for the
+ * next: bring the query. */
 size_t dlsa_gram_workspace_bytes(int64_t n, int p, int elem_bytes);
 int dlsa_gram_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p,
                   double* H, int64_t ldh, int accumulate, void* ws, size_t ws_bytes, void* stream);
@@ -112,7 +120,8 @@ int dlsa_logit_pass_f64(const double* X, int64_t ldx, const double* y, const dou
 
 /* ---- N1: log-likelihood of c estimator columns (dlsa/models.py:217-222) ---------------
  * par: p x c row-major (ldpar >= c), c <= 8; out: c values.  One read of X for all columns.
- * Workspace: dlsa_logit_workspace_bytes(n, p) is sufficient. */
+ * Workspace: dlsa_logit_workspace_bytes(n, p) is sufficient (the per-block sums take 128 KiB of it, which is what the entry
+ * checks). */
 int dlsa_loglik_f64(const double* X, int64_t ldx, const double* y, int64_t n, int p,
                     const double* par, int64_t ldpar, int c, double* out,
                     void* ws, size_t ws_bytes, void* stream);
@@ -122,7 +131,8 @@ int dlsa_loglik_f64(const double* X, int64_t ldx, const double* y, int64_t n, in
  * dlsa_logit_workspace_bytes. */
 int dlsa_xtv_f64(const double* X, int64_t ldx, const double* v, int64_t n, int p,
                  double* g, double* vv, void* ws, size_t ws_bytes, void* stream);
-/* fp32 rows (wide-p linear config): fp64 accumulation, fp32 results; workspace 2x the fp64 query */
+/* fp32 rows (wide-p linear config): fp64 accumulation, fp32 results; workspace 2x the fp64 query (the entry checks what its
+ * partials take, at most that) */
 int dlsa_xtv_f32(const float* X, int64_t ldx, const float* v, int64_t n, int p,
                  float* g, float* vv, void* ws, size_t ws_bytes, void* stream);
 
@@ -208,7 +218,12 @@ int dlsa_irls_set_options(const dlsa_irls_options* opt);         /* NULL: back t
  * Outputs (device): coef K x p, Sig_inv K x p x p (evaluated at coef, models.py:130),
  * Sig_invMcoef K x p (models.py:131).  Host outputs (nullable): n_iter[K], status[K]
  * (dlsa_part_status), loglik[K].  If X is to carry an intercept, the caller materialises the
- * leading ones column (models.py:121-122) -- see dlsa_synth_f64(ones_col). */
+ * leading ones column (models.py:121-122) -- see dlsa_synth_f64(ones_col).
+ * Workspace: the query is one slice per partition chain (1 .. 8: dlsa_irls_options.chains; automatic: 4, or 1 for partitions
+ * beyond 8 GB).  At the query the fit takes the driver the shapes pick: as many chains as the options allow, the one-launch
+ * kernel (whose K * 32 + 512 bytes always fit one slice: K <= 8192 there and a slice is never below 4 MiB) or the lock step
+ * (memory from the stream's pool, not from ws).  More bytes change nothing; fewer, down to ONE slice (the query under
+ * chains = 1), are accepted and only lower the number of chains; below one slice the call is DLSA_ERR_WORKSPACE. */
 size_t dlsa_irls_workspace_bytes(int64_t max_rows_per_partition, int p);
 int dlsa_irls_fit_f64(const double* X, int64_t ldx, const double* y,
                       const int64_t* part_offsets_host, int K, int p,
@@ -247,6 +262,10 @@ int dlsa_newton_wide_pass_f64(const double* X, int64_t ldx, const double* y, con
 size_t dlsa_gram_icpt_workspace_bytes(int64_t n, int p);
 int dlsa_gram_icpt_f64(const double* X, int64_t ldx, const double* w, int64_t n, int p, double* H, int64_t ldh,
                        void* ws, size_t ws_bytes, void* stream);
+/* Workspace of dlsa_irls_fit_ex_f64: one slice per chain as dlsa_irls_workspace_bytes (each with the gathered labels of a strided
+ * partition) plus 1 MiB, and the whole query is required.  The one-launch kernel keeps K * 32 + 512 bytes of per-partition
+ * results in it: a call whose shapes pick that kernel with more partitions than the query holds (beyond ~160 000 under
+ * chains = 1, ~550 000 on automatic) returns DLSA_ERR_WORKSPACE naming the bytes to bring. */
 size_t dlsa_irls_ex_workspace_bytes(int64_t max_rows_per_partition, int p, int intercept, int64_t row_step);
 int dlsa_irls_fit_ex_f64(const double* X, int64_t ldx, const double* y, const int64_t* part_first_host,
                          const int64_t* part_rows_host, int64_t row_step, int K, int p, int intercept, double tol, int max_iter,
