@@ -175,6 +175,14 @@ static PinvLayout pinv_layout(int p) {
 
 size_t sym_pinv_workspace_bytes_impl(int p) { return pinv_layout(p).total; }
 
+// out[i] = L[i][i], out[p + i] = S[i][i]: the two diagonals wls_solve reads back, packed for ONE contiguous copy on the caller's
+// stream (a strided device-to-host hipMemcpy2DAsync into pageable memory waits for the default stream: on a side stream the entry
+// then stalls behind whatever other work the process has queued there)
+__global__ void diag_pair_kernel(const double* __restrict__ L, int p, const double* __restrict__ S, int64_t lds, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < p) { out[i] = L[(int64_t)i * (p + 1)]; out[p + i] = S[(int64_t)i * (lds + 1)]; }
+}
+
 // theta = pinv(S) v with the lstsq(rcond) cut; eig_host (nullable, p values) receives the eigenvalues, rank_host the rank,
 // sweeps_host the number of sweeps taken, V_out (nullable, device, p rows of pitch ldv) the eigenvectors as columns, in the order
 // of eig_host
@@ -287,11 +295,16 @@ int dlsa_wls_solve_f64(const double* S, int64_t lds, const double* v, int p, dou
     double* stats = (double*)ar.take(4 * sizeof(double));
     int rc = launch_chol_solve(S, lds, 0, v, 0, nullptr, 0, p, 1, L, theta, 0, stats, 0, s, 0);
     if (rc) return rc;
-    std::vector<double> dl((size_t)p), ds((size_t)p);
+    // (the query is at least the spectral path's four m x m matrices: room for 2 p doubles behind L and the statistics)
+    double* diag = (double*)ar.take(2 * (size_t)p * sizeof(double));
+    if (!L || !stats || !diag) { set_error("wls_solve: workspace %zu bytes needed (256-aligned), got %zu", need, ws_bytes); return DLSA_ERR_WORKSPACE; }
+    hipLaunchKernelGGL(diag_pair_kernel, dim3((p + 255) / 256), dim3(256), 0, s, (const double*)L, p, S, lds, diag);
+    DLSA_HIP_CHECK(hipGetLastError());
+    std::vector<double> dl(2 * (size_t)p);
+    const double* ds = dl.data() + p;
     double h[3];
     DLSA_HIP_CHECK(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, s));
-    DLSA_HIP_CHECK(hipMemcpy2DAsync(dl.data(), sizeof(double), L, (size_t)(p + 1) * sizeof(double), sizeof(double), (size_t)p, hipMemcpyDeviceToHost, s));
-    DLSA_HIP_CHECK(hipMemcpy2DAsync(ds.data(), sizeof(double), S, (size_t)(lds + 1) * sizeof(double), sizeof(double), (size_t)p, hipMemcpyDeviceToHost, s));
+    DLSA_HIP_CHECK(hipMemcpyAsync(dl.data(), diag, 2 * (size_t)p * sizeof(double), hipMemcpyDeviceToHost, s));
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     if (h[2] == 2.0) {
         // a non-finite pivot or solution: NaN/Inf in (S, v) -- or finite entries so large that the arithmetic which continues past
