@@ -10,7 +10,9 @@ struct LarsArgs {
     const double* Sigma0;   // p x p
     const double* b0;       // p
     int64_t lds0;
-    int p, intercept, type, max_steps;
+    int p, intercept, type, max_steps;   // intercept: 1 when exactly ONE leading coefficient is unpenalised (the scalar Schur complement), else 0
+    int unpen;        // u, the number of leading unpenalised coefficients (m = p - u); u >= 2: the kernels subtract V'V instead
+    const double* V;  // u >= 2: u x ld, L^{-1} Sigma0[:u, u:] with L the Cholesky factor of Sigma0[:u,:u] (lars_unpen.hip; pad column zero)
     double n, eps;
     // workspace
     double* S;        // m x ld scaled Sigma (ld = m rounded up to even; the pad column is zero)
@@ -20,7 +22,7 @@ struct LarsArgs {
     int* ivec;        // 4 int vectors of length m
     // outputs
     double* beta_path; double* beta0; double* aic; double* bic;
-    int* n_steps;     // device scalar
+    int* n_steps;     // device scalar; u >= 2: n_steps[1] is the prepare kernel's flag (0, or 1 + the index of the bad pivot of A11)
     // multi-workgroup kernel only
     double* rbuf;     // m: r = R^{-T} x of the current append, gathered from the row owners
     double* wbuf;     // m: equiangular weights, gathered from the row owners
@@ -31,6 +33,26 @@ struct LarsArgs {
 };
 
 extern std::mutex g_lars_grid_mu;      // lars.hip: serialises this process's multi-workgroup path launches (launch .. completion)
+
+// In the functions below `intercept` is the COUNT u of leading unpenalised coefficients and m = p - u.  Which kernel takes a width
+// is decided by m; lars.hip's own choices (workgroups, 512 / 1024 threads) are keyed as before u >= 2 existed, by m + (u ? 1 : 0).
+inline int lars_keyed_p(int p, int intercept) { return p - intercept + (intercept ? 1 : 0); }
+
+// lars_unpen.hip: u >= 2.  prepare: one workgroup, writes a.V and the flag a.n_steps[1] (and zeroes a.n_steps[0]); the path kernels
+// leave at once when the flag is set.  finish: a.beta0[k][r] for k <= *a.n_steps from a.beta_path (nothing when *a.n_steps < 0).
+int lars_unpen_prepare(const LarsArgs& a, hipStream_t s);
+int lars_unpen_finish(const LarsArgs& a, int rows, hipStream_t s);
+#if defined(__HIPCC__)
+// The term the prologues subtract from Sigma0[u + i][u + j] when u >= 2: (V'V)[i][j] = sum_r V[r][i] V[r][j], in the fixed order
+// r = 0 .. u - 1.  The path kernels read rows of S for columns, so S must be symmetric TO THE BIT: a product commutes, also inside an
+// fma, so (i, j) and (j, i) give the same bits -- which A12' (A11^-1 A12) would not.  V is read from global memory (u m doubles,
+// L2-resident; m^2 u loads once per call).
+__device__ __forceinline__ double lars_unpen_term(const double* __restrict__ V, int ld, int u, int i, int j) {
+    double s = 0.0;
+    for (int r = 0; r < u; ++r) s = fma(V[(int64_t)r * ld + i], V[(int64_t)r * ld + j], s);
+    return s;
+}
+#endif
 
 // lars_q.hip: the path kernel for narrow problems (m = p - intercept <= LARS_Q_MAX_M)
 constexpr int LARS_Q_MAX_M = 1020;

@@ -288,7 +288,8 @@ __global__ __launch_bounds__(LARS_THREADS) void lars_kernel(LarsArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];     // sh_part[2*LARS_THREADS] | sh_w, sh_x, sh_r, sh_t, sh_gi1 [m] | sh_act[m]
     const int tid = threadIdx.x;
     const int p = a.p;
-    const int off = a.intercept ? 1 : 0;
+    const int off = a.unpen;
+    if (a.unpen >= 2 && a.n_steps[1] != 0) return;      // A11 is not positive definite (lars_unpen.hip): every workgroup leaves, no path
     const int m = p - off;
     const int ld = (m + 1) & ~1;
     const double eps = a.eps;
@@ -346,6 +347,7 @@ __global__ __launch_bounds__(LARS_THREADS) void lars_kernel(LarsArgs a) {
         if (j < m) {
             v = a.Sigma0[(int64_t)(i + off) * a.lds0 + (j + off)];
             if (a.intercept) v -= a12[i] * a12[j] / a11;
+            else if (a.unpen >= 2) v -= lars_unpen_term(a.V, ld, a.unpen, i, j);
             v = absb[i] * v * absb[j];
         }
         S[e] = v;
@@ -672,7 +674,8 @@ __global__ __launch_bounds__(LARS_THREADS) void lars_grid_kernel(LarsArgs a) {
     const int tid = threadIdx.x;
     const int g = blockIdx.x, G = gridDim.x;
     const int p = a.p;
-    const int off = a.intercept ? 1 : 0;
+    const int off = a.unpen;
+    if (a.unpen >= 2 && a.n_steps[1] != 0) return;      // A11 is not positive definite (lars_unpen.hip): every workgroup leaves, no path
     const int m = p - off;
     const int ld = (m + 1) & ~1;
     const int mo = m / G + 2;                        // own-list capacity
@@ -727,6 +730,7 @@ __global__ __launch_bounds__(LARS_THREADS) void lars_grid_kernel(LarsArgs a) {
             if (j < m) {
                 v = a.Sigma0[(int64_t)(i + off) * a.lds0 + (j + off)];
                 if (a.intercept) v -= tv[i] * tv[j] / a11;
+                else if (a.unpen >= 2) v -= lars_unpen_term(a.V, ld, a.unpen, i, j);
                 v = rw[i] * v * rw[j];
             }
             S[(int64_t)i * ld + j] = v;
@@ -939,8 +943,8 @@ static int lars_workgroups(int p) {
 
 // launch of this build's kernels (the C ABI entry below picks the build by p)
 int lars_run(LarsArgs& a, int p, int intercept, hipStream_t s, int max_wgs, int* wgs_used) {
-    const size_t mm = (size_t)(p - (intercept ? 1 : 0));
-    int wgs = std::min(lars_workgroups(p), std::max(1, max_wgs));
+    const size_t mm = (size_t)(p - intercept);
+    int wgs = std::min(lars_workgroups(lars_keyed_p(p, intercept)), std::max(1, max_wgs));
     if (wgs > kNumCU) wgs = 1;                   // (the spinning barrier needs a CU per workgroup)
     // the grid kernel replicates more vectors in LDS; beyond its limit (m ~ 2440) the single-workgroup kernel still fits
     if (wgs > 1 && (size_t)LARS_THREADS * 16 + mm * 60 + (mm / wgs + 2) * 12 + 64 > (size_t)kLdsBytes) wgs = 1;
@@ -995,7 +999,9 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
                       double* bic, int* n_steps_host, void* ws, size_t ws_bytes, void* stream) {
     using namespace dlsa;
     DLSA_REQUIRE(Sigma0 && b0 && beta_path && beta0 && aic && bic, "lars_lsa: null argument");
-    DLSA_REQUIRE(p > (intercept ? 1 : 0) && lds >= p, "lars_lsa: bad shape p=%d lds=%lld", p, (long long)lds);
+    DLSA_REQUIRE(intercept >= 0 && intercept <= DLSA_LARS_MAX_UNPENALIZED,
+                 "lars_lsa: %d unpenalised coefficients asked for (0 .. %d)", intercept, DLSA_LARS_MAX_UNPENALIZED);
+    DLSA_REQUIRE(p > intercept && lds >= p, "lars_lsa: bad shape p=%d lds=%lld with %d unpenalised coefficients", p, (long long)lds, intercept);
     DLSA_REQUIRE(type == 0 || type == 1, "lars_lsa: type must be 0 ('lar') or 1 ('lasso')");
     DLSA_REQUIRE(n > 0, "lars_lsa: sample size must be positive");
     if (!ws || ws_bytes < dlsa_lars_workspace_bytes(p) || ((uintptr_t)ws & 255)) {
@@ -1006,7 +1012,8 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
     Arena ar(ws, ws_bytes);
     const size_t m = (size_t)p, ld = (m + 1) & ~(size_t)1;
     LarsArgs a;
-    a.Sigma0 = Sigma0; a.b0 = b0; a.lds0 = lds; a.p = p; a.intercept = intercept ? 1 : 0; a.type = type;
+    const int u = intercept, mr = p - u;            // mr penalised variables: what every choice by width below looks at
+    a.Sigma0 = Sigma0; a.b0 = b0; a.lds0 = lds; a.p = p; a.intercept = u == 1 ? 1 : 0; a.unpen = u; a.type = type;
     a.max_steps = max_steps; a.n = n; a.eps = eps;
     a.S = (double*)ar.take(m * ld * 8);
     a.Rinv = (double*)ar.take((m * ld + LARS_SLACK) * 8);
@@ -1019,13 +1026,35 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
     a.upart = (double*)ar.take((size_t)LARS_MAX_WGS * ld * 8);
     a.bar = (unsigned*)ar.take(256);
     a.beta_path = beta_path; a.beta0 = beta0; a.aic = aic; a.bic = bic;
+    // u >= 2: V (u x ld(mr)) lies in the S region behind the mr x ld(mr) reduced matrix -- the region holds p ld(p) doubles and
+    // p ld(p) - mr ld(mr) >= (p - mr) ld(p) = u ld(p) >= u ld(mr) for either parity of p and of mr (ld(x) = x rounded up to even is
+    // monotone).  No path kernel writes S beyond mr ld(mr), so a rerun finds V where the prepare kernel left it.
+    a.V = u >= 2 ? a.S + (size_t)mr * (((size_t)mr + 1) & ~(size_t)1) : nullptr;
+    if (u >= 2) { const int rc = lars_unpen_prepare(a, s); if (rc) return rc; }
+    int hs[2] = {0, 0}, wgs_used = 1;     // n_steps, and for u >= 2 the prepare kernel's flag beside it: one copy, one synchronisation
+    int& steps = hs[0];
+    const size_t ncopy = u >= 2 ? 2 : 1;
+    // the path is complete (steps >= 0, read after the stream's synchronisation): u >= 2 checks the prepare kernel's flag, which made
+    // the path kernels leave at once, and enqueues the beta0 rows
+    auto done = [&](int steps) -> int {
+        if (u >= 2) {
+            const int flag = hs[1];
+            if (flag != 0) {
+                set_error("lars_lsa: the block of the %d unpenalised coefficients is not positive definite (pivot %d of its Cholesky factor)", u, flag - 1);
+                return DLSA_ERR_NOT_SPD;
+            }
+            const int rc = lars_unpen_finish(a, steps + 1, s);
+            if (rc) return rc;
+        }
+        if (n_steps_host) *n_steps_host = steps;
+        return DLSA_OK;
+    };
     // 512-thread workgroups up to p = 768, 1024-thread ones beyond (DLSA_LARS_THREADS=512|1024 forces a build)
-    bool small_wg = p <= 768;
+    bool small_wg = lars_keyed_p(p, u) <= 768;
     if (const char* e = kernel_knob("DLSA_LARS_THREADS")) small_wg = atoi(e) == 512;
     // ticks of the 100 MHz wall clock a workgroup of the grid kernel waits at one grid barrier (normally microseconds) before it
     // gives the launch up: 0.25 s
     a.bar_timeout = g_lars_barrier_timeout_ticks.load();
-    int steps = 0, wgs_used = 1;
     const bool use_c = lars_c_eligible(p, intercept);
     if (!use_c && lars_q_eligible(p, intercept)) {
         // up to 448 variables (1020 when the column-split kernel is switched off): the carried Cholesky rows (lars_q.hip) -- one workgroup, or a few that share the fused pass and meet
@@ -1034,10 +1063,10 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
         for (int attempt = 0; attempt < 2; ++attempt) {
             std::unique_lock<std::mutex> grid_lock(g_lars_grid_mu, std::defer_lock);
             const int max_wgs = attempt == 0 ? LARS_MAX_WGS : 1;
-            if (max_wgs > 1 && p - (intercept ? 1 : 0) > 108) grid_lock.lock();
+            if (max_wgs > 1 && mr > 108) grid_lock.lock();
             const int rc = lars_q_run(a, p, intercept, s, max_wgs, &wgs_used);
             if (rc) return rc;
-            DLSA_HIP_CHECK(hipMemcpyAsync(&steps, a.n_steps, sizeof(int), hipMemcpyDeviceToHost, s));
+            DLSA_HIP_CHECK(hipMemcpyAsync(hs, a.n_steps, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
             DLSA_HIP_CHECK(hipStreamSynchronize(s));
             if (steps >= 0) break;
             g_lars_grid_aborts.fetch_add(1);
@@ -1046,8 +1075,7 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
                 return DLSA_ERR_HIP;
             }
         }
-        if (n_steps_host) *n_steps_host = steps;
-        return DLSA_OK;
+        return done(steps);
     }
     int first_attempt = 0;
     if (use_c) {
@@ -1056,12 +1084,9 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
         std::unique_lock<std::mutex> grid_lock(g_lars_grid_mu);
         const int rc = lars_c_run(a, p, intercept, s, &wgs_used);
         if (rc) return rc;
-        DLSA_HIP_CHECK(hipMemcpyAsync(&steps, a.n_steps, sizeof(int), hipMemcpyDeviceToHost, s));
+        DLSA_HIP_CHECK(hipMemcpyAsync(hs, a.n_steps, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
         DLSA_HIP_CHECK(hipStreamSynchronize(s));
-        if (steps >= 0) {
-            if (n_steps_host) *n_steps_host = steps;
-            return DLSA_OK;
-        }
+        if (steps >= 0) return done(steps);
         g_lars_grid_aborts.fetch_add(1);
         first_attempt = 1;
     }
@@ -1073,10 +1098,10 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
         // other's queued workgroups need.  Other processes on the same GPU are covered by the barrier's timeout alone.
         std::unique_lock<std::mutex> grid_lock(g_lars_grid_mu, std::defer_lock);
         const int max_wgs = attempt == 0 ? LARS_MAX_WGS : 1;
-        if (max_wgs > 1 && p >= 256) grid_lock.lock();
+        if (max_wgs > 1 && lars_keyed_p(p, u) >= 256) grid_lock.lock();
         const int rc = small_wg ? lars_t512::lars_run(a, p, intercept, s, max_wgs, &wgs_used) : lars_t1024::lars_run(a, p, intercept, s, max_wgs, &wgs_used);
         if (rc) return rc;
-        DLSA_HIP_CHECK(hipMemcpyAsync(&steps, a.n_steps, sizeof(int), hipMemcpyDeviceToHost, s));
+        DLSA_HIP_CHECK(hipMemcpyAsync(hs, a.n_steps, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
         DLSA_HIP_CHECK(hipStreamSynchronize(s));
         if (steps >= 0) break;
         // the grid kernel gave up at a barrier (its workgroups were not all resident within the timeout): the single-workgroup
@@ -1087,8 +1112,7 @@ int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p
             return DLSA_ERR_HIP;
         }
     }
-    if (n_steps_host) *n_steps_host = steps;
-    return DLSA_OK;
+    return done(steps);
 }
 
 // Test / diagnostics hook for the bounded grid barrier of lars_grid_kernel (not a reference entry: the reference's lars_lsa,

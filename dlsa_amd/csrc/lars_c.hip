@@ -227,7 +227,8 @@ __global__ __launch_bounds__(CT) void lars_c_kernel(LarsArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int p = a.p;
-    const int off = a.intercept ? 1 : 0;
+    const int off = a.unpen;
+    if (a.unpen >= 2 && a.n_steps[1] != 0) return;      // A11 is not positive definite (lars_unpen.hip): every workgroup leaves, no path
     const int m = p - off;
     const int ld = (m + 1) & ~1;
     const double eps = a.eps;
@@ -294,6 +295,7 @@ __global__ __launch_bounds__(CT) void lars_c_kernel(LarsArgs a) {
             if (j < m) {
                 val = a.Sigma0[(int64_t)(i + off) * a.lds0 + (j + off)];
                 if (a.intercept) val -= a12i * gi1[j] / a11;
+                else if (a.unpen >= 2) val -= lars_unpen_term(a.V, ld, a.unpen, i, j);
                 val = ai * val * tv[j];
             }
             S[(int64_t)i * ld + j] = val;
@@ -589,7 +591,7 @@ __global__ __launch_bounds__(CT) void lars_c_kernel(LarsArgs a) {
 // gather -- 3.4 -> 3.0 us of a step at m = 2000, the path's time unchanged (35.0 ms): the gather waits for a fabric round trip to rows
 // other XCDs wrote (every grid barrier's agent-scope acquire empties this XCD's L2), not for its own access pattern.
 bool lars_c_eligible(int p, int intercept) {
-    const int m = p - (intercept ? 1 : 0);
+    const int m = p - intercept;
     if (m > LARS_C_MAX_M || lars_c_lds_bytes(m) + 1024 > (size_t)kLdsBytes) return false;
     // dlsa_kernel_options.lars_q: automatic = the measured hand-over (LARS_C_MIN_M); 0: lars.hip for every width; 1: lars_q.hip for every
     // width it takes (<= LARS_Q_MAX_M), this kernel beyond; 2: this kernel for every width it can take (A/B runs, tests)
@@ -604,7 +606,7 @@ bool lars_c_eligible(int p, int intercept) {
 // dlsa_kernel_options.lars_wgs overrides (2 .. LARS_C_MAX_WGS; every count gives the same path: the sums over the rows are taken in
 // an order that depends on the count only to rounding).
 int lars_c_run(LarsArgs& a, int p, int intercept, hipStream_t s, int* wgs_used) {
-    const int m = p - (intercept ? 1 : 0);
+    const int m = p - intercept;
     const int ld = (m + 1) & ~1, nblk = (ld + 15) / 16;
     int nwg = (nblk + 1) / 2;
     if (const char* e = kernel_knob("DLSA_LARS_WGS")) nwg = atoi(e);

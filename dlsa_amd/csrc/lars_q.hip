@@ -337,7 +337,8 @@ __global__ __launch_bounds__(T) void lars_q_kernel(LarsArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int p = a.p;
-    const int off = a.intercept ? 1 : 0;
+    const int off = a.unpen;
+    if (a.unpen >= 2 && a.n_steps[1] != 0) return;      // A11 is not positive definite (lars_unpen.hip): every workgroup leaves, no path
     const int m = p - off;
     const int ld = (m + 1) & ~1;
     const int NQ = ld >> 1;
@@ -412,6 +413,7 @@ __global__ __launch_bounds__(T) void lars_q_kernel(LarsArgs a) {
         if (j < m) {
             val = a.Sigma0[(int64_t)(i + off) * a.lds0 + (j + off)];
             if (a.intercept) val -= a12[i] * a12[j] / a11;
+            else if (a.unpen >= 2) val -= lars_unpen_term(a.V, ld, a.unpen, i, j);
             val = absb[i] * val * absb[j];
         }
         S[e] = val;
@@ -696,7 +698,7 @@ constexpr size_t LARS_Q_STATIC_LDS = 1024;      // red, sh_i and alignment
 
 // DLSA_LARS_Q=0 keeps lars.hip's kernels for every width (A/B runs, tests of both forms)
 bool lars_q_eligible(int p, int intercept) {
-    const int m = p - (intercept ? 1 : 0);
+    const int m = p - intercept;
     if (m < 1 || m > LARS_Q_MAX_M) return false;
     if (const char* e = kernel_knob("DLSA_LARS_Q")) return atoi(e) != 0;
     return true;
@@ -713,7 +715,7 @@ static int lars_q_workgroups(int m) {
 
 // DLSA_LARS_Q_THREADS: 256 | 512 | 1024 forces the workgroup size; DLSA_LARS_Q_LDS=0 keeps Q and RT in global memory
 int lars_q_run(LarsArgs& a, int p, int intercept, hipStream_t s, int max_wgs, int* wgs_used) {
-    const int m = p - (intercept ? 1 : 0);
+    const int m = p - intercept;
     int threads = 0;
     if (const char* e = kernel_knob("DLSA_LARS_Q_THREADS")) threads = atoi(e);
     bool want_lds = true;

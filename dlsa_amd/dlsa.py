@@ -14,7 +14,7 @@ import torch
 
 from . import distributed, engine
 from .lsa import lars_path_device
-from .models import MappedBlocks
+from .models import MappedBlocks, intercept_columns
 
 
 def _blocks_from_frame(pdf):
@@ -95,11 +95,45 @@ def dlsa_mapred(model_mapped_sdf, num_partitions=None, comm=None):
     return pd.DataFrame(out, columns=["beta_byOLS", "beta_byONESHOT"] + list(names))
 
 
-def dlsa(Sig_inv_, beta_, sample_size, fit_intercept=False, type="lar"):
+def _unpenalized_indices(unpenalized, Sig_inv_):
+    """dlsa's `unpenalized` as indices: "intercepts" (every column named intercept or intercept:<j>), or a sequence of indices
+    and / or column names; names need Sig_inv_ to be a frame with column names, as dlsa_mapred returns it."""
+    names = [str(c) for c in Sig_inv_.columns] if hasattr(Sig_inv_, "columns") else None
+    if isinstance(unpenalized, str):
+        if unpenalized != "intercepts":
+            raise ValueError("dlsa: unpenalized must be a sequence of indices or names, or the string 'intercepts'; got %r" % unpenalized)
+        if names is None:
+            raise ValueError("dlsa: unpenalized='intercepts' needs Sig_inv_ as a frame with column names (dlsa_mapred's)")
+        return intercept_columns(names)
+    out = []
+    for v in unpenalized:
+        if isinstance(v, str):
+            if names is None:
+                raise ValueError("dlsa: the unpenalized name %r needs Sig_inv_ as a frame with column names (dlsa_mapred's)" % v)
+            if names.count(v) != 1:
+                raise ValueError("dlsa: unpenalized name %r is the name of %d columns" % (v, names.count(v)))
+            out.append(names.index(v))
+        else:
+            out.append(v)
+    return out
+
+
+def dlsa(Sig_inv_, beta_, sample_size, fit_intercept=False, type="lar", unpenalized=None):
     """Distributed Least Squares Approximation (dlsa.py:70-107): LARS path of the quadratic
     (theta - beta_)' Sig_inv_ (theta - beta_) and the path points minimising AIC and BIC.
     With an intercept the intercept estimate is beta0[idx] + beta_[0] (the rpy2 original,
-    dlsa.py:97 comment).  Returns DataFrame {beta_byAIC, beta_byBIC}."""
+    dlsa.py:97 comment).  `unpenalized` -- indices, column names, or "intercepts" for the columns intercept / intercept:<j> of a
+    dlsa_mapred frame -- keeps the named coefficients out of the penalty wherever they stand (the J intercepts of a multinomial
+    block); not together with fit_intercept=True.  Returns DataFrame {beta_byAIC, beta_byBIC} over all p coefficients in the
+    caller's order."""
+    if unpenalized is not None:
+        idx = _unpenalized_indices(unpenalized, Sig_inv_)
+        S = Sig_inv_ if isinstance(Sig_inv_, torch.Tensor) else np.asarray(Sig_inv_, dtype=np.float64)
+        b = beta_ if isinstance(beta_, torch.Tensor) else np.asarray(beta_, dtype=np.float64)
+        fit = lars_path_device(S, b, fit_intercept, sample_size, type=type, unpenalized=idx)
+        ia = int(np.argmin(fit["AIC"].cpu().numpy()))
+        ib = int(np.argmin(fit["BIC"].cpu().numpy()))
+        return pd.DataFrame({"beta_byAIC": fit["theta"][ia].cpu().numpy(), "beta_byBIC": fit["theta"][ib].cpu().numpy()})
     S = np.asarray(Sig_inv_, dtype=np.float64) if not isinstance(Sig_inv_, torch.Tensor) else Sig_inv_
     b = np.asarray(beta_, dtype=np.float64) if not isinstance(beta_, torch.Tensor) else beta_
     fit = lars_path_device(S, b, fit_intercept, sample_size, type=type)

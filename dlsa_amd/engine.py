@@ -1223,9 +1223,30 @@ def sym_pinv_probe(S, v, p, lds, rcond=None, ldv=None):
     return theta, rank.value, list(eig), sweeps.value, V
 
 
+LARS_MAX_UNPENALIZED = 32      # include/dlsa_hip.h: DLSA_LARS_MAX_UNPENALIZED
+
+
+def lars_unpenalized_count(who, intercept, p):
+    """`intercept` of lars_path as the count u of leading unpenalised coefficients: a bool (True is 1) or an integer with
+    0 <= u <= LARS_MAX_UNPENALIZED and u < p."""
+    if isinstance(intercept, bool) or intercept is None:
+        u = 1 if intercept else 0
+    else:
+        u = int(intercept)
+        if u != intercept:
+            raise ValueError("%s: intercept must be a bool or a whole number, got %r" % (who, intercept))
+    if u < 0 or u > LARS_MAX_UNPENALIZED:
+        raise ValueError("%s: %d unpenalised coefficients asked for (0 .. %d)" % (who, u, LARS_MAX_UNPENALIZED))
+    if u >= p:
+        raise ValueError("%s: %d unpenalised coefficients leave nothing to select among p = %d" % (who, u, p))
+    return u
+
+
 def lars_path(Sigma0, b0, intercept, n, type="lar", eps=2.220446049250313e-16, max_steps=None):
-    """LARS / lasso path of the LSA objective on the device (dlsa/lsa.py:90-212).
-    Returns dict of device tensors AIC, BIC [steps+1], beta [steps+1, m], beta0 [steps+1]."""
+    """LARS / lasso path of the LSA objective on the device (dlsa/lsa.py:90-212).  `intercept` is a bool or the count u of LEADING
+    coefficients that are not penalised (True is 1); m = p - u.
+    Returns dict of device tensors AIC, BIC [steps+1], beta [steps+1, m], beta0 [steps+1] for u <= 1 and [steps+1, u] for u >= 2
+    (beta0 excludes b0[:u], as the reference's does: the caller adds it)."""
     lib = _lib.load()
     _require_gpu(Sigma0, b0)
     _f64(Sigma0, "Sigma0")
@@ -1233,18 +1254,19 @@ def lars_path(Sigma0, b0, intercept, n, type="lar", eps=2.220446049250313e-16, m
     p = Sigma0.shape[0]
     if Sigma0.dim() != 2 or Sigma0.shape[1] != p or b0.numel() != p:
         raise ValueError("lars_path: Sigma0 must be p x p and b0 of length p")
-    m = p - (1 if intercept else 0)
+    u = lars_unpenalized_count("lars_path", intercept, p)
+    m = p - u
     # lsa.py:93-94: max_steps defaults to 8 m; the C ABI reads <= 0 as that default, so the buffers are sized for it too
     ms = 8 * m if (max_steps is None or int(max_steps) <= 0) else int(max_steps)
     dev = Sigma0.device
     beta = torch.zeros((ms + 1, m), dtype=torch.float64, device=dev)
-    beta0 = torch.zeros((ms + 1,), dtype=torch.float64, device=dev)
+    beta0 = torch.zeros((ms + 1,) if u <= 1 else (ms + 1, u), dtype=torch.float64, device=dev)
     aic = torch.zeros((ms + 1,), dtype=torch.float64, device=dev)
     bic = torch.zeros((ms + 1,), dtype=torch.float64, device=dev)
     nb = lib.dlsa_lars_workspace_bytes(p)
     ws = _workspace(nb, dev)
     steps = ctypes.c_int(0)
-    check(lib.dlsa_lars_lsa_f64(_ptr(Sigma0), _rowmajor(Sigma0), _ptr(b0), p, 1 if intercept else 0,
+    check(lib.dlsa_lars_lsa_f64(_ptr(Sigma0), _rowmajor(Sigma0), _ptr(b0), p, u,
                                 float(n), {"lar": 0, "lasso": 1}[type], float(eps), ms,
                                 _ptr(beta), _ptr(beta0), _ptr(aic), _ptr(bic), ctypes.byref(steps),
                                 _ptr(ws), ws.numel(), _stream()))

@@ -1178,7 +1178,8 @@ def tweedie_model_eval(sample_df, Y_name, par, power, dispersion, fit_intercept=
 # Multinomial logistic (softmax) map step for a response with C unordered classes (delay cause, product chosen, diagnosis group).
 # Class 0 is the reference class; the parameter is class-major, theta = [beta_1 | ... | beta_J] with J = C - 1, so a partition's block
 # is [coef | Sig_inv coef | Sig_inv] over J * pe coefficients named "<name>:<j>", and dlsa_mapred applies unchanged.  dlsa() knows
-# one unpenalised intercept at position 0: multinomial blocks go through dlsa(..., fit_intercept=False).
+# one unpenalised intercept at position 0 through fit_intercept=True; multinomial blocks with intercepts go through
+# dlsa(..., unpenalized="intercepts") (intercept_columns below), those without through dlsa(..., fit_intercept=False).
 # ---------------------------------------------------------------------------------------------
 def simulate_multinomial(sample_size, p, partition_num, classes, seed=20260101, coef_value=1.0):
     """Seeded rows with a class response: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), beta*_j = +-coef_value
@@ -1198,6 +1199,17 @@ def simulate_multinomial(sample_size, p, partition_num, classes, seed=20260101, 
     y = np.minimum((rng.random(n)[:, None] > cdf).sum(1), C - 1).astype(np.float64)
     pid = (np.arange(n) % int(partition_num)).astype(np.float64)
     return pd.DataFrame(np.concatenate([pid[:, None], y[:, None], X], 1), columns=["partition_id", "y"] + ["x" + str(i) for i in range(p)])
+
+
+def intercept_columns(names):
+    """Indices of the intercept columns among `names`: "intercept" (one-response families) and "intercept:<j>" (class j of a
+    multinomial block) -- what dlsa(..., unpenalized="intercepts") keeps out of the penalty."""
+    out = []
+    for i, nm in enumerate(names):
+        head, sep, tail = str(nm).partition(":")
+        if head == "intercept" and (not sep or tail.isdigit()):
+            out.append(i)
+    return out
 
 
 def multinomial_column_names(names, classes):

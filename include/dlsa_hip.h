@@ -526,9 +526,17 @@ int dlsa_sym_pinv_solve_f64(const double* S, int64_t lds, const double* v, int p
 
 /* ---- a13/a14: LARS path for the least-squares approximation (dlsa/lsa.py:90-212) ------
  * Sigma0 p x p, b0 p (device).  type 0 = 'lar', 1 = 'lasso'.  max_steps <= 0 -> 8*m.
- * Outputs (device): beta_path (max_steps+1) x m row-major (m = p - intercept), beta0,
- * aic, bic (max_steps+1 each); n_steps_host = number of steps taken (path has n_steps+1
- * rows).  Runs as one persistent kernel on the device.  Up to 448 variables the carried-rows
+ * `intercept` is u, the number of LEADING coefficients that are not penalised: 0 <= u <= DLSA_LARS_MAX_UNPENALIZED and u < p
+ * (anything else: DLSA_ERR_INVALID); m = p - u.  With A11 = Sigma0[:u,:u], A12 = Sigma0[:u,u:], A22 = Sigma0[u:,u:] the path is
+ * that of (A22 - A12' A11^-1 A12, b0[u:]) (lsa.py:98-104 for u = 1); dof counts the penalised coefficients only.
+ * Outputs (device): beta_path (max_steps+1) x m row-major, aic, bic (max_steps+1 each), beta0 (max_steps+1) x max(1, u)
+ * row-major [step][r] = (A11^-1 A12 (b0[u:] - beta_k))_r -- the reference's convention at u = 1: b0[:u] is NOT included, the
+ * caller adds it (zeros for u = 0); n_steps_host = number of steps taken (path has n_steps+1
+ * rows).  u <= 1 is one persistent kernel; u >= 2 adds a one-workgroup prepare kernel before it (Cholesky factor L of A11 and
+ * V = L^-1 A12 in the part of the workspace's S region that the reduced matrix leaves free: the kernels subtract V'V, which is
+ * symmetric to the bit) and a finish kernel after it (beta0 from beta_path), all on `stream`.  A pivot of A11 that is not
+ * positive (at most u 2^-50 times its diagonal entry) or not finite: DLSA_ERR_NOT_SPD, the message names it, no path is written.
+ * Runs as one persistent kernel on the device.  Up to 448 variables the carried-rows
  * form (lars_q.hip): one workgroup up to 200 variables, 4 (beyond 420: 8) workgroups that share
  * the fused pass above; 449 .. 2044 variables the same rows with the pass split by COLUMNS over
  * 16 .. 64 workgroups (lars_c.hip, round 6: one grid barrier per append; p = 2000 in 35 ms);
@@ -541,6 +549,7 @@ int dlsa_sym_pinv_solve_f64(const double* S, int64_t lds, const double* v, int p
  * HIP streams created after a process's first cooperative launch serialise on this runtime).
  * p is bounded by the LDS per workgroup: about 2400 columns for the grid kernel, 3300 for
  * the single workgroup it falls back to. */
+#define DLSA_LARS_MAX_UNPENALIZED 32
 size_t dlsa_lars_workspace_bytes(int p);
 int dlsa_lars_lsa_f64(const double* Sigma0, int64_t lds, const double* b0, int p,
                       int intercept, double n, int type, double eps, int max_steps,
