@@ -8,7 +8,7 @@ import contextlib
 import ctypes
 import dataclasses
 import threading
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -642,35 +642,40 @@ def _offset_partitions(who, part_offsets, n, ascending_from_zero=False):
 
 class _FitOut:
     """What a per-partition fit of K partitions with pe coefficients writes: coef / Sig_invMcoef [K, pe] and Sig_inv [K, pe, pe] on the
-    device, n_iter / status / loglik on the host, and with `dispersion` the family's own host lists: True (NB2) alpha / alpha_info /
-    pearson, or their names (Gamma and Tweedie: GAMMA_LISTS).  `args` is the run of output arguments every dlsa_*_fit_* entry takes, in the C
-    ABI's order; result(rc) is the wrappers' result dict."""
+    device, n_iter / status / loglik on the host, and with a log-link `family` (a GLM_FAMILIES record) its own host lists
+    (family.fit_lists).  `args` is the run of output arguments every dlsa_*_fit_* entry takes, in the C ABI's order; result(rc) is the
+    wrappers' result dict."""
 
-    def __init__(self, K, pe, device, dispersion=False):
+    def __init__(self, K, pe, device, family=None):
         self.coef = torch.empty((K, pe), dtype=torch.float64, device=device)
         self.smc = torch.empty((K, pe), dtype=torch.float64, device=device)
         self.sig = torch.empty((K, pe, pe), dtype=torch.float64, device=device)
         self.host = {"n_iter": (ctypes.c_int * K)(), "status": (ctypes.c_int * K)(), "loglik": (ctypes.c_double * K)()}
-        if dispersion:
-            self.host.update({k: (ctypes.c_double * K)() for k in (("alpha", "alpha_info", "pearson") if dispersion is True else dispersion)})
+        if family is not None:
+            self.host.update({k: (ctypes.c_double * K)() for k in family.fit_lists})
         self.args = (_ptr(self.coef), _ptr(self.sig), _ptr(self.smc)) + tuple(self.host.values())
 
-    def result(self, rc):
+    def result(self, rc, df_rows=None):
+        """df_rows: the partitions' row counts of a family whose result carries `df` = rows - pe per partition (what the Pearson
+        estimate of the dispersion divides by)."""
         if rc not in FIT_WROTE_BLOCKS:
             check(rc)
-        return {"coef": self.coef, "Sig_invMcoef": self.smc, "Sig_inv": self.sig, **{k: list(v) for k, v in self.host.items()}, "rc": rc}
+        r = {"coef": self.coef, "Sig_invMcoef": self.smc, "Sig_inv": self.sig, **{k: list(v) for k, v in self.host.items()}, "rc": rc}
+        if df_rows is not None:
+            r["df"] = [int(m) - self.coef.shape[1] for m in df_rows]
+        return r
 
 
-def _pass_out(pe, n, device, want_H, want_w, negbin=False, want_theta=False, want_stats=None):
+def _pass_out(pe, n, device, want_H, want_w, family=None, want=None):
     """The outputs of one pass at a fixed beta, in the order the pass wrappers return them: (H [pe, pe] or None, g [pe], loglik [1],
-    w [n] or None), for NB2 (..., mu [n] or None -- with want_w --, theta_terms [3] or None) and for Gamma and Tweedie (want_stats not None:
-    ..., stats [2] or None)."""
+    w [n] or None), and with a log-link `family` (a GLM_FAMILIES record) its extra outputs family.pass_extra, each asked for by its flag
+    in `want` (or by want_w): NB2's (..., mu [n] or None, theta_terms [3] or None), Gamma's and Tweedie's (..., stats [2] or None)."""
     def new(shape, want=True):
         return torch.empty(shape, dtype=torch.float64, device=device) if want else None
     out = (new((pe, pe), want_H), new((pe,)), new((1,)), new((n,), want_w))
-    if want_stats is not None:
-        return out + (new((2,), want_stats),)
-    return out + (new((n,), want_w), new((3,), want_theta)) if negbin else out
+    if family is None:
+        return out
+    return out + tuple([new((n if size is None else size,), want_w if flag == "want_w" else want[flag]) for size, flag in family.pass_extra])
 
 
 def _alpha_positive(who, alpha, other):
@@ -691,6 +696,102 @@ def _alpha_fixed(who, alpha, other):
     if not 0.0 < alpha < float("inf"):
         raise ValueError("%s: a fixed alpha must be positive and finite" % who)
     return alpha
+
+
+def _dispersion_positive(who, dispersion):
+    """The dispersion of a Gamma pass: a positive finite float."""
+    dispersion = float(dispersion)
+    if not 0.0 < dispersion < float("inf"):
+        raise ValueError("%s: dispersion must be positive and finite" % who)
+    return dispersion
+
+
+def _dispersion_fixed(who, dispersion):
+    """The dispersion argument of a Gamma fit as the C ABI takes it: 0.0 for None (estimate it), else a positive finite float."""
+    return 0.0 if dispersion is None else _dispersion_positive(who, dispersion)
+
+
+def tweedie_power(who, power):
+    """The variance power of a Tweedie entry: a float strictly between 1 and 2 (ValueError otherwise; NaN fails)."""
+    power = float(power)
+    if not 1.0 < power < 2.0:
+        raise ValueError("%s: power must lie strictly between 1 and 2, got %r" % (who, power))
+    return power
+
+
+GAMMA_LISTS = ("dispersion", "pearson", "deviance")
+
+
+class _Scalar(NamedTuple):
+    """One scalar parameter of a log-link family: its keyword name and its checks (who, value) -> the double the C ABI takes, at a pass
+    and at a fit."""
+    name: str
+    at_pass: Callable
+    at_fit: Callable
+
+
+class _Family(NamedTuple):
+    """What varies between the log-link families behind the {,onehot_}<name>_{pass,fit_ex} wrappers; everything else is the four bodies
+    below.  The C entries are dlsa_[onehot_]<name>_{workspace_bytes,pass_f64,fit_f64}."""
+    name: str
+    scalars: tuple = ()         # in the C ABI's order: after beta in a pass, after K, [p, icpt] in a fit
+    pass_extra: tuple = ()      # a pass's outputs after w: (length, or None for n; the want_* flag that asks for it)
+    fit_lists: tuple = ()       # a fit's host lists after loglik, doubles
+    df: bool = False            # a fit's result carries `df`
+    other: Optional[str] = None  # the family a refused parameter value belongs to: the checks get `who` with its name as a third argument
+
+    def checked(self, who, values, fit):
+        """The scalars `values` as the C ABI takes them, checked in its order."""
+        other = (who.replace(self.name, self.other),) if self.other else ()
+        return tuple([(s.at_fit if fit else s.at_pass)(who, v, *other) for s, v in zip(self.scalars, values)])
+
+
+_DISPERSION = _Scalar("dispersion", _dispersion_positive, _dispersion_fixed)
+GLM_FAMILIES = {f.name: f for f in (
+    _Family("poisson"),
+    _Family("negbin", (_Scalar("alpha", _alpha_positive, _alpha_fixed),), ((None, "want_w"), (3, "want_theta")),
+            ("alpha", "alpha_info", "pearson"), other="poisson"),
+    _Family("gamma", (_DISPERSION,), ((2, "want_stats"),), GAMMA_LISTS, df=True),
+    _Family("tweedie", (_Scalar("power", tweedie_power, tweedie_power), _DISPERSION), ((2, "want_stats"),), GAMMA_LISTS, df=True),
+)}
+
+
+def _glm_pass(fam, X, y, beta, scalars, offset, fit_intercept, want_H, want_w, **want):
+    """The body of <name>_pass: dlsa_<name>_pass_f64 on the rows X."""
+    family, who = fam.name, fam.name + "_pass"
+    lib = _lib.load()
+    _require_gpu(X, y, beta, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
+    n, p = X.shape
+    icpt = 1 if fit_intercept else 0
+    pe = p + icpt
+    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
+        raise ValueError("%s: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (who, n, pe))
+    scalars = fam.checked(who, scalars, fit=False)
+    out = _pass_out(pe, n, X.device, want_H, want_w, fam, want)
+    ws = _workspace(getattr(lib, "dlsa_%s_workspace_bytes" % family)(n, p, icpt, 1), X.device)
+    check(getattr(lib, "dlsa_%s_pass_f64" % family)(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), *scalars, n, p, icpt, _ptr(out[0]),
+                                                    pe, *[_ptr(t) for t in out[1:]], _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def _glm_fit(fam, X, y, part_first, part_rows, row_step, offset, fit_intercept, scalars, tol, max_iter):
+    """The body of <name>_fit_ex: dlsa_<name>_fit_f64 on strided partitions of the rows X."""
+    family, who = fam.name, fam.name + "_fit_ex"
+    lib = _lib.load()
+    _require_gpu(X, y, offset)
+    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
+    n, p = X.shape
+    if y.numel() != n or (offset is not None and offset.numel() != n):
+        raise ValueError("%s: y and offset must have n = %d elements" % (who, n))
+    scalars = fam.checked(who, scalars, fit=True)
+    K, step, max_rows, c_first, c_rows = _strided_partitions(who, part_first, part_rows, row_step, n)
+    icpt = 1 if fit_intercept else 0
+    out = _FitOut(K, p + icpt, X.device, fam)
+    ws = _workspace(getattr(lib, "dlsa_%s_workspace_bytes" % family)(max_rows, p, icpt, step), X.device)
+    rc = getattr(lib, "dlsa_%s_fit_f64" % family)(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, *scalars,
+                                                  tol, max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc, c_rows if fam.df else None)
 
 
 def irls_fit_ex(X, y, part_first, part_rows, row_step=1, fit_intercept=False, tol=1e-13, max_iter=100):
@@ -821,38 +922,14 @@ def poisson_pass(X, y, beta, offset=None, fit_intercept=False, want_H=True, want
     """One Poisson partition at a fixed beta (dlsa_poisson_pass_f64): eta = [1 | X] beta + offset, mu = exp(eta).  fit_intercept: the
     ones column is implicit -- beta, g and H have p + 1 entries, intercept first.  Returns (H [pe,pe] = [1 | X]' diag(mu) [1 | X] or
     None, g [pe] = [1 | X]'(y - mu), loglik [1] = sum y eta - mu - lgamma(y + 1), w [n] = mu or None)."""
-    lib = _lib.load()
-    _require_gpu(X, y, beta, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
-    n, p = X.shape
-    icpt = 1 if fit_intercept else 0
-    pe = p + icpt
-    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
-        raise ValueError("poisson_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
-    H, g, ll, w = out = _pass_out(pe, n, X.device, want_H, want_w)
-    ws = _workspace(lib.dlsa_poisson_workspace_bytes(n, p, icpt, 1), X.device)
-    check(lib.dlsa_poisson_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), n, p, icpt, _ptr(H), pe, _ptr(g), _ptr(ll),
-                                    _ptr(w), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_pass(GLM_FAMILIES["poisson"], X, y, beta, (), offset, fit_intercept, want_H, want_w)
 
 
 def poisson_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, tol=1e-13, max_iter=100):
     """Per-partition Poisson fit (dlsa_poisson_fit_f64): partition k = rows part_first[k] + j * row_step, j < part_rows[k] (a strided
     view: partition_id = i % K is part_first = 0..K-1, row_step = K), log link, optional offset [n], implicit intercept with
     fit_intercept.  Same result dict as irls_fit_ex; `loglik` is the full log-likelihood at coef."""
-    lib = _lib.load()
-    _require_gpu(X, y, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
-    n, p = X.shape
-    if y.numel() != n or (offset is not None and offset.numel() != n):
-        raise ValueError("poisson_fit_ex: y and offset must have n = %d elements" % n)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("poisson_fit_ex", part_first, part_rows, row_step, n)
-    icpt = 1 if fit_intercept else 0
-    out = _FitOut(K, p + icpt, X.device)
-    ws = _workspace(lib.dlsa_poisson_workspace_bytes(max_rows, p, icpt, step), X.device)
-    rc = lib.dlsa_poisson_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, tol, max_iter, *out.args,
-                                  _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
+    return _glm_fit(GLM_FAMILIES["poisson"], X, y, part_first, part_rows, row_step, offset, fit_intercept, (), tol, max_iter)
 
 
 def negbin_pass(X, y, beta, alpha, offset=None, fit_intercept=False, want_H=True, want_w=False, want_theta=False):
@@ -860,20 +937,7 @@ def negbin_pass(X, y, beta, alpha, offset=None, fit_intercept=False, want_H=True
     mu = exp(eta), Var y = mu + alpha mu^2.  Arguments as poisson_pass.  Returns (H [pe,pe] = [1 | X]' diag(mu / (1 + alpha mu)) [1 | X]
     or None, g [pe], loglik [1] = the full log-likelihood, w [n] = mu / (1 + alpha mu) or None, mu [n] or None (with want_w),
     theta_terms [3] = (s, i, pearson) at theta = 1 / alpha or None (with want_theta))."""
-    lib = _lib.load()
-    _require_gpu(X, y, beta, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
-    n, p = X.shape
-    icpt = 1 if fit_intercept else 0
-    pe = p + icpt
-    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
-        raise ValueError("negbin_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
-    alpha = _alpha_positive("negbin_pass", alpha, "poisson_pass")
-    H, g, ll, w, mu, tt = out = _pass_out(pe, n, X.device, want_H, want_w, negbin=True, want_theta=want_theta)
-    ws = _workspace(lib.dlsa_negbin_workspace_bytes(n, p, icpt, 1), X.device)
-    check(lib.dlsa_negbin_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), alpha, n, p, icpt, _ptr(H), pe, _ptr(g), _ptr(ll),
-                                   _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_pass(GLM_FAMILIES["negbin"], X, y, beta, (alpha,), offset, fit_intercept, want_H, want_w, want_theta=want_theta)
 
 
 def negbin_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, alpha=None, tol=1e-13, max_iter=100):
@@ -881,43 +945,7 @@ def negbin_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_inte
     estimates the dispersion of every partition (0 for a partition that is not overdispersed: its block is the Poisson block);
     alpha > 0 fits beta at that fixed dispersion.  The result dict of poisson_fit_ex plus the per-partition lists `alpha`,
     `alpha_info` (the information about log alpha) and `pearson`; `loglik` is the full log-likelihood at (coef, alpha)."""
-    lib = _lib.load()
-    _require_gpu(X, y, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
-    n, p = X.shape
-    if y.numel() != n or (offset is not None and offset.numel() != n):
-        raise ValueError("negbin_fit_ex: y and offset must have n = %d elements" % n)
-    alpha = _alpha_fixed("negbin_fit_ex", alpha, "poisson_fit_ex")
-    K, step, max_rows, c_first, c_rows = _strided_partitions("negbin_fit_ex", part_first, part_rows, row_step, n)
-    icpt = 1 if fit_intercept else 0
-    out = _FitOut(K, p + icpt, X.device, dispersion=True)
-    ws = _workspace(lib.dlsa_negbin_workspace_bytes(max_rows, p, icpt, step), X.device)
-    rc = lib.dlsa_negbin_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, alpha, tol, max_iter,
-                                 *out.args, _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
-
-
-def _dispersion_positive(who, dispersion):
-    """The dispersion of a Gamma pass: a positive finite float."""
-    dispersion = float(dispersion)
-    if not 0.0 < dispersion < float("inf"):
-        raise ValueError("%s: dispersion must be positive and finite" % who)
-    return dispersion
-
-
-def _dispersion_fixed(who, dispersion):
-    """The dispersion argument of a Gamma fit as the C ABI takes it: 0.0 for None (estimate it), else a positive finite float."""
-    return 0.0 if dispersion is None else _dispersion_positive(who, dispersion)
-
-
-GAMMA_LISTS = ("dispersion", "pearson", "deviance")
-
-
-def _gamma_result(out, rc, rows, pe):
-    """A Gamma fit's result dict: the lists of GAMMA_LISTS plus `df` = rows - pe per partition (what the Pearson estimate divides by)."""
-    r = out.result(rc)
-    r["df"] = [int(m) - pe for m in rows]
-    return r
+    return _glm_fit(GLM_FAMILIES["negbin"], X, y, part_first, part_rows, row_step, offset, fit_intercept, (alpha,), tol, max_iter)
 
 
 def gamma_pass(X, y, beta, dispersion=1.0, offset=None, fit_intercept=False, want_H=True, want_w=False, want_stats=False):
@@ -925,20 +953,7 @@ def gamma_pass(X, y, beta, dispersion=1.0, offset=None, fit_intercept=False, wan
     r = y / mu.  Arguments as poisson_pass.  Returns (H [pe,pe] = [1 | X]' diag(r) [1 | X] / dispersion or None, g [pe] = [1 | X]'(r - 1)
     / dispersion, loglik [1] = the full log-likelihood at that dispersion, w [n] = r or None, stats [2] = (Pearson sum (r - 1)^2,
     deviance 2 sum (r - 1 - log r)) or None (with want_stats))."""
-    lib = _lib.load()
-    _require_gpu(X, y, beta, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
-    n, p = X.shape
-    icpt = 1 if fit_intercept else 0
-    pe = p + icpt
-    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
-        raise ValueError("gamma_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
-    dispersion = _dispersion_positive("gamma_pass", dispersion)
-    H, g, ll, w, st = out = _pass_out(pe, n, X.device, want_H, want_w, want_stats=want_stats)
-    ws = _workspace(lib.dlsa_gamma_workspace_bytes(n, p, icpt, 1), X.device)
-    check(lib.dlsa_gamma_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), dispersion, n, p, icpt, _ptr(H), pe, _ptr(g),
-                                  _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_pass(GLM_FAMILIES["gamma"], X, y, beta, (dispersion,), offset, fit_intercept, want_H, want_w, want_stats=want_stats)
 
 
 def gamma_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, dispersion=None, tol=1e-13, max_iter=100):
@@ -946,28 +961,7 @@ def gamma_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_inter
     dispersion=None estimates every partition's own dispersion (Pearson: P / (rows - pe)); dispersion > 0 gives every block that
     fixed dispersion.  The result dict of poisson_fit_ex -- Sig_inv is the information divided by the dispersion used, `loglik` the
     full log-likelihood at (coef, that dispersion) -- plus the per-partition lists `dispersion`, `pearson`, `deviance` and `df`."""
-    lib = _lib.load()
-    _require_gpu(X, y, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
-    n, p = X.shape
-    if y.numel() != n or (offset is not None and offset.numel() != n):
-        raise ValueError("gamma_fit_ex: y and offset must have n = %d elements" % n)
-    dispersion = _dispersion_fixed("gamma_fit_ex", dispersion)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("gamma_fit_ex", part_first, part_rows, row_step, n)
-    icpt = 1 if fit_intercept else 0
-    out = _FitOut(K, p + icpt, X.device, dispersion=GAMMA_LISTS)
-    ws = _workspace(lib.dlsa_gamma_workspace_bytes(max_rows, p, icpt, step), X.device)
-    rc = lib.dlsa_gamma_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, dispersion, tol, max_iter,
-                                *out.args, _ptr(ws), ws.numel(), _stream())
-    return _gamma_result(out, rc, c_rows, p + icpt)
-
-
-def tweedie_power(who, power):
-    """The variance power of a Tweedie entry: a float strictly between 1 and 2 (ValueError otherwise; NaN fails)."""
-    power = float(power)
-    if not 1.0 < power < 2.0:
-        raise ValueError("%s: power must lie strictly between 1 and 2, got %r" % (who, power))
-    return power
+    return _glm_fit(GLM_FAMILIES["gamma"], X, y, part_first, part_rows, row_step, offset, fit_intercept, (dispersion,), tol, max_iter)
 
 
 def tweedie_pass(X, y, beta, power, dispersion=1.0, offset=None, fit_intercept=False, want_H=True, want_w=False, want_stats=False):
@@ -977,21 +971,7 @@ def tweedie_pass(X, y, beta, power, dispersion=1.0, offset=None, fit_intercept=F
     loglik [1] = the QUASI-log-likelihood sum (y a / (1 - power) - b / (2 - power)) / dispersion -- the series factor of the density
     is not computed, so it compares values of beta at one (power, dispersion) only --, w [n] = (power - 1) y a + (2 - power) b or
     None, stats [2] = (Pearson sum (y - mu)^2 mu^-power, deviance) or None (with want_stats))."""
-    lib = _lib.load()
-    _require_gpu(X, y, beta, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(beta, "beta"); _f64(offset, "offset")
-    n, p = X.shape
-    icpt = 1 if fit_intercept else 0
-    pe = p + icpt
-    if n < 1 or y.numel() != n or beta.numel() != pe or (offset is not None and offset.numel() != n):
-        raise ValueError("tweedie_pass: need n >= 1 rows, y and offset with n = %d and beta with %d elements" % (n, pe))
-    power = tweedie_power("tweedie_pass", power)
-    dispersion = _dispersion_positive("tweedie_pass", dispersion)
-    H, g, ll, w, st = out = _pass_out(pe, n, X.device, want_H, want_w, want_stats=want_stats)
-    ws = _workspace(lib.dlsa_tweedie_workspace_bytes(n, p, icpt, 1), X.device)
-    check(lib.dlsa_tweedie_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), _ptr(beta), power, dispersion, n, p, icpt, _ptr(H), pe,
-                                    _ptr(g), _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_pass(GLM_FAMILIES["tweedie"], X, y, beta, (power, dispersion), offset, fit_intercept, want_H, want_w, want_stats=want_stats)
 
 
 def tweedie_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, power=1.5, dispersion=None, tol=1e-13,
@@ -999,21 +979,7 @@ def tweedie_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_int
     """Per-partition Tweedie fit with a log link at the variance power `power` (dlsa_tweedie_fit_f64; 1 < power < 2, given, not
     estimated): partitions, offset and intercept as poisson_fit_ex, dispersion as gamma_fit_ex.  The result dict of gamma_fit_ex
     (`dispersion`, `pearson`, `deviance`, `df`); `loglik` is the quasi-log-likelihood at (coef, the dispersion used)."""
-    lib = _lib.load()
-    _require_gpu(X, y, offset)
-    _f64(X, "X"); _f64(y, "y"); _f64(offset, "offset")
-    n, p = X.shape
-    if y.numel() != n or (offset is not None and offset.numel() != n):
-        raise ValueError("tweedie_fit_ex: y and offset must have n = %d elements" % n)
-    power = tweedie_power("tweedie_fit_ex", power)
-    dispersion = _dispersion_fixed("tweedie_fit_ex", dispersion)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("tweedie_fit_ex", part_first, part_rows, row_step, n)
-    icpt = 1 if fit_intercept else 0
-    out = _FitOut(K, p + icpt, X.device, dispersion=GAMMA_LISTS)
-    ws = _workspace(lib.dlsa_tweedie_workspace_bytes(max_rows, p, icpt, step), X.device)
-    rc = lib.dlsa_tweedie_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(offset), c_first, c_rows, step, K, p, icpt, power, dispersion, tol,
-                                  max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
-    return _gamma_result(out, rc, c_rows, p + icpt)
+    return _glm_fit(GLM_FAMILIES["tweedie"], X, y, part_first, part_rows, row_step, offset, fit_intercept, (power, dispersion), tol, max_iter)
 
 
 MULTINOMIAL_MAX_CLASSES = 8
@@ -1381,37 +1347,51 @@ def _oh_poisson_rows(plan, num, codes, y, offset, who):
     return n
 
 
+def _glm_onehot_pass(fam, plan, num, codes, y, beta, scalars, offset, want_H, want_w, **want):
+    """The body of onehot_<name>_pass: dlsa_onehot_<name>_pass_f64 on the raw representation (num, codes) of the plan's design."""
+    family, who = fam.name, "onehot_%s_pass" % fam.name
+    lib = _lib.load()
+    _require_gpu(beta)
+    _f64(beta, "beta")
+    n = _oh_poisson_rows(plan, num, codes, y, offset, who)
+    p = plan.p
+    if n < 1 or beta.numel() != p:
+        raise ValueError("%s: need n >= 1 rows and beta with %d elements" % (who, p))
+    scalars = fam.checked(who, scalars, fit=False)
+    out = _pass_out(p, n, y.device, want_H, want_w, fam, want)
+    ws = _workspace(getattr(lib, "dlsa_onehot_%s_workspace_bytes" % family)(plan._h, n, 1), y.device)
+    check(getattr(lib, "dlsa_onehot_%s_pass_f64" % family)(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), *scalars, n,
+                                                           _ptr(out[0]), p, *[_ptr(t) for t in out[1:]], _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def _glm_onehot_fit(fam, plan, num, codes, y, part_first, part_rows, row_step, offset, scalars, tol, max_iter):
+    """The body of onehot_<name>_fit_ex: dlsa_onehot_<name>_fit_f64 on strided partitions of the raw representation."""
+    family, who = fam.name, "onehot_%s_fit_ex" % fam.name
+    lib = _lib.load()
+    n = _oh_poisson_rows(plan, num, codes, y, offset, who)
+    scalars = fam.checked(who, scalars, fit=True)
+    K, step, max_rows, c_first, c_rows = _strided_partitions(who, part_first, part_rows, row_step, n)
+    out = _FitOut(K, plan.p, y.device, fam)
+    ws = _workspace(getattr(lib, "dlsa_onehot_%s_workspace_bytes" % family)(plan._h, max_rows, step), y.device)
+    rc = getattr(lib, "dlsa_onehot_%s_fit_f64" % family)(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K,
+                                                         *scalars, tol, max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc, c_rows if fam.df else None)
+
+
 def onehot_poisson_pass(plan, num, codes, y, beta, offset=None, want_H=True, want_w=False):
     """poisson_pass on the raw representation of a one-hot design (dlsa_onehot_poisson_pass_f64): num [n,q] fp64, codes [n,f]
     int32, counts y [n], optional offset [n]; beta has plan.p entries in the plan's column order (an intercept is the plan's
     constant column).  Returns (H [p,p] = X' diag(mu) X or None, g [p] = X'(y - mu), loglik [1], w [n] = mu or None) of the matrix
     dlsa_design_f64 would build -- which is never built."""
-    lib = _lib.load()
-    _require_gpu(beta)
-    _f64(beta, "beta")
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_poisson_pass")
-    p = plan.p
-    if n < 1 or beta.numel() != p:
-        raise ValueError("onehot_poisson_pass: need n >= 1 rows and beta with %d elements" % p)
-    H, g, ll, w = out = _pass_out(p, n, y.device, want_H, want_w)
-    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, n, 1), y.device)
-    check(lib.dlsa_onehot_poisson_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), n, _ptr(H), p, _ptr(g),
-                                           _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_onehot_pass(GLM_FAMILIES["poisson"], plan, num, codes, y, beta, (), offset, want_H, want_w)
 
 
 def onehot_poisson_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, tol=1e-13, max_iter=100):
     """poisson_fit_ex on the raw representation of a one-hot design (dlsa_onehot_poisson_fit_f64): partition k = rows
     part_first[k] + j * row_step, j < part_rows[k] -- strided views of num / codes, only the counts and offsets of a strided
     partition are gathered.  Same result dict as poisson_fit_ex, plan.p columns in the plan's order."""
-    lib = _lib.load()
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_poisson_fit_ex")
-    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_poisson_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, plan.p, y.device)
-    ws = _workspace(lib.dlsa_onehot_poisson_workspace_bytes(plan._h, max_rows, step), y.device)
-    rc = lib.dlsa_onehot_poisson_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, tol, max_iter,
-                                         *out.args, _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
+    return _glm_onehot_fit(GLM_FAMILIES["poisson"], plan, num, codes, y, part_first, part_rows, row_step, offset, (), tol, max_iter)
 
 
 def onehot_negbin_pass(plan, num, codes, y, beta, alpha, offset=None, want_H=True, want_w=False, want_theta=False):
@@ -1419,33 +1399,13 @@ def onehot_negbin_pass(plan, num, codes, y, beta, alpha, offset=None, want_H=Tru
     onehot_poisson_pass, alpha > 0 as negbin_pass.  Returns (H [p,p] = X' diag(mu / (1 + alpha mu)) X or None, g [p], loglik [1] = the
     full log-likelihood, w [n] or None, mu [n] or None (with want_w), theta_terms [3] = (s, i, pearson) or None (with want_theta))
     of the matrix dlsa_design_f64 would build -- which is never built."""
-    lib = _lib.load()
-    _require_gpu(beta)
-    _f64(beta, "beta")
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_negbin_pass")
-    p = plan.p
-    if n < 1 or beta.numel() != p:
-        raise ValueError("onehot_negbin_pass: need n >= 1 rows and beta with %d elements" % p)
-    alpha = _alpha_positive("onehot_negbin_pass", alpha, "onehot_poisson_pass")
-    H, g, ll, w, mu, tt = out = _pass_out(p, n, y.device, want_H, want_w, negbin=True, want_theta=want_theta)
-    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, n, 1), y.device)
-    check(lib.dlsa_onehot_negbin_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), alpha, n, _ptr(H), p,
-                                          _ptr(g), _ptr(ll), _ptr(w), _ptr(mu), _ptr(tt), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_onehot_pass(GLM_FAMILIES["negbin"], plan, num, codes, y, beta, (alpha,), offset, want_H, want_w, want_theta=want_theta)
 
 
 def onehot_negbin_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, alpha=None, tol=1e-13, max_iter=100):
     """negbin_fit_ex on the raw representation of a one-hot design (dlsa_onehot_negbin_fit_f64): partitions as
     onehot_poisson_fit_ex, alpha as negbin_fit_ex.  Same result dict as negbin_fit_ex, plan.p columns in the plan's order."""
-    lib = _lib.load()
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_negbin_fit_ex")
-    alpha = _alpha_fixed("onehot_negbin_fit_ex", alpha, "onehot_poisson_fit_ex")
-    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_negbin_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, plan.p, y.device, dispersion=True)
-    ws = _workspace(lib.dlsa_onehot_negbin_workspace_bytes(plan._h, max_rows, step), y.device)
-    rc = lib.dlsa_onehot_negbin_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, alpha, tol,
-                                        max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
+    return _glm_onehot_fit(GLM_FAMILIES["negbin"], plan, num, codes, y, part_first, part_rows, row_step, offset, (alpha,), tol, max_iter)
 
 
 def onehot_gamma_pass(plan, num, codes, y, beta, dispersion=1.0, offset=None, want_H=True, want_w=False, want_stats=False):
@@ -1453,33 +1413,13 @@ def onehot_gamma_pass(plan, num, codes, y, beta, dispersion=1.0, offset=None, wa
     dispersion > 0 as gamma_pass.  Returns (H [p,p] = X' diag(r) X / dispersion or None, g [p], loglik [1] = the full log-likelihood,
     w [n] = r or None, stats [2] = (Pearson, deviance) or None (with want_stats)) of the matrix dlsa_design_f64 would build -- which is
     never built."""
-    lib = _lib.load()
-    _require_gpu(beta)
-    _f64(beta, "beta")
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_gamma_pass")
-    p = plan.p
-    if n < 1 or beta.numel() != p:
-        raise ValueError("onehot_gamma_pass: need n >= 1 rows and beta with %d elements" % p)
-    dispersion = _dispersion_positive("onehot_gamma_pass", dispersion)
-    H, g, ll, w, st = out = _pass_out(p, n, y.device, want_H, want_w, want_stats=want_stats)
-    ws = _workspace(lib.dlsa_onehot_gamma_workspace_bytes(plan._h, n, 1), y.device)
-    check(lib.dlsa_onehot_gamma_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), dispersion, n, _ptr(H), p,
-                                         _ptr(g), _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_onehot_pass(GLM_FAMILIES["gamma"], plan, num, codes, y, beta, (dispersion,), offset, want_H, want_w, want_stats=want_stats)
 
 
 def onehot_gamma_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, dispersion=None, tol=1e-13, max_iter=100):
     """gamma_fit_ex on the raw representation of a one-hot design (dlsa_onehot_gamma_fit_f64): partitions as onehot_poisson_fit_ex,
     dispersion as gamma_fit_ex.  Same result dict as gamma_fit_ex, plan.p columns in the plan's order."""
-    lib = _lib.load()
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_gamma_fit_ex")
-    dispersion = _dispersion_fixed("onehot_gamma_fit_ex", dispersion)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_gamma_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, plan.p, y.device, dispersion=GAMMA_LISTS)
-    ws = _workspace(lib.dlsa_onehot_gamma_workspace_bytes(plan._h, max_rows, step), y.device)
-    rc = lib.dlsa_onehot_gamma_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, dispersion, tol,
-                                       max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
-    return _gamma_result(out, rc, c_rows, plan.p)
+    return _glm_onehot_fit(GLM_FAMILIES["gamma"], plan, num, codes, y, part_first, part_rows, row_step, offset, (dispersion,), tol, max_iter)
 
 
 def onehot_tweedie_pass(plan, num, codes, y, beta, power, dispersion=1.0, offset=None, want_H=True, want_w=False, want_stats=False):
@@ -1487,20 +1427,8 @@ def onehot_tweedie_pass(plan, num, codes, y, beta, power, dispersion=1.0, offset
     onehot_poisson_pass, power and dispersion as tweedie_pass.  Returns (H [p,p] or None, g [p], loglik [1] = the
     quasi-log-likelihood, w [n] or None, stats [2] = (Pearson, deviance) or None (with want_stats)) of the matrix dlsa_design_f64
     would build -- which is never built."""
-    lib = _lib.load()
-    _require_gpu(beta)
-    _f64(beta, "beta")
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_tweedie_pass")
-    p = plan.p
-    if n < 1 or beta.numel() != p:
-        raise ValueError("onehot_tweedie_pass: need n >= 1 rows and beta with %d elements" % p)
-    power = tweedie_power("onehot_tweedie_pass", power)
-    dispersion = _dispersion_positive("onehot_tweedie_pass", dispersion)
-    H, g, ll, w, st = out = _pass_out(p, n, y.device, want_H, want_w, want_stats=want_stats)
-    ws = _workspace(lib.dlsa_onehot_tweedie_workspace_bytes(plan._h, n, 1), y.device)
-    check(lib.dlsa_onehot_tweedie_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), _ptr(beta), power, dispersion, n,
-                                           _ptr(H), p, _ptr(g), _ptr(ll), _ptr(w), _ptr(st), _ptr(ws), ws.numel(), _stream()))
-    return out
+    return _glm_onehot_pass(GLM_FAMILIES["tweedie"], plan, num, codes, y, beta, (power, dispersion), offset, want_H, want_w,
+                            want_stats=want_stats)
 
 
 def onehot_tweedie_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, offset=None, power=1.5, dispersion=None, tol=1e-13,
@@ -1508,16 +1436,8 @@ def onehot_tweedie_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1
     """tweedie_fit_ex on the raw representation of a one-hot design (dlsa_onehot_tweedie_fit_f64): partitions as
     onehot_poisson_fit_ex, power and dispersion as tweedie_fit_ex.  Same result dict as tweedie_fit_ex, plan.p columns in the plan's
     order."""
-    lib = _lib.load()
-    n = _oh_poisson_rows(plan, num, codes, y, offset, "onehot_tweedie_fit_ex")
-    power = tweedie_power("onehot_tweedie_fit_ex", power)
-    dispersion = _dispersion_fixed("onehot_tweedie_fit_ex", dispersion)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_tweedie_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, plan.p, y.device, dispersion=GAMMA_LISTS)
-    ws = _workspace(lib.dlsa_onehot_tweedie_workspace_bytes(plan._h, max_rows, step), y.device)
-    rc = lib.dlsa_onehot_tweedie_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(offset), c_first, c_rows, step, K, power,
-                                         dispersion, tol, max_iter, *out.args, _ptr(ws), ws.numel(), _stream())
-    return _gamma_result(out, rc, c_rows, plan.p)
+    return _glm_onehot_fit(GLM_FAMILIES["tweedie"], plan, num, codes, y, part_first, part_rows, row_step, offset, (power, dispersion), tol,
+                           max_iter)
 
 
 def onehot_multinomial_pass(plan, num, codes, y, theta, classes, want_H=True, want_prob=False):

@@ -72,19 +72,34 @@ def _column_names(names, p, fit_intercept):
     return (["intercept"] if fit_intercept else []) + list(names)
 
 
-def _blocks(r, names, n):
-    """MappedBlocks of an engine fit's result dict (the NB2, Gamma and Tweedie fits' dispersion lists go to `extra`)."""
-    extra = {k: r[k] for k in ("alpha", "alpha_info", "pearson")} if "alpha" in r else None
-    if "dispersion" in r:
-        extra = {k: r[k] for k in ("dispersion", "pearson", "deviance", "df")}
+def _blocks(r, names, n, family=None):
+    """MappedBlocks of an engine fit's result dict; with a log-link `family` (an engine.GLM_FAMILIES record) its own per-partition
+    lists go to `extra`."""
+    extra = None if family is None else {k: r[k] for k in family.fit_lists + (("df",) if family.df else ())}
     return MappedBlocks(r["coef"], r["Sig_invMcoef"], r["Sig_inv"], names, r["status"], r["n_iter"], r["loglik"], sample_size=n,
                         extra=extra)
 
 
-def _fit_design(onehot_fit, dense_fit, num, codes, y, spec, partition_num, part_offsets, structured, names=None, **fit_args):
+def _require_dense_rows(who, X, note=""):
+    """What opens every fit_*_partitions: the rows are on the GPU and fp64."""
+    if not X.is_cuda:
+        raise RuntimeError("%s runs on the GPU only (no CPU fallback)" % who)
+    if X.dtype != torch.float64:
+        raise TypeError("%s: X must be float64%s, got %s" % (who, note, X.dtype))
+
+
+def _require_raw_rows(who, num, y):
+    """What opens every fit_*_design: the response is on the GPU, the numeric columns (if any) are fp64."""
+    if not torch.is_tensor(y) or not y.is_cuda:
+        raise RuntimeError("%s runs on the GPU only (no CPU fallback)" % who)
+    if num is not None and num.dtype != torch.float64:
+        raise TypeError("%s: num must be float64, got %s" % (who, num.dtype))
+
+
+def _fit_design(onehot_fit, dense_fit, num, codes, y, spec, partition_num, part_offsets, structured, names=None, family=None, **fit_args):
     """The body of the fit_*_design functions: the family's structured engine fit on the raw columns when the design qualifies,
     else its dense fit on the matrix the design kernel builds once; the same strided partitions either way.  `names`: the blocks'
-    column names when they are not spec.names (the multinomial family's J class blocks)."""
+    column names when they are not spec.names (the multinomial family's J class blocks); `family` as in _blocks."""
     n = y.numel()
     first, rows, step = _partitions(n, partition_num, part_offsets)
     plan = spec.onehot_plan() if structured else None
@@ -94,7 +109,7 @@ def _fit_design(onehot_fit, dense_fit, num, codes, y, spec, partition_num, part_
     else:
         X, _ = spec.build(num, codes)
         r = dense_fit(X, y, first, rows, row_step=step, **fit_args)
-    return _blocks(r, spec.names if names is None else names, n)
+    return _blocks(r, spec.names if names is None else names, n, family)
 
 
 def _to_device(sample_df, name):
@@ -201,11 +216,7 @@ def fit_logistic_partitions(X, y, partition_num=None, part_offsets=None, fit_int
     `options` (an engine.IrlsOptions) or its fields as keyword arguments -- chains=, seeded=, fused=, predict=, subsample_div=, ... --
     set the IRLS driver's policy for this call (default: chosen from the shapes; same results to the parity tolerance either way).
     Returns MappedBlocks."""
-    if not X.is_cuda:
-        raise RuntimeError("fit_logistic_partitions runs on the GPU only (no CPU fallback)")
-    if X.dtype != torch.float64:
-        raise TypeError("fit_logistic_partitions: X must be float64 (the logistic path is fp64 end to end; "
-                        "fit_linear_partitions takes fp32 rows), got %s" % X.dtype)
+    _require_dense_rows("fit_logistic_partitions", X, " (the logistic path is fp64 end to end; fit_linear_partitions takes fp32 rows)")
     y = y.to(torch.float64)                 # labels may arrive as integers / bools / fp32
     n, p = X.shape
     names = _column_names(names, p, fit_intercept)
@@ -227,11 +238,8 @@ def fit_logistic_design(num, codes, y, spec, partition_num=None, part_offsets=No
     the raw representation -- gather / histogram passes, the dense [n, p] matrix is never built (config 4: 76 B
     instead of 2080 B per row and pass); otherwise the matrix is built once by the design kernel and the dense
     kernels run.  Same MappedBlocks either way."""
-    if not y.is_cuda:
-        raise RuntimeError("fit_logistic_design runs on the GPU only (no CPU fallback)")
+    _require_raw_rows("fit_logistic_design", num, y)
     y = y.to(torch.float64)
-    if num is not None and num.dtype != torch.float64:
-        raise TypeError("fit_logistic_design: num must be float64, got %s" % num.dtype)
     # partition_id = i % K (models.py:33) as strided views: nothing is gathered (the structured fit takes (first, rows, step); the
     # dense one builds the matrix once and hands the same views to dlsa_irls_fit_ex_f64)
     with engine.irls_options(options, **option_fields):       # (the IRLS driver's policy for this call: see fit_logistic_partitions)
@@ -582,10 +590,7 @@ def fit_cox_partitions(X, time, event, partition_num=None, part_offsets=None, na
     Returns MappedBlocks with `loglik` = log partial likelihood of that method per partition."""
     engine.cox_ties(ties)          # (a wrong name fails before any GPU work)
     engine.cox_strata(strata, X.shape[0])
-    if not X.is_cuda:
-        raise RuntimeError("fit_cox_partitions runs on the GPU only (no CPU fallback)")
-    if X.dtype != torch.float64:
-        raise TypeError("fit_cox_partitions: X must be float64, got %s" % X.dtype)
+    _require_dense_rows("fit_cox_partitions", X)
     X = engine.row_major(X)
     n, p = X.shape
     time = time.to(torch.float64).contiguous()
@@ -640,10 +645,8 @@ def cox_model(sample_df, time_name, event_name, dummy_info=[], dummy_factors_bas
 # partition's MLE, Sig_inv = the Fisher information [1 | X]' diag(mu) [1 | X] there, Sig_invMcoef = Sig_inv coef, so
 # dlsa_mapred / dlsa apply unchanged.  The intercept is implicit, as in fit_logistic_partitions.
 # ---------------------------------------------------------------------------------------------
-def simulate_poisson(sample_size, p, partition_num, seed=20260101, base_rate=1.0, coef_value=0.5, exposure=False):
-    """Seeded count rows: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), beta* = coef_value on the first int(0.4p)
-    coefficients, y ~ Poisson(base_rate * exposure * exp(x beta*)) drawn with numpy; exposure (with exposure=True) ~ U(0.5, 2), else 1.
-    partition_id = i % partition_num.  Returns the frame partition_id, y, [exposure,] x0 .. x{p-1}."""
+def _simulate_glm(sample_size, p, partition_num, seed, base, coef_value, exposure, draw):
+    """The body of the log-link simulators: simulate_poisson's rows and frame with y = draw(rng, mu), mu = base * exposure * exp(x beta*)."""
     n, p = int(sample_size), int(p)
     X, _ = engine.synth(seed, 0, n, p, labels=False)
     X = X.cpu().numpy()
@@ -651,11 +654,19 @@ def simulate_poisson(sample_size, p, partition_num, seed=20260101, base_rate=1.0
     beta[:int(0.4 * p)] = float(coef_value)
     rng = np.random.default_rng(seed)
     e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
-    y = rng.poisson(float(base_rate) * e * np.exp(X @ beta)).astype(np.float64)
+    y = draw(rng, float(base) * e * np.exp(X @ beta))
     pid = (np.arange(n) % int(partition_num)).astype(np.float64)
     cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
     return pd.DataFrame(np.concatenate(cols, 1),
                         columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
+
+
+def simulate_poisson(sample_size, p, partition_num, seed=20260101, base_rate=1.0, coef_value=0.5, exposure=False):
+    """Seeded count rows: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), beta* = coef_value on the first int(0.4p)
+    coefficients, y ~ Poisson(base_rate * exposure * exp(x beta*)) drawn with numpy; exposure (with exposure=True) ~ U(0.5, 2), else 1.
+    partition_id = i % partition_num.  Returns the frame partition_id, y, [exposure,] x0 .. x{p-1}."""
+    return _simulate_glm(sample_size, p, partition_num, seed, base_rate, coef_value, exposure,
+                         lambda rng, mu: rng.poisson(mu).astype(np.float64))
 
 
 def _poisson_offset(offset, exposure, n, device):
@@ -674,15 +685,78 @@ def _poisson_offset(offset, exposure, n, device):
     return offset
 
 
-def _count_rows(who, y, n, offset, exposure, device):
-    """The counts and the offset of a count fit of n rows as the engine takes them: (y fp64 contiguous, offset fp64 or None), on
-    `device`; ValueError for a wrong length, a negative count or a bad offset / exposure."""
+def _count_response(y):
+    return "counts must be non-negative" if bool((y < 0).any()) else None
+
+
+def _positive_response(y):
+    return None if bool(((y > 0) & torch.isfinite(y)).all()) else "the response must be positive and finite"           # (NaN fails y > 0)
+
+
+def _tweedie_response(y):
+    if not bool(((y >= 0) & torch.isfinite(y)).all()):                # (NaN fails y >= 0)
+        return "the response must be non-negative and finite"
+    if y.numel() > 0 and not bool((y > 0).any()):
+        return "no response is positive: the fit runs off to mu = 0"
+    return None
+
+
+# What a log-link family refuses in its response: y -> the message, or None for a response it takes.
+_RESPONSE_REFUSED = {"poisson": _count_response, "negbin": _count_response, "gamma": _positive_response, "tweedie": _tweedie_response}
+
+
+def _alpha_not_zero(who, alpha, other):
+    if alpha is not None and float(alpha) == 0.0:
+        raise ValueError("%s: alpha = 0 is the Poisson model: use %s" % (who, other))
+
+
+def _dispersion_or_none(who, dispersion, other):
+    if dispersion is not None and not 0.0 < float(dispersion) < float("inf"):
+        raise ValueError("%s: dispersion must be positive and finite (None estimates it)" % who)
+
+
+# What fit_*_partitions / fit_*_design refuse in a family's scalar keyword before they look at the rows (the engine checks the rest):
+# keyword -> check(who, value, who with the family's name replaced by its `other`).
+_KEYWORD_REFUSED = {"alpha": _alpha_not_zero, "dispersion": _dispersion_or_none, "power": lambda who, power, other: engine.tweedie_power(who, power)}
+
+
+def _glm_rows(fam, who, y, n, offset, exposure, device, scalars):
+    """The response and the offset of a log-link fit of n rows as the engine takes them: (y fp64 contiguous, offset fp64 or None), on
+    `device`; ValueError for a bad scalar keyword (in the C ABI's order), a wrong length, a response the family refuses or a bad offset /
+    exposure, in this order."""
+    for s in fam.scalars:
+        _KEYWORD_REFUSED[s.name](who, scalars[s.name], who.replace(fam.name, fam.other) if fam.other else None)
     y = torch.as_tensor(y, device=device).to(torch.float64).contiguous()
     if y.numel() != n:
         raise ValueError("%s: y must have n = %d elements" % (who, n))
-    if bool((y < 0).any()):
-        raise ValueError("%s: counts must be non-negative" % who)
+    refused = _RESPONSE_REFUSED[fam.name](y)
+    if refused:
+        raise ValueError("%s: %s" % (who, refused))
     return y, _poisson_offset(offset, exposure, n, device)
+
+
+def _fit_glm_partitions(family, X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, names=None,
+                        tol=1e-13, max_iter=100, **scalars):
+    """The body of fit_<family>_partitions; `scalars`: the family's own keywords, as engine.<family>_fit_ex takes them."""
+    fam, who = engine.GLM_FAMILIES[family], "fit_%s_partitions" % family
+    _require_dense_rows(who, X)
+    n, p = X.shape
+    y, offset = _glm_rows(fam, who, y, n, offset, exposure, X.device, scalars)
+    names = _column_names(names, p, fit_intercept)
+    first, rows, step = _partitions(n, partition_num, part_offsets)
+    r = getattr(engine, family + "_fit_ex")(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept,
+                                            tol=tol, max_iter=max_iter, **scalars)
+    return _blocks(r, names, n, fam)
+
+
+def _fit_glm_design(family, num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, structured=True,
+                    tol=1e-13, max_iter=100, **scalars):
+    """The body of fit_<family>_design, on top of _fit_design; `scalars` as in _fit_glm_partitions."""
+    fam, who = engine.GLM_FAMILIES[family], "fit_%s_design" % family
+    _require_raw_rows(who, num, y)
+    y, offset = _glm_rows(fam, who, y, y.numel(), offset, exposure, y.device, scalars)
+    return _fit_design(getattr(engine, "onehot_%s_fit_ex" % family), getattr(engine, family + "_fit_ex"), num, codes, y, spec, partition_num,
+                       part_offsets, structured, family=fam, offset=offset, tol=tol, max_iter=max_iter, **scalars)
 
 
 def fit_poisson_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, names=None,
@@ -692,17 +766,7 @@ def fit_poisson_partitions(X, y, partition_num=None, part_offsets=None, fit_inte
     strided views: nothing is copied but the partition's counts and offsets, 8 bytes per row each).  With fit_intercept the ones column
     is implicit (results have p + 1 columns, `intercept` first).  `offset` [n] enters eta as is; `exposure` [n] is turned into
     offset = log(exposure).  Returns MappedBlocks with `loglik` = the full log-likelihood per partition."""
-    if not X.is_cuda:
-        raise RuntimeError("fit_poisson_partitions runs on the GPU only (no CPU fallback)")
-    if X.dtype != torch.float64:
-        raise TypeError("fit_poisson_partitions: X must be float64, got %s" % X.dtype)
-    n, p = X.shape
-    y, offset = _count_rows("fit_poisson_partitions", y, n, offset, exposure, X.device)
-    names = _column_names(names, p, fit_intercept)
-    first, rows, step = _partitions(n, partition_num, part_offsets)
-    r = engine.poisson_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept,
-                              tol=tol, max_iter=max_iter)
-    return _blocks(r, names, n)
+    return _fit_glm_partitions("poisson", X, y, partition_num, part_offsets, fit_intercept, offset, exposure, names, tol, max_iter)
 
 
 def fit_poisson_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, structured=True,
@@ -713,13 +777,7 @@ def fit_poisson_design(num, codes, y, spec, partition_num=None, part_offsets=Non
     representation -- gather / histogram passes, the dense [n, p] matrix is never built; otherwise the matrix is built once by the
     design kernel and the dense Poisson fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and
     `exposure` as fit_poisson_partitions.  Same MappedBlocks either way (names = spec.names)."""
-    if not torch.is_tensor(y) or not y.is_cuda:
-        raise RuntimeError("fit_poisson_design runs on the GPU only (no CPU fallback)")
-    if num is not None and num.dtype != torch.float64:
-        raise TypeError("fit_poisson_design: num must be float64, got %s" % num.dtype)
-    y, offset = _count_rows("fit_poisson_design", y, y.numel(), offset, exposure, y.device)
-    return _fit_design(engine.onehot_poisson_fit_ex, engine.poisson_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
-                       offset=offset, tol=tol, max_iter=max_iter)
+    return _fit_glm_design("poisson", num, codes, y, spec, partition_num, part_offsets, offset, exposure, structured, tol, max_iter)
 
 
 def _count_raw_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info):
@@ -743,10 +801,10 @@ def _count_frame(sample_df, Y_name, fit_intercept, offset_name, exposure_name, d
             _to_device(sample_df, exposure_name))
 
 
-def _count_model(who, fit_design, fit_partitions, structured, chunk, **fit_args):
-    """The body of poisson_model / negbin_model: `chunk` is (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
-    dummy_factors_baseline, data_info), fit_args the family's own keywords.  Returns (the block's frame, the MappedBlocks or None for
-    the all-zero block of a skipped chunk)."""
+def _count_model(family, structured, *chunk, **scalars):
+    """The body of the log-link families' <family>_model: `chunk` is (sample_df, Y_name, fit_intercept, offset_name, exposure_name,
+    dummy_info, dummy_factors_baseline, data_info), `scalars` the family's own keywords.  Returns (the block's frame, the MappedBlocks or
+    None for the all-zero block of a skipped chunk)."""
     sample_df, fit_intercept, dummy_info = chunk[0], chunk[2], chunk[5]
     mb = None
     if structured and len(dummy_info) > 0:
@@ -757,22 +815,32 @@ def _count_model(who, fit_design, fit_partitions, structured, chunk, **fit_args)
             if missing or unknown:
                 _warn_missing_levels(missing, len(sample_df), names, fit_intercept, skip=True)
                 return _zero_block(names), None
-            mb = fit_design(spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, spec, offset=od, exposure=ed, **fit_args)
+            mb = _fit_glm_design(family, spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda(), yd, spec, offset=od, exposure=ed,
+                                 **scalars)
     if mb is None:
         Xd, names, yd, od, ed = _count_frame(*chunk)
         if Xd is None:
             return _zero_block(names), None
-        mb = fit_partitions(Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed, names=names[1:] if fit_intercept else names,
-                            **fit_args)
-    return _first_block_frame(mb, who), mb
+        mb = _fit_glm_partitions(family, Xd, yd, fit_intercept=fit_intercept, offset=od, exposure=ed,
+                                 names=names[1:] if fit_intercept else names, **scalars)
+    return _first_block_frame(mb, family + "_model"), mb
 
 
-def _count_model_eval(dense_pass, onehot_pass, par, structured, chunk):
-    """The body of poisson_model_eval / negbin_model_eval, `chunk` as in _count_model: the log-likelihood of every column of `par` by
-    one pass without the information per column -- dense_pass(X, y, beta, ...) or, on the raw representation,
-    onehot_pass(plan, num, codes, y, beta, ...)."""
-    sample_df, fit_intercept, dummy_info = chunk[0], chunk[2], chunk[5]
+def _loglik_frame(par, run):
+    """One row, a column per estimator column of `par`: the log-likelihood run(beta)[2] of one pass at that column."""
     pard = np.asarray(par, dtype=np.float64)
+    out = {}
+    for i in range(pard.shape[1]):
+        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
+        out[par.columns[i]] = [float(run(b)[2].item())]
+    return pd.DataFrame(out)
+
+
+def _count_model_eval(family, par, structured, *chunk, **scalars):
+    """The body of the log-link families' <family>_model_eval, `chunk` and `scalars` as in _count_model: the log-likelihood of every
+    column of `par` by one pass without the information per column -- engine.<family>_pass or, on the raw representation,
+    engine.onehot_<family>_pass."""
+    sample_df, fit_intercept, dummy_info = chunk[0], chunk[2], chunk[5]
     run = None
     if structured and len(dummy_info) > 0:
         spec, plan, codes, unknown, yd, od, ed = _count_raw_frame(*chunk)
@@ -784,19 +852,15 @@ def _count_model_eval(dense_pass, onehot_pass, par, structured, chunk):
             num, cd = spec.numeric_to_device(sample_df), torch.from_numpy(codes).cuda()
 
             def run(b):
-                return onehot_pass(plan, num, cd, yd, b, offset=od, want_H=False)
+                return getattr(engine, "onehot_%s_pass" % family)(plan, num, cd, yd, b, offset=od, want_H=False, **scalars)
     if run is None:
         Xd, _, yd, od, ed = _count_frame(*chunk, for_eval=True)
         od = _poisson_offset(od, ed, yd.numel(), yd.device)
         X = engine.row_major(Xd)
 
         def run(b):
-            return dense_pass(X, yd, b, offset=od, fit_intercept=fit_intercept, want_H=False)
-    out = {}
-    for i in range(pard.shape[1]):
-        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
-        out[par.columns[i]] = [float(run(b)[2].item())]
-    return pd.DataFrame(out)
+            return getattr(engine, family + "_pass")(X, yd, b, offset=od, fit_intercept=fit_intercept, want_H=False, **scalars)
+    return _loglik_frame(par, run)
 
 
 def poisson_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
@@ -806,8 +870,8 @@ def poisson_model(sample_df, Y_name, fit_intercept=False, offset_name=None, expo
     [intercept,] <features>`; a chunk that lacks an expected dummy level returns the all-zero block with a warning.
     structured=True with a dummy_info and a qualifying design fits on the raw numerics + level codes (fit_poisson_design; the
     dense one-hot matrix is never built, the missing-level check runs on the codes); the default is the dense path."""
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    return _count_model("poisson_model", fit_poisson_design, fit_poisson_partitions, structured, chunk)[0]
+    return _count_model("poisson", structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                        dummy_factors_baseline, data_info)[0]
 
 
 def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
@@ -815,8 +879,8 @@ def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=
     """Log-likelihood (sum y eta - mu - lgamma(y + 1)) of every estimator column of `par` on one partition, shaped like
     logistic_model_eval's output: one row, a column per estimator.  structured=True with a dummy_info and a qualifying design
     evaluates on the raw numerics + level codes (one structured pass per estimator column); the default is the dense path."""
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    return _count_model_eval(engine.poisson_pass, engine.onehot_poisson_pass, par, structured, chunk)
+    return _count_model_eval("poisson", par, structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                             dummy_factors_baseline, data_info)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -828,21 +892,11 @@ def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=
 def simulate_negbin(sample_size, p, partition_num, alpha, seed=20260101, base_rate=1.0, coef_value=0.5, exposure=False):
     """simulate_poisson's rows and frame with overdispersed counts: y ~ Poisson(mu * G), G ~ Gamma(shape 1 / alpha, scale alpha)
     (mean 1), so y ~ NB2(mu, alpha) with mu = base_rate * exposure * exp(x beta*)."""
-    n, p, alpha = int(sample_size), int(p), float(alpha)
+    alpha = float(alpha)
     if not alpha > 0:
         raise ValueError("simulate_negbin: alpha must be positive (alpha = 0 is simulate_poisson)")
-    X, _ = engine.synth(seed, 0, n, p, labels=False)
-    X = X.cpu().numpy()
-    beta = np.zeros(p)
-    beta[:int(0.4 * p)] = float(coef_value)
-    rng = np.random.default_rng(seed)
-    e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
-    mu = float(base_rate) * e * np.exp(X @ beta)
-    y = rng.poisson(mu * rng.gamma(1.0 / alpha, alpha, n)).astype(np.float64)
-    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
-    cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
-    return pd.DataFrame(np.concatenate(cols, 1),
-                        columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
+    return _simulate_glm(sample_size, p, partition_num, seed, base_rate, coef_value, exposure,
+                         lambda rng, mu: rng.poisson(mu * rng.gamma(1.0 / alpha, alpha, len(mu))).astype(np.float64))
 
 
 def fit_negbin_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, alpha=None,
@@ -852,19 +906,7 @@ def fit_negbin_partitions(X, y, partition_num=None, part_offsets=None, fit_inter
     alpha > 0 fits every partition at that common dispersion (e.g. combine_dispersion of a first map step); alpha = 0 is refused:
     that is fit_poisson_partitions.  Returns MappedBlocks with `loglik` = the full log-likelihood per partition and
     `extra` = {"alpha", "alpha_info" (the information about log alpha), "pearson"} per partition."""
-    if not X.is_cuda:
-        raise RuntimeError("fit_negbin_partitions runs on the GPU only (no CPU fallback)")
-    if X.dtype != torch.float64:
-        raise TypeError("fit_negbin_partitions: X must be float64, got %s" % X.dtype)
-    if alpha is not None and float(alpha) == 0.0:
-        raise ValueError("fit_negbin_partitions: alpha = 0 is the Poisson model: use fit_poisson_partitions")
-    n, p = X.shape
-    y, offset = _count_rows("fit_negbin_partitions", y, n, offset, exposure, X.device)
-    names = _column_names(names, p, fit_intercept)
-    first, rows, step = _partitions(n, partition_num, part_offsets)
-    r = engine.negbin_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept, alpha=alpha,
-                             tol=tol, max_iter=max_iter)
-    return _blocks(r, names, n)
+    return _fit_glm_partitions("negbin", X, y, partition_num, part_offsets, fit_intercept, offset, exposure, names, tol, max_iter, alpha=alpha)
 
 
 def fit_negbin_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, alpha=None,
@@ -875,15 +917,7 @@ def fit_negbin_design(num, codes, y, spec, partition_num=None, part_offsets=None
     design kernel and the dense NB2 fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and
     `exposure` as fit_poisson_partitions, alpha as fit_negbin_partitions (alpha = 0 is refused: that is fit_poisson_design).  Same
     MappedBlocks either way (names = spec.names, `extra` = {"alpha", "alpha_info", "pearson"} per partition)."""
-    if not torch.is_tensor(y) or not y.is_cuda:
-        raise RuntimeError("fit_negbin_design runs on the GPU only (no CPU fallback)")
-    if num is not None and num.dtype != torch.float64:
-        raise TypeError("fit_negbin_design: num must be float64, got %s" % num.dtype)
-    if alpha is not None and float(alpha) == 0.0:
-        raise ValueError("fit_negbin_design: alpha = 0 is the Poisson model: use fit_poisson_design")
-    y, offset = _count_rows("fit_negbin_design", y, y.numel(), offset, exposure, y.device)
-    return _fit_design(engine.onehot_negbin_fit_ex, engine.negbin_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
-                       offset=offset, alpha=alpha, tol=tol, max_iter=max_iter)
+    return _fit_glm_design("negbin", num, codes, y, spec, partition_num, part_offsets, offset, exposure, structured, tol, max_iter, alpha=alpha)
 
 
 def combine_dispersion(mb):
@@ -906,8 +940,8 @@ def negbin_model(sample_df, Y_name, fit_intercept=False, offset_name=None, expos
     returns the all-zero block with a warning.  structured=True with a dummy_info and a qualifying design fits on the raw numerics +
     level codes (fit_negbin_design; the dense one-hot matrix is never built, the missing-level check runs on the codes); the
     default is the dense path."""
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    out, mb = _count_model("negbin_model", fit_negbin_design, fit_negbin_partitions, structured, chunk, alpha=alpha)
+    out, mb = _count_model("negbin", structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                           dummy_factors_baseline, data_info, alpha=alpha)
     out.attrs["alpha"] = mb.extra["alpha"][0] if mb is not None else 0.0         # (a skipped chunk's all-zero block: 0)
     return out
 
@@ -918,13 +952,8 @@ def negbin_model_eval(sample_df, Y_name, par, alpha, fit_intercept=False, offset
     poisson_model_eval's output: one row, a column per estimator (one pass without the information per column).  structured=True
     with a dummy_info and a qualifying design evaluates on the raw numerics + level codes (one structured pass per estimator
     column); the default is the dense path."""
-    def dense_pass(X, y, b, **kw):
-        return engine.negbin_pass(X, y, b, alpha, **kw)
-
-    def onehot_pass(plan, num, codes, y, b, **kw):
-        return engine.onehot_negbin_pass(plan, num, codes, y, b, alpha, **kw)
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)
+    return _count_model_eval("negbin", par, structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                             dummy_factors_baseline, data_info, alpha=alpha)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -937,34 +966,10 @@ def negbin_model_eval(sample_df, Y_name, par, alpha, fit_intercept=False, offset
 def simulate_gamma(sample_size, p, partition_num, shape, seed=20260101, base_mean=1.0, coef_value=0.5, exposure=False):
     """simulate_poisson's rows and frame with a positive continuous response: y ~ Gamma(shape, scale mu / shape) (mean mu, dispersion
     1 / shape) with mu = base_mean * exposure * exp(x beta*)."""
-    n, p, shape = int(sample_size), int(p), float(shape)
+    shape = float(shape)
     if not shape > 0:
         raise ValueError("simulate_gamma: shape must be positive")
-    X, _ = engine.synth(seed, 0, n, p, labels=False)
-    X = X.cpu().numpy()
-    beta = np.zeros(p)
-    beta[:int(0.4 * p)] = float(coef_value)
-    rng = np.random.default_rng(seed)
-    e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
-    mu = float(base_mean) * e * np.exp(X @ beta)
-    y = rng.gamma(shape, mu / shape)
-    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
-    cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
-    return pd.DataFrame(np.concatenate(cols, 1),
-                        columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
-
-
-def _gamma_rows(who, y, n, offset, exposure, dispersion, device):
-    """The responses and the offset of a Gamma fit of n rows as the engine takes them: (y fp64 contiguous, offset fp64 or None), on
-    `device`; ValueError for a wrong length, a response that is not positive, a bad offset / exposure or a bad `dispersion=`."""
-    if dispersion is not None and not 0.0 < float(dispersion) < float("inf"):
-        raise ValueError("%s: dispersion must be positive and finite (None estimates it)" % who)
-    y = torch.as_tensor(y, device=device).to(torch.float64).contiguous()
-    if y.numel() != n:
-        raise ValueError("%s: y must have n = %d elements" % (who, n))
-    if not bool(((y > 0) & torch.isfinite(y)).all()):                 # (NaN fails y > 0)
-        raise ValueError("%s: the response must be positive and finite" % who)
-    return y, _poisson_offset(offset, exposure, n, device)
+    return _simulate_glm(sample_size, p, partition_num, seed, base_mean, coef_value, exposure, lambda rng, mu: rng.gamma(shape, mu / shape))
 
 
 def fit_gamma_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, dispersion=None,
@@ -973,17 +978,8 @@ def fit_gamma_partitions(X, y, partition_num=None, part_offsets=None, fit_interc
     dispersion=None estimates every partition's own dispersion (Pearson) for its block; dispersion > 0 gives every block that common
     dispersion (e.g. combine_gamma_dispersion of a first map step).  Returns MappedBlocks with `loglik` = the full log-likelihood per
     partition at the dispersion used and `extra` = {"dispersion", "pearson", "deviance", "df"} per partition."""
-    if not X.is_cuda:
-        raise RuntimeError("fit_gamma_partitions runs on the GPU only (no CPU fallback)")
-    if X.dtype != torch.float64:
-        raise TypeError("fit_gamma_partitions: X must be float64, got %s" % X.dtype)
-    n, p = X.shape
-    y, offset = _gamma_rows("fit_gamma_partitions", y, n, offset, exposure, dispersion, X.device)
-    names = _column_names(names, p, fit_intercept)
-    first, rows, step = _partitions(n, partition_num, part_offsets)
-    r = engine.gamma_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept,
-                            dispersion=dispersion, tol=tol, max_iter=max_iter)
-    return _blocks(r, names, n)
+    return _fit_glm_partitions("gamma", X, y, partition_num, part_offsets, fit_intercept, offset, exposure, names, tol, max_iter,
+                               dispersion=dispersion)
 
 
 def fit_gamma_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, dispersion=None,
@@ -993,13 +989,8 @@ def fit_gamma_design(num, codes, y, spec, partition_num=None, part_offsets=None,
     runs on the raw representation -- the dense [n, p] matrix is never built; otherwise the matrix is built once by the design kernel
     and the dense Gamma fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and `exposure` as
     fit_poisson_partitions, dispersion as fit_gamma_partitions.  Same MappedBlocks either way (names = spec.names)."""
-    if not torch.is_tensor(y) or not y.is_cuda:
-        raise RuntimeError("fit_gamma_design runs on the GPU only (no CPU fallback)")
-    if num is not None and num.dtype != torch.float64:
-        raise TypeError("fit_gamma_design: num must be float64, got %s" % num.dtype)
-    y, offset = _gamma_rows("fit_gamma_design", y, y.numel(), offset, exposure, dispersion, y.device)
-    return _fit_design(engine.onehot_gamma_fit_ex, engine.gamma_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
-                       offset=offset, dispersion=dispersion, tol=tol, max_iter=max_iter)
+    return _fit_glm_design("gamma", num, codes, y, spec, partition_num, part_offsets, offset, exposure, structured, tol, max_iter,
+                           dispersion=dispersion)
 
 
 def combine_gamma_dispersion(mb):
@@ -1026,8 +1017,8 @@ def gamma_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposu
     `par_id, coef, Sig_invMcoef, [intercept,] <features>` with the dispersion used in `out.attrs["dispersion"]`; a chunk that lacks an
     expected dummy level returns the all-zero block with a warning.  structured=True with a dummy_info and a qualifying design fits
     on the raw numerics + level codes (fit_gamma_design); the default is the dense path."""
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    out, mb = _count_model("gamma_model", fit_gamma_design, fit_gamma_partitions, structured, chunk, dispersion=dispersion)
+    out, mb = _count_model("gamma", structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                           dummy_factors_baseline, data_info, dispersion=dispersion)
     out.attrs["dispersion"] = mb.extra["dispersion"][0] if mb is not None else 0.0      # (a skipped chunk's all-zero block: 0)
     return out
 
@@ -1037,13 +1028,8 @@ def gamma_model_eval(sample_df, Y_name, par, dispersion, fit_intercept=False, of
     """Gamma log-likelihood at dispersion > 0 of every estimator column of `par` on one partition, shaped like poisson_model_eval's
     output: one row, a column per estimator (one pass without the information per column).  structured=True with a dummy_info and a
     qualifying design evaluates on the raw numerics + level codes; the default is the dense path."""
-    def dense_pass(X, y, b, **kw):
-        return engine.gamma_pass(X, y, b, dispersion, **kw)
-
-    def onehot_pass(plan, num, codes, y, b, **kw):
-        return engine.onehot_gamma_pass(plan, num, codes, y, b, dispersion, **kw)
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)
+    return _count_model_eval("gamma", par, structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                             dummy_factors_baseline, data_info, dispersion=dispersion)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1059,22 +1045,10 @@ def simulate_tweedie(sample_size, p, partition_num, power, dispersion, seed=2026
     """simulate_poisson's rows and frame with a compound Poisson-Gamma response of mean mu = base_mean * exposure * exp(x beta*) and
     variance dispersion * mu^power: N ~ Poisson(mu^(2 - power) / (dispersion (2 - power))), y = the sum of N Gamma draws = Gamma(shape
     N (2 - power) / (power - 1), scale dispersion (power - 1) mu^(power - 1)), y = 0 at N = 0."""
-    n, p = int(sample_size), int(p)
     xi, phi = engine.tweedie_power("simulate_tweedie", power), float(dispersion)
     if not 0.0 < phi < float("inf"):
         raise ValueError("simulate_tweedie: dispersion must be positive and finite")
-    X, _ = engine.synth(seed, 0, n, p, labels=False)
-    X = X.cpu().numpy()
-    beta = np.zeros(p)
-    beta[:int(0.4 * p)] = float(coef_value)
-    rng = np.random.default_rng(seed)
-    e = rng.uniform(0.5, 2.0, n) if exposure else np.ones(n)
-    mu = float(base_mean) * e * np.exp(X @ beta)
-    y = _tweedie_draw(rng, mu, xi, phi)
-    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
-    cols = [pid[:, None], y[:, None]] + ([e[:, None]] if exposure else []) + [X]
-    return pd.DataFrame(np.concatenate(cols, 1),
-                        columns=["partition_id", "y"] + (["exposure"] if exposure else []) + ["x" + str(i) for i in range(p)])
+    return _simulate_glm(sample_size, p, partition_num, seed, base_mean, coef_value, exposure, lambda rng, mu: _tweedie_draw(rng, mu, xi, phi))
 
 
 def _tweedie_draw(rng, mu, power, dispersion):
@@ -1084,23 +1058,6 @@ def _tweedie_draw(rng, mu, power, dispersion):
     return np.where(N > 0, draws, 0.0)
 
 
-def _tweedie_rows(who, y, n, offset, exposure, power, dispersion, device):
-    """The responses and the offset of a Tweedie fit of n rows as the engine takes them: (y fp64 contiguous, offset fp64 or None), on
-    `device`; ValueError for a wrong length, a response that is negative or not finite, no positive response at all, a bad offset /
-    exposure, a `power=` outside (1, 2) or a bad `dispersion=`."""
-    engine.tweedie_power(who, power)
-    if dispersion is not None and not 0.0 < float(dispersion) < float("inf"):
-        raise ValueError("%s: dispersion must be positive and finite (None estimates it)" % who)
-    y = torch.as_tensor(y, device=device).to(torch.float64).contiguous()
-    if y.numel() != n:
-        raise ValueError("%s: y must have n = %d elements" % (who, n))
-    if not bool(((y >= 0) & torch.isfinite(y)).all()):                # (NaN fails y >= 0)
-        raise ValueError("%s: the response must be non-negative and finite" % who)
-    if n > 0 and not bool((y > 0).any()):
-        raise ValueError("%s: no response is positive: the fit runs off to mu = 0" % who)
-    return y, _poisson_offset(offset, exposure, n, device)
-
-
 def fit_tweedie_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, power=1.5,
                            dispersion=None, names=None, tol=1e-13, max_iter=100):
     """Tweedie (log link, Var y = dispersion * mu^power, 1 < power < 2 given) map step for the partitions of one device-resident
@@ -1108,17 +1065,8 @@ def fit_tweedie_partitions(X, y, partition_num=None, part_offsets=None, fit_inte
     fit_gamma_partitions (None: every partition's own Pearson estimate; > 0: that common one, e.g. combine_tweedie_dispersion of a
     first map step).  Returns MappedBlocks with `loglik` = the quasi-log-likelihood per partition at the dispersion used (the density's
     series factor is not computed) and `extra` = {"dispersion", "pearson", "deviance", "df"} per partition."""
-    if not X.is_cuda:
-        raise RuntimeError("fit_tweedie_partitions runs on the GPU only (no CPU fallback)")
-    if X.dtype != torch.float64:
-        raise TypeError("fit_tweedie_partitions: X must be float64, got %s" % X.dtype)
-    n, p = X.shape
-    y, offset = _tweedie_rows("fit_tweedie_partitions", y, n, offset, exposure, power, dispersion, X.device)
-    names = _column_names(names, p, fit_intercept)
-    first, rows, step = _partitions(n, partition_num, part_offsets)
-    r = engine.tweedie_fit_ex(engine.row_major(X), y, first, rows, row_step=step, offset=offset, fit_intercept=fit_intercept, power=power,
-                              dispersion=dispersion, tol=tol, max_iter=max_iter)
-    return _blocks(r, names, n)
+    return _fit_glm_partitions("tweedie", X, y, partition_num, part_offsets, fit_intercept, offset, exposure, names, tol, max_iter,
+                               power=power, dispersion=dispersion)
 
 
 def fit_tweedie_design(num, codes, y, spec, partition_num=None, part_offsets=None, offset=None, exposure=None, power=1.5,
@@ -1128,13 +1076,8 @@ def fit_tweedie_design(num, codes, y, spec, partition_num=None, part_offsets=Non
     runs on the raw representation -- the dense [n, p] matrix is never built; otherwise the matrix is built once by the design kernel
     and the dense Tweedie fit runs on it.  An intercept is the spec's own constant column.  Partitions, `offset` and `exposure` as
     fit_poisson_partitions, power and dispersion as fit_tweedie_partitions.  Same MappedBlocks either way (names = spec.names)."""
-    if not torch.is_tensor(y) or not y.is_cuda:
-        raise RuntimeError("fit_tweedie_design runs on the GPU only (no CPU fallback)")
-    if num is not None and num.dtype != torch.float64:
-        raise TypeError("fit_tweedie_design: num must be float64, got %s" % num.dtype)
-    y, offset = _tweedie_rows("fit_tweedie_design", y, y.numel(), offset, exposure, power, dispersion, y.device)
-    return _fit_design(engine.onehot_tweedie_fit_ex, engine.tweedie_fit_ex, num, codes, y, spec, partition_num, part_offsets, structured,
-                       offset=offset, power=power, dispersion=dispersion, tol=tol, max_iter=max_iter)
+    return _fit_glm_design("tweedie", num, codes, y, spec, partition_num, part_offsets, offset, exposure, structured, tol, max_iter,
+                           power=power, dispersion=dispersion)
 
 
 def combine_tweedie_dispersion(mb):
@@ -1151,9 +1094,8 @@ def tweedie_model(sample_df, Y_name, fit_intercept=False, offset_name=None, expo
     and the power in `out.attrs["power"]`; a chunk that lacks an expected dummy level returns the all-zero block with a warning.
     structured=True with a dummy_info and a qualifying design fits on the raw numerics + level codes (fit_tweedie_design); the
     default is the dense path."""
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    out, mb = _count_model("tweedie_model", fit_tweedie_design, fit_tweedie_partitions, structured, chunk, power=power,
-                           dispersion=dispersion)
+    out, mb = _count_model("tweedie", structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                           dummy_factors_baseline, data_info, power=power, dispersion=dispersion)
     out.attrs["dispersion"] = mb.extra["dispersion"][0] if mb is not None else 0.0      # (a skipped chunk's all-zero block: 0)
     out.attrs["power"] = float(power)
     return out
@@ -1165,13 +1107,8 @@ def tweedie_model_eval(sample_df, Y_name, par, power, dispersion, fit_intercept=
     poisson_model_eval's output: one row, a column per estimator (one pass without the information per column).  The values compare
     estimators at this (power, dispersion) only.  structured=True with a dummy_info and a qualifying design evaluates on the raw
     numerics + level codes; the default is the dense path."""
-    def dense_pass(X, y, b, **kw):
-        return engine.tweedie_pass(X, y, b, power, dispersion, **kw)
-
-    def onehot_pass(plan, num, codes, y, b, **kw):
-        return engine.onehot_tweedie_pass(plan, num, codes, y, b, power, dispersion, **kw)
-    chunk = (sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info, dummy_factors_baseline, data_info)
-    return _count_model_eval(dense_pass, onehot_pass, par, structured, chunk)
+    return _count_model_eval("tweedie", par, structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                             dummy_factors_baseline, data_info, power=power, dispersion=dispersion)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1224,10 +1161,7 @@ def fit_multinomial_partitions(X, y, classes, partition_num=None, part_offsets=N
     0 .. classes - 1 on the GPU (class 0 is the reference).  Partitions and the implicit intercept as fit_poisson_partitions.  Every
     partition with rows must hold every class.  Returns MappedBlocks over the (classes - 1) * pe coefficients "<name>:<j>",
     "intercept:<j>" first in each class block, with `loglik` = the log-likelihood per partition."""
-    if not X.is_cuda:
-        raise RuntimeError("fit_multinomial_partitions runs on the GPU only (no CPU fallback)")
-    if X.dtype != torch.float64:
-        raise TypeError("fit_multinomial_partitions: X must be float64, got %s" % X.dtype)
+    _require_dense_rows("fit_multinomial_partitions", X)
     n, p = X.shape
     y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
     if y.numel() != n:
@@ -1249,10 +1183,7 @@ def fit_multinomial_design(num, codes, y, spec, classes, partition_num=None, par
     without an implicit intercept.  An intercept is the spec's own constant column, one column of every class block.  Partitions as
     fit_poisson_partitions; every partition with rows must hold every class.  Same MappedBlocks either way over the
     (classes - 1) * p coefficients multinomial_column_names(spec.names, classes)."""
-    if not torch.is_tensor(y) or not y.is_cuda:
-        raise RuntimeError("fit_multinomial_design runs on the GPU only (no CPU fallback)")
-    if num is not None and num.dtype != torch.float64:
-        raise TypeError("fit_multinomial_design: num must be float64, got %s" % num.dtype)
+    _require_raw_rows("fit_multinomial_design", num, y)
     y = y.to(torch.float64).contiguous()
     classes = engine.multinomial_classes("fit_multinomial_design", classes, len(spec.names))
     return _fit_design(engine.onehot_multinomial_fit_ex, engine.multinomial_fit_ex, num, codes, y, spec, partition_num, part_offsets,
@@ -1312,7 +1243,7 @@ def multinomial_model_eval(sample_df, Y_name, par, classes, fit_intercept=False,
     """Log-likelihood (sum log p_y) of every estimator column of `par` (J * pe rows, class-major) on one partition, shaped like
     logistic_model_eval's output: one row, a column per estimator (one pass without the information per column).  structured=True
     with a dummy_info and a qualifying design runs the passes on the raw numerics + level codes."""
-    pard = np.asarray(par, dtype=np.float64)
+    run = None
     if structured and len(dummy_info) > 0:
         frame, C = _multinomial_codes_frame("multinomial_model_eval", sample_df, Y_name, classes)
         spec, plan, codes, unknown, yd, _, _ = _count_raw_frame(frame, Y_name, fit_intercept, None, None, dummy_info,
@@ -1322,16 +1253,14 @@ def multinomial_model_eval(sample_df, Y_name, par, classes, fit_intercept=False,
             if missing or unknown:
                 _warn_missing_levels(missing, len(sample_df), spec.names, fit_intercept, skip=False)
             num, cd = spec.numeric_to_device(frame), torch.from_numpy(codes).cuda()
-            out = {}
-            for i in range(pard.shape[1]):
-                b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
-                out[par.columns[i]] = [float(engine.onehot_multinomial_pass(plan, num, cd, yd, b, C, want_H=False)[2].item())]
-            return pd.DataFrame(out)
-    Xd, _, yd, C = _multinomial_frame("multinomial_model_eval", sample_df, Y_name, classes, fit_intercept, dummy_info,
-                                      dummy_factors_baseline, data_info, for_eval=True)
-    X = engine.row_major(Xd)
-    out = {}
-    for i in range(pard.shape[1]):
-        b = torch.from_numpy(np.ascontiguousarray(pard[:, i])).cuda()
-        out[par.columns[i]] = [float(engine.multinomial_pass(X, yd, b, C, fit_intercept=fit_intercept, want_H=False)[2].item())]
-    return pd.DataFrame(out)
+
+            def run(b):
+                return engine.onehot_multinomial_pass(plan, num, cd, yd, b, C, want_H=False)
+    if run is None:
+        Xd, _, yd, C = _multinomial_frame("multinomial_model_eval", sample_df, Y_name, classes, fit_intercept, dummy_info,
+                                          dummy_factors_baseline, data_info, for_eval=True)
+        X = engine.row_major(Xd)
+
+        def run(b):
+            return engine.multinomial_pass(X, yd, b, C, fit_intercept=fit_intercept, want_H=False)
+    return _loglik_frame(par, run)
