@@ -13,12 +13,13 @@
 //   3 the Gram              onehot_gram_impl(plan, num, codes, r) with irls_weights = false: r is unbounded, so the ordered
 //                           floating-point mode, never the fixed-point one.
 // Traffic per row: 8q + 4f + 8 (y) + 8 (o) + 16 (r, mu written) bytes for the pass, 8q + 4f + 8 for the Gram.
-// The once-per-partition sums, the dispersion sums over (y, mu), the scaling and the fit driver are gamma.hip's
-// (gamma_internal.h); the row checks of num / codes and the plan's constant column are onehot_poisson.hip's (poisson_internal.h).
+// The once-per-partition sums and the dispersion sums over (y, mu) are gamma.hip's, reached through its family record; the
+// entries' bodies, the workspace, the scaling and the fit driver are the dispersion driver's (dispersion.hip,
+// dispersion_internal.h); the row checks of num / codes and the plan's constant column are onehot_poisson.hip's.
 #include "common.h"
 #include "onehot_plan.h"
 #include "poisson_internal.h"
-#include "gamma_internal.h"
+#include "dispersion_internal.h"
 #include <math.h>
 #include <algorithm>
 
@@ -45,37 +46,10 @@ struct OhGammaRow {       // eta += o, mu = exp(eta), r = y / mu = w (kept from 
 };
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-struct OhGammaLayout {
-    size_t off_oh, oh_bytes, off_w, off_mu, off_y, off_o, off_cpart, off_cst, off_dpart, off_dst, off_state, total;
-};
-
-// off_oh: the arena of the structured passes (the pass's partials, then the Gram's: onehot_workspace_bytes_impl sizes both);
-// row_step > 1: room for the gathered responses and offsets of a strided partition; then the Newton state
-static OhGammaLayout oh_gamma_layout(const dlsa_onehot_plan* pl, int64_t max_rows, int64_t row_step) {
-    OhGammaLayout l{};
-    const int64_t n = std::max<int64_t>(max_rows, 1);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
-    l.oh_bytes = align_up(onehot_workspace_bytes_impl(pl, n), 256);
-    l.off_oh = take(l.oh_bytes);
-    l.off_w = take(8 * (size_t)n);
-    l.off_mu = take(8 * (size_t)n);
-    l.off_y = take(row_step > 1 ? 8 * (size_t)n : 0);
-    l.off_o = take(row_step > 1 ? 8 * (size_t)n : 0);
-    l.off_cpart = take(8 * (size_t)GAMMA_NC * GAMMA_SUM_BLOCKS);
-    l.off_cst = take(8 * 4);
-    l.off_dpart = take(8 * (size_t)GAMMA_ND * GAMMA_SUM_BLOCKS);
-    l.off_dst = take(8 * 4);
-    l.off_state = take(newton_state_bytes(onehot_plan_p(pl)));
-    l.total = o;
-    return l;
-}
-
-// One partition at a fixed beta and unit dispersion.  H (nullable) needs w (r per row: the Gram's weights); g, loglik (the sum of
-// -(r + eta)) and mu nullable.  ws_oh: the structured passes' arena (256-aligned, >= onehot_workspace_bytes_impl(pl, n)).
-static int oh_gamma_pass_impl(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
-                              const double* y, const double* off, const double* beta, int64_t n, double* H, int64_t ldh, double* g,
-                              double* loglik, double* w, double* mu, void* ws_oh, size_t ws_oh_bytes, hipStream_t s) {
+// the structured row pass of the dispersion driver (dispersion_internal.h): w is r per row, loglik the sum of -(r + eta)
+static int oh_gamma_rows(const dlsa_onehot_plan* pl, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc, const double* y,
+                         const double* off, const double* beta, int64_t n, double* H, int64_t ldh, double* g, double* loglik, double* w,
+                         double* mu, void* ws_oh, size_t ws_oh_bytes, hipStream_t s) {
     const char* who = "onehot gamma pass";
     const int rc = off ? oh_row_pass(who, OhGammaRow<true>{off, 0.0}, pl, num, ldn, codes, ldc, y, beta, n, w, mu, g, loglik, ws_oh, ws_oh_bytes, s)
                        : oh_row_pass(who, OhGammaRow<false>{off, 0.0}, pl, num, ldn, codes, ldc, y, beta, n, w, mu, g, loglik, ws_oh, ws_oh_bytes, s);
@@ -89,32 +63,15 @@ static int oh_gamma_pass_impl(const dlsa_onehot_plan* pl, const double* num, int
 extern "C" {
 
 size_t dlsa_onehot_gamma_workspace_bytes(const dlsa_onehot_plan* plan, int64_t max_rows, int64_t row_step) {
-    if (!plan || max_rows < 0 || row_step < 1) return 0;
-    return dlsa::oh_gamma_layout(plan, max_rows, row_step).total;
+    return dlsa::disp_onehot_workspace_bytes(dlsa::GAMMA_NC, plan, max_rows, row_step);
 }
 
 int dlsa_onehot_gamma_pass_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
                                const double* y, const double* offset, const double* beta, double dispersion, int64_t n, double* H,
                                int64_t ldh, double* g, double* loglik, double* w_out, double* stats_out, void* ws, size_t ws_bytes,
                                void* stream) {
-    using namespace dlsa;
-    DLSA_REQUIRE(plan && y && beta, "onehot_gamma_pass: null plan, y or beta");
-    int rc = oh_pois_check_rows("onehot_gamma_pass", plan, num, ldn, codes, ldc);
-    if (rc) return rc;
-    const int p = onehot_plan_p(plan);
-    DLSA_REQUIRE(n >= 1 && (!H || ldh >= p), "onehot_gamma_pass: bad shape n=%lld p=%d ldh=%lld", (long long)n, p, (long long)ldh);
-    DLSA_REQUIRE(dispersion > 0 && isfinite(dispersion), "onehot_gamma_pass: the dispersion must be positive and finite");
-    const OhGammaLayout l = oh_gamma_layout(plan, n, 1);
-    rc = newton_check_ws("onehot_gamma_pass", ws, ws_bytes, l.total);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    char* wsc = (char*)ws;
-    double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
-    double* mu = stats_out ? (double*)(wsc + l.off_mu) : nullptr;
-    rc = oh_gamma_pass_impl(plan, num, ldn, codes, ldc, y, offset, beta, n, H, ldh, g, loglik, w, mu, wsc + l.off_oh, l.oh_bytes, s);
-    if (rc) return rc;
-    return gamma_pass_finish(y, offset, mu, n, p, dispersion, H, ldh, g, loglik, stats_out, (double*)(wsc + l.off_cpart),
-                             (double*)(wsc + l.off_cst), (double*)(wsc + l.off_dpart), s);
+    return dlsa::disp_onehot_pass_entry("onehot_gamma_pass", dlsa::gamma_family(), dlsa::oh_gamma_rows, plan, num, ldn, codes, ldc, y,
+                                        offset, beta, dispersion, n, H, ldh, g, loglik, w_out, stats_out, ws, ws_bytes, stream);
 }
 
 int dlsa_onehot_gamma_fit_f64(const dlsa_onehot_plan* plan, const double* num, int64_t ldn, const int32_t* codes, int64_t ldc,
@@ -123,43 +80,10 @@ int dlsa_onehot_gamma_fit_f64(const dlsa_onehot_plan* plan, const double* num, i
                               double* Sig_inv, double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host,
                               double* dispersion_host, double* pearson_host, double* deviance_host, void* ws, size_t ws_bytes,
                               void* stream) {
-    using namespace dlsa;
-    DLSA_REQUIRE(plan && y && part_first_host && part_rows_host && coef && Sig_inv && Sig_invMcoef, "onehot_gamma_fit: null argument");
-    int rc = oh_pois_check_rows("onehot_gamma_fit", plan, num, ldn, codes, ldc);
-    if (rc) return rc;
-    DLSA_REQUIRE(K > 0 && row_step >= 1, "onehot_gamma_fit: bad shape K=%d step=%lld", K, (long long)row_step);
-    DLSA_REQUIRE(max_iter > 0 && tol > 0, "onehot_gamma_fit: bad tol/max_iter");
-    DLSA_REQUIRE(!(dispersion_fixed > 0) || isfinite(dispersion_fixed), "onehot_gamma_fit: a fixed dispersion must be finite");
-    int64_t max_rows = 0;
-    for (int k = 0; k < K; ++k) {
-        DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "onehot_gamma_fit: negative partition shape (partition %d)", k);
-        max_rows = std::max(max_rows, part_rows_host[k]);
-    }
-    const int p = onehot_plan_p(plan);
-    const OhGammaLayout l = oh_gamma_layout(plan, max_rows, row_step);
-    rc = newton_check_ws("onehot_gamma_fit", ws, ws_bytes, l.total);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    char* wsc = (char*)ws;
-    GammaFitBufs b{};
-    b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
-    b.dpart = (double*)(wsc + l.off_dpart); b.dst = (double*)(wsc + l.off_dst);
-    b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
-    b.mu = (double*)(wsc + l.off_mu);
-    b.st = newton_state_at(wsc + l.off_state, p);
-    double* wv = (double*)(wsc + l.off_w);
-    void* ws_oh = wsc + l.off_oh;
-    const size_t oh_bytes = l.oh_bytes;
-    const int64_t pn = ldn * row_step, pc = ldc * row_step;   // rows first, first + step, ...: strided views, num / codes read in place
-    const GammaEval eval = [=](int k, const double* yk, const double* ok, int64_t nk, const double* beta, double* Hk, double* g,
-                               double* ll, double* mu) {
-        const double* numk = num ? num + part_first_host[k] * ldn : nullptr;
-        const int32_t* codesk = codes ? codes + part_first_host[k] * ldc : nullptr;
-        return oh_gamma_pass_impl(plan, numk, pn, codesk, pc, yk, ok, beta, nk, Hk, p, g, ll, wv, mu, ws_oh, oh_bytes, s);
-    };
-    return gamma_fit_core("onehot_gamma_fit", y, offset, part_first_host, part_rows_host, row_step, K, p, oh_pois_icpt_col(plan),
-                          dispersion_fixed, tol, max_iter, coef, Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host,
-                          dispersion_host, pearson_host, deviance_host, b, eval, s);
+    return dlsa::disp_onehot_fit_entry("onehot_gamma_fit", dlsa::gamma_family(), dlsa::oh_gamma_rows, plan, num, ldn, codes, ldc, y,
+                                       offset, part_first_host, part_rows_host, row_step, K, dispersion_fixed, tol, max_iter, coef,
+                                       Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host, dispersion_host, pearson_host,
+                                       deviance_host, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 // (onehot_poisson.hip) through poisson_internal.h, as are the constant-term, log-likelihood-fix and gather launchers; the Newton
 // iteration itself is newton_fit.h's, shared with negbin.hip and cox.hip.
 #include "common.h"
+#include "block_sums.h"
 #include "poisson_internal.h"
 #include <math.h>
 #include <algorithm>
@@ -42,7 +43,6 @@ struct PoisRow {
 // ---- once per partition: [sum lgamma(y + 1), sum y, sum e^o, rows with y < 0 or a non-finite y / o] --------------------
 __global__ __launch_bounds__(256) void poisson_const_kernel(const double* __restrict__ y, const double* __restrict__ off,
                                                             int64_t n, double* __restrict__ part) {
-    __shared__ double red[4][4];
     double lg = 0.0, sy = 0.0, se = 0.0, bad = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double yv = y[i], ov = off ? off[i] : 0.0;
@@ -54,22 +54,17 @@ __global__ __launch_bounds__(256) void poisson_const_kernel(const double* __rest
             bad += 1.0;
         }
     }
-    lg = wave_allreduce_sum(lg); sy = wave_allreduce_sum(sy); se = wave_allreduce_sum(se); bad = wave_allreduce_sum(bad);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[wave][0] = lg; red[wave][1] = sy; red[wave][2] = se; red[wave][3] = bad; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double t = red[0][threadIdx.x];
-        for (int k = 1; k < 4; ++k) t += red[k][threadIdx.x];
-        part[(int64_t)blockIdx.x * 4 + threadIdx.x] = t;
-    }
+    const double acc[4] = {lg, sy, se, bad};
+    block_partials_store(acc, part);
 }
 
-// one wave per quantity, the block partials in a fixed order
-__global__ __launch_bounds__(256) void poisson_const_finish_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
+// one wave per quantity (nq <= 4 of them), the block partials in a fixed order
+__global__ __launch_bounds__(256) void block_sum_finish_kernel(const double* __restrict__ part, int nblocks, int nq,
+                                                              double* __restrict__ out) {
     const int j = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (j >= nq) return;
     double s = 0.0;
-    for (int b = lane; b < nblocks; b += 64) s += part[(int64_t)b * 4 + j];
+    for (int b = lane; b < nblocks; b += 64) s += part[(int64_t)b * nq + j];
     s = wave_allreduce_sum(s);
     if (lane == 0) out[j] = s;
 }
@@ -114,12 +109,16 @@ static PoisLayout pois_layout(int64_t max_rows, int p, int64_t row_step) {
     return l;
 }
 
+int block_sum_finish(const double* part, int nblocks, int nq, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(block_sum_finish_kernel, dim3(1), dim3(256), 0, s, part, nblocks, nq, out);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
 int pois_const(const double* y, const double* off, int64_t n, double* cpart, double* cst, hipStream_t s) {
     const int blocks = (int)std::min<int64_t>(POIS_CONST_BLOCKS, std::max<int64_t>(1, (n + 255) / 256));
     hipLaunchKernelGGL(poisson_const_kernel, dim3(blocks), dim3(256), 0, s, y, off, n, cpart);
-    hipLaunchKernelGGL(poisson_const_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)cpart, blocks, cst);
-    DLSA_HIP_CHECK(hipGetLastError());
-    return DLSA_OK;
+    return block_sum_finish(cpart, blocks, 4, cst, s);
 }
 
 int pois_ll_fix(double* ll, const double* cst, hipStream_t s) {

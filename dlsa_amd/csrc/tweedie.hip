@@ -25,15 +25,16 @@
 //                           the intercept and H wanted, of X'w and sum w;
 //   2 logit_finish_launch   the fixed-order column sums of those partials (logit.hip, shared);
 //   3 the Gram              dlsa_gram_f64's dispatch on (X, w) into the p x p block (gram_icpt_impl with the border).
-// Once per partition: tweedie_const_kernel + the sum finish of gamma.hip (sum y e^((1 - xi) o) and sum e^((2 - xi) o) for the
+// Once per partition: tweedie_const_kernel + block_sum_finish_kernel (sum y e^((1 - xi) o) and sum e^((2 - xi) o) for the
 // intercept's start, the data check, the count of positive responses).  Once per fit (and per pass that asks): tweedie_disp_kernel
-// + the same finish over (y, mu), 16 bytes per row, and gamma.hip's scaling of the pe x pe block.
-// The fit driver (tweedie_fit_core) takes the evaluation as a callable and is shared with the structured one-hot fit
-// (onehot_tweedie.hip) through tweedie_internal.h; the Newton iteration is newton_fit.h's with the policy of the Poisson fit, the
-// gather of a strided partition's responses and offsets poisson_internal.h's.
+// + the same finish over (y, mu), 16 bytes per row, and disp_scale_kernel on the pe x pe block.
+// This file holds what is the Tweedie family's: the row model, the two sum kernels, the log-likelihood and the record that hands
+// them to the driver of the dispersion families (dispersion.hip, dispersion_internal.h), which owns the entries' bodies, the
+// workspace and the fit; onehot_tweedie.hip brings the same record with its own row pass and shares the row's arithmetic through
+// tweedie_internal.h.
 #include "common.h"
 #include "poisson_internal.h"
-#include "gamma_internal.h"
+#include "dispersion_internal.h"
 #include "tweedie_internal.h"
 #include <math.h>
 #include <algorithm>
@@ -43,6 +44,9 @@ namespace dlsa {
 #include "rowdot.h"       // merged_reduce, row_of_lane, rep_mask, rank1_update
 #include "poisson_exp.h"  // exp_full
 #include "count_pass.h"   // count_pass_kernel, count_pass, CountScratch
+
+// once per partition, TWEEDIE_NC sums: [sum y e^((1 - xi) o), sum e^((2 - xi) o), rows with y < 0 or a non-finite y / o, rows with y > 0]
+enum { TWEEDIE_YEO = 0, TWEEDIE_EO = 1, TWEEDIE_BAD = 2, TWEEDIE_POS = 3 };
 
 // the Tweedie row at unit dispersion (tweedie_row, tweedie_internal.h): weight (xi - 1) y a + (2 - xi) b, residual y a - b, term
 // y a / (1 - xi) - b / (2 - xi)
@@ -63,10 +67,9 @@ static TweedieRow tweedie_row_model(double power) {
     return TweedieRow{c1, c2, 1.0 / c1, 1.0 / c2};
 }
 
-// ---- once per partition: [sum y e^((1 - xi) o), sum e^((2 - xi) o), rows with y < 0 or a non-finite y / o, rows with y > 0] ---
+// ---- once per partition: the TWEEDIE_NC sums ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tweedie_const_kernel(const double* __restrict__ y, const double* __restrict__ off, int64_t n,
                                                             double one_m_xi, double* __restrict__ part) {
-    __shared__ double red[4][TWEEDIE_NC];
     double acc[TWEEDIE_NC] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double yv = y[i], ov = off ? off[i] : 0.0;
@@ -79,18 +82,7 @@ __global__ __launch_bounds__(256) void tweedie_const_kernel(const double* __rest
             acc[TWEEDIE_BAD] += 1.0;
         }
     }
-    const int wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < TWEEDIE_NC; ++j) {
-        const double t = wave_allreduce_sum(acc[j]);
-        if ((threadIdx.x & 63) == 0) red[wave][j] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < TWEEDIE_NC) {
-        double t = red[0][threadIdx.x];
-        for (int k = 1; k < 4; ++k) t += red[k][threadIdx.x];
-        part[(int64_t)blockIdx.x * TWEEDIE_NC + threadIdx.x] = t;
-    }
+    block_partials_store(acc, part);
 }
 
 // ---- the dispersion sums over (y, mu): [sum (y - mu)^2 mu^-xi, 2 sum (y^(2 - xi) / ((1 - xi)(2 - xi)) - y a / (1 - xi) + b / (2 - xi))]
@@ -98,7 +90,6 @@ __global__ __launch_bounds__(256) void tweedie_const_kernel(const double* __rest
 // the result selected away, so no log(0) is formed and no lane branches.
 __global__ __launch_bounds__(256) void tweedie_disp_kernel(const double* __restrict__ y, const double* __restrict__ mu, int64_t n,
                                                            double one_m_xi, double two_m_xi, double* __restrict__ part) {
-    __shared__ double red[4][TWEEDIE_ND];
     const double inv_one = 1.0 / one_m_xi, inv_two = 1.0 / two_m_xi, inv_both = inv_one * inv_two;
     double ps = 0.0, dv = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -110,16 +101,8 @@ __global__ __launch_bounds__(256) void tweedie_disp_kernel(const double* __restr
         const double yp = tweedie_exp_prod(two_m_xi, log(pos ? yv : 1.0));
         dv += fma(pos ? yp : 0.0, inv_both, fma(b, inv_two, -(yv * a * inv_one)));
     }
-    ps = wave_allreduce_sum(ps);
-    dv = wave_allreduce_sum(dv);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[wave][GAMMA_PEARSON] = ps; red[wave][GAMMA_DEV] = dv; }
-    __syncthreads();
-    if (threadIdx.x < TWEEDIE_ND) {
-        double t = red[0][threadIdx.x];
-        for (int k = 1; k < 4; ++k) t += red[k][threadIdx.x];
-        part[(int64_t)blockIdx.x * TWEEDIE_ND + threadIdx.x] = threadIdx.x == GAMMA_DEV ? 2.0 * t : t;
-    }
+    const double acc[DISP_ND] = {ps, 2.0 * dv};               // (the doubling is exact, so it commutes with the sums)
+    block_partials_store(acc, part);
 }
 
 // the pass entry's quasi-log-likelihood from the row sum of q: nu ll (NaN when a row is not a valid response)
@@ -127,151 +110,53 @@ __global__ void tweedie_ll_fix_kernel(double* __restrict__ ll, const double* __r
     if (threadIdx.x == 0) ll[0] = cst[TWEEDIE_BAD] > 0.0 ? NAN : nu * ll[0];
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------
-int tweedie_const(const double* y, const double* off, int64_t n, double power, double* cpart, double* cst, hipStream_t s) {
-    const int blocks = gamma_sum_blocks(n);
-    hipLaunchKernelGGL(tweedie_const_kernel, dim3(blocks), dim3(256), 0, s, y, off, n, 1.0 - power, cpart);
-    return gamma_sum_finish(cpart, blocks, TWEEDIE_NC, cst, s);
+// ---- host side: the family record ------------------------------------------------------------------------------------------
+static int tweedie_const(const DispFamily& f, const double* y, const double* off, int64_t n, double* cpart, double* cst, hipStream_t s) {
+    const int blocks = disp_sum_blocks(n);
+    hipLaunchKernelGGL(tweedie_const_kernel, dim3(blocks), dim3(256), 0, s, y, off, n, 1.0 - f.power, cpart);
+    return block_sum_finish(cpart, blocks, TWEEDIE_NC, cst, s);
 }
 
-int tweedie_disp(const double* y, const double* mu, int64_t n, double power, double* dpart, double* dst, hipStream_t s) {
-    const int blocks = gamma_sum_blocks(n);
-    hipLaunchKernelGGL(tweedie_disp_kernel, dim3(blocks), dim3(256), 0, s, y, mu, n, 1.0 - power, 2.0 - power, dpart);
-    return gamma_sum_finish(dpart, blocks, TWEEDIE_ND, dst, s);
+static int tweedie_disp(const DispFamily& f, const double* y, const double* mu, int64_t n, double* dpart, double* dst, hipStream_t s) {
+    const int blocks = disp_sum_blocks(n);
+    hipLaunchKernelGGL(tweedie_disp_kernel, dim3(blocks), dim3(256), 0, s, y, mu, n, 1.0 - f.power, 2.0 - f.power, dpart);
+    return block_sum_finish(dpart, blocks, DISP_ND, dst, s);
 }
 
-int tweedie_pass_finish(const double* y, const double* off, const double* mu, int64_t n, int pe, double power, double dispersion,
-                        double* H, int64_t ldh, double* g, double* loglik, double* stats_out, double* cpart, double* cst,
-                        double* dpart, hipStream_t s) {
-    const double nu = 1.0 / dispersion;
-    int rc = DLSA_OK;
-    if (stats_out) {
-        rc = tweedie_disp(y, mu, n, power, dpart, stats_out, s);
-        if (rc) return rc;
+static int tweedie_check(const char* who, int k, const double* cst) {
+    if (cst[TWEEDIE_BAD] > 0.0) {
+        set_error("%s: partition %d has %.0f rows with a negative or non-finite response or a non-finite offset", who, k,
+                  cst[TWEEDIE_BAD]);
+        return DLSA_ERR_INVALID;
     }
-    if (nu != 1.0) {
-        rc = gamma_scale(H, ldh, pe, g, nu, s);
-        if (rc) return rc;
+    if (!(cst[TWEEDIE_POS] > 0.0)) {
+        set_error("%s: partition %d has no positive response: its maximum-likelihood fit runs off to mu = 0", who, k);
+        return DLSA_ERR_INVALID;
     }
-    if (!loglik) return DLSA_OK;
-    rc = tweedie_const(y, off, n, power, cpart, cst, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tweedie_ll_fix_kernel, dim3(1), dim3(64), 0, s, loglik, (const double*)cst, nu);
+    return DLSA_OK;
+}
+
+// sum y e^((1 - xi) o) / sum e^((2 - xi) o)
+static double tweedie_start_mean(const double* cst, int64_t) { return cst[TWEEDIE_YEO] / cst[TWEEDIE_EO]; }
+
+// (not the Gamma expression with zero coefficients: cst[0] can be infinite here, and 0 * inf would make a finite result NaN)
+static double tweedie_loglik(double nu, double ll, const double*, int64_t) { return nu * ll; }
+
+static int tweedie_ll_fix(double* ll, const double* cst, double nu, int64_t, hipStream_t s) {
+    hipLaunchKernelGGL(tweedie_ll_fix_kernel, dim3(1), dim3(64), 0, s, ll, cst, nu);
     DLSA_HIP_CHECK(hipGetLastError());
     return DLSA_OK;
 }
 
-struct TweedieLayout {
-    CountScratchOff sc;
-    size_t off_cpart, off_cst, off_dpart, off_dst, off_w, off_mu, off_y, off_o, off_gram, total;
-};
-
-// pass scratch; row_step > 1: room for the gathered responses and offsets of a strided partition
-static TweedieLayout tweedie_layout(int64_t max_rows, int p, int64_t row_step) {
-    TweedieLayout l{};
-    const int64_t n = std::max<int64_t>(max_rows, 1);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
-    l.sc = count_scratch_take(take, p);
-    l.off_cpart = take(8 * (size_t)TWEEDIE_NC * GAMMA_SUM_BLOCKS);
-    l.off_cst = take(8 * 4);
-    l.off_dpart = take(8 * (size_t)TWEEDIE_ND * GAMMA_SUM_BLOCKS);
-    l.off_dst = take(8 * 4);
-    l.off_w = take(8 * (size_t)n);
-    l.off_mu = take(8 * (size_t)n);
-    l.off_y = take(row_step > 1 ? 8 * (size_t)n : 0);
-    l.off_o = take(row_step > 1 ? 8 * (size_t)n : 0);
-    l.off_gram = take(gram_workspace_bytes_impl(n, p, 8));
-    l.total = o;
-    return l;
+DispFamily tweedie_family(double power) {
+    // 1 < power < 2 (a NaN fails both comparisons)
+    const char* bad = power > 1.0 && power < 2.0 ? nullptr : "the variance power must lie strictly between 1 and 2";
+    return {TWEEDIE_NC, power, bad, tweedie_const, tweedie_disp, tweedie_check, tweedie_start_mean, tweedie_loglik, tweedie_ll_fix};
 }
 
-// One partition at a fixed beta and unit dispersion (count_pass with the Tweedie row): w is the weight per row, loglik the sum of
-// q, mu (nullable) mu per row.
-static int tweedie_pass_impl(double power, const double* X, int64_t ldx, const double* y, const double* off, const double* beta,
-                             int64_t n, int p, int intercept, double* H, int64_t ldh, double* g, double* loglik, double* w,
-                             double* mu, char* ws, const TweedieLayout& l, hipStream_t s) {
-    return count_pass(tweedie_row_model(power), X, ldx, y, off, beta, n, p, intercept, H, ldh, g, loglik, w, mu, count_scratch_at(ws, l.sc),
-                      ws + l.off_gram, l.total - l.off_gram, s);
-}
-
-// The driver of the Tweedie fits (dense rows here, raw one-hot rows in onehot_tweedie.hip): `eval` is the only part that knows the
-// representation of the design; the iteration is newton_fit_loop (newton_fit.h).
-int tweedie_fit_core(const char* who, const double* y, const double* offset, const int64_t* part_first_host,
-                     const int64_t* part_rows_host, int64_t row_step, int K, int pe, int icpt_col, double power,
-                     double dispersion_fixed, double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef,
-                     int* n_iter_host, int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
-                     double* deviance_host, const TweedieFitBufs& b, const TweedieEval& eval, hipStream_t s) {
-    const bool fixed = dispersion_fixed > 0;
-    if (!fixed) {
-        for (int k = 0; k < K; ++k) {
-            if (part_rows_host[k] > 0 && part_rows_host[k] <= pe) {
-                set_error("%s: partition %d has %lld rows for %d coefficients: the estimated dispersion has no degrees of freedom",
-                          who, k, (long long)part_rows_host[k], pe);
-                return DLSA_ERR_INVALID;
-            }
-        }
-    }
-    int overall = DLSA_OK;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        double* Hk = Sig_inv + (size_t)k * pe * pe;
-        double* ck = coef + (size_t)k * pe;
-        double* sk = Sig_invMcoef + (size_t)k * pe;
-        int st_k = DLSA_PART_EMPTY, iters = 0;
-        double ll = 0.0, phi = 0.0, d[TWEEDIE_ND] = {0.0, 0.0};
-        if (nk > 0) {
-            const double *yk, *ok;
-            int rc = pois_gather_rows(y, offset, part_first_host[k], row_step, nk, b.ybuf, b.obuf, yk, ok, s);
-            if (rc) return rc;
-            rc = tweedie_const(yk, ok, nk, power, b.cpart, b.cst, s);
-            if (rc) return rc;
-            double cst[TWEEDIE_NC];
-            DLSA_HIP_CHECK(hipMemcpyAsync(cst, b.cst, sizeof(cst), hipMemcpyDeviceToHost, s));
-            DLSA_HIP_CHECK(hipStreamSynchronize(s));
-            if (cst[TWEEDIE_BAD] > 0.0) {
-                set_error("%s: partition %d has %.0f rows with a negative or non-finite response or a non-finite offset", who, k,
-                          cst[TWEEDIE_BAD]);
-                return DLSA_ERR_INVALID;
-            }
-            if (!(cst[TWEEDIE_POS] > 0.0)) {
-                set_error("%s: partition %d has no positive response: its maximum-likelihood fit runs off to mu = 0", who, k);
-                return DLSA_ERR_INVALID;
-            }
-            // the intercept starts at log(sum y e^((1 - xi) o) / sum e^((2 - xi) o)), the exact MLE of the intercept-only model
-            const double m0 = cst[TWEEDIE_YEO] / cst[TWEEDIE_EO];
-            const double b0 = (icpt_col >= 0 && m0 > 0.0 && isfinite(m0)) ? log(m0) : 0.0;
-            rc = pois_start(b.st.beta, pe, icpt_col, b0, s);
-            if (rc) return rc;
-            const NewtonDevice dev{b.st, Hk, pe, s};
-            NewtonOutcome o;
-            rc = newton_fit_loop(NEWTON_POISSON, tol, max_iter + 1,
-                                 [&](bool&) { return eval(k, yk, ok, nk, b.st.beta, Hk, b.st.g, b.st.stats + 3, b.mu); }, dev,
-                                 newton_no_hook, o);
-            if (rc) return rc;
-            st_k = o.status; iters = o.n_iter;
-            // the dispersion of the point H was evaluated at: b.mu is that evaluation's
-            rc = tweedie_disp(yk, b.mu, nk, power, b.dpart, b.dst, s);
-            if (rc) return rc;
-            DLSA_HIP_CHECK(hipMemcpyAsync(d, b.dst, sizeof(d), hipMemcpyDeviceToHost, s));
-            DLSA_HIP_CHECK(hipStreamSynchronize(s));
-            phi = fixed ? dispersion_fixed : d[GAMMA_PEARSON] / (double)(nk - pe);
-            ll = o.ll;
-            if (phi > 0.0 && isfinite(phi)) {              // (else: Sig_inv and loglik stay those of unit dispersion)
-                const double nu = 1.0 / phi;
-                rc = gamma_scale(Hk, pe, pe, nullptr, nu, s);
-                if (rc) return rc;
-                ll = nu * o.ll;
-            }
-        }
-        const int rcf = newton_fit_finish(st_k, iters, ll, b.st.beta, pe, Hk, ck, sk, k, n_iter_host, status_host, loglik_host, overall, s);
-        if (rcf) return rcf;
-        if (dispersion_host) dispersion_host[k] = phi;
-        if (pearson_host) pearson_host[k] = d[GAMMA_PEARSON];
-        if (deviance_host) deviance_host[k] = d[GAMMA_DEV];
-    }
-    DLSA_HIP_CHECK(hipStreamSynchronize(s));
-    return overall;
+// the dense row pass: count_pass with the Tweedie row at `power` (w is the weight per row, loglik the sum of q)
+static DispDenseRows tweedie_rows(double power) {
+    return [power](const auto&... a) { return count_pass(tweedie_row_model(power), a...); };
 }
 
 }  // namespace dlsa
@@ -279,32 +164,14 @@ int tweedie_fit_core(const char* who, const double* y, const double* offset, con
 extern "C" {
 
 size_t dlsa_tweedie_workspace_bytes(int64_t max_rows, int p, int intercept, int64_t row_step) {
-    if (p <= 0 || p + (intercept ? 1 : 0) > 2048 || max_rows < 0 || row_step < 1) return 0;
-    return dlsa::align_up(dlsa::tweedie_layout(max_rows, p, row_step).total, 256) + dlsa::newton_state_bytes(p + (intercept ? 1 : 0));
+    return dlsa::disp_workspace_bytes(dlsa::TWEEDIE_NC, max_rows, p, intercept, row_step);
 }
 
 int dlsa_tweedie_pass_f64(const double* X, int64_t ldx, const double* y, const double* offset, const double* beta, double power,
                           double dispersion, int64_t n, int p, int intercept, double* H, int64_t ldh, double* g, double* loglik,
                           double* w_out, double* stats_out, void* ws, size_t ws_bytes, void* stream) {
-    using namespace dlsa;
-    DLSA_REQUIRE(X && y && beta, "tweedie_pass: null X, y or beta");
-    const int pe = p + (intercept ? 1 : 0);
-    DLSA_REQUIRE(n >= 1 && p > 0 && pe <= 2048 && ldx >= p && (!H || ldh >= pe), "tweedie_pass: bad shape n=%lld p=%d ldx=%lld ldh=%lld",
-                 (long long)n, p, (long long)ldx, (long long)ldh);
-    DLSA_REQUIRE(tweedie_power_ok(power), "tweedie_pass: the variance power must lie strictly between 1 and 2");
-    DLSA_REQUIRE(dispersion > 0 && isfinite(dispersion), "tweedie_pass: the dispersion must be positive and finite");
-    const TweedieLayout l = tweedie_layout(n, p, 1);
-    // (the pass carves l.total of it; the contract is the query, which also holds a fit's Newton state)
-    int rc = newton_check_ws("tweedie_pass", ws, ws_bytes, dlsa_tweedie_workspace_bytes(n, p, intercept, 1));
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    char* wsc = (char*)ws;
-    double* w = w_out ? w_out : (H ? (double*)(wsc + l.off_w) : nullptr);
-    double* mu = stats_out ? (double*)(wsc + l.off_mu) : nullptr;
-    rc = tweedie_pass_impl(power, X, ldx, y, offset, beta, n, p, intercept, H, ldh, g, loglik, w, mu, wsc, l, s);
-    if (rc) return rc;
-    return tweedie_pass_finish(y, offset, mu, n, pe, power, dispersion, H, ldh, g, loglik, stats_out, (double*)(wsc + l.off_cpart),
-                               (double*)(wsc + l.off_cst), (double*)(wsc + l.off_dpart), s);
+    return dlsa::disp_pass_entry("tweedie_pass", dlsa::tweedie_family(power), dlsa::tweedie_rows(power), X, ldx, y, offset, beta,
+                                 dispersion, n, p, intercept, H, ldh, g, loglik, w_out, stats_out, ws, ws_bytes, stream);
 }
 
 int dlsa_tweedie_fit_f64(const double* X, int64_t ldx, const double* y, const double* offset, const int64_t* part_first_host,
@@ -312,40 +179,10 @@ int dlsa_tweedie_fit_f64(const double* X, int64_t ldx, const double* y, const do
                          double dispersion_fixed, double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef,
                          int* n_iter_host, int* status_host, double* loglik_host, double* dispersion_host, double* pearson_host,
                          double* deviance_host, void* ws, size_t ws_bytes, void* stream) {
-    using namespace dlsa;
-    DLSA_REQUIRE(X && y && part_first_host && part_rows_host && coef && Sig_inv && Sig_invMcoef, "tweedie_fit: null argument");
-    const int pe = p + (intercept ? 1 : 0);
-    DLSA_REQUIRE(K > 0 && p > 0 && pe <= 2048 && ldx >= p && row_step >= 1, "tweedie_fit: bad shape K=%d p=%d ldx=%lld step=%lld", K, p,
-                 (long long)ldx, (long long)row_step);
-    DLSA_REQUIRE(max_iter > 0 && tol > 0, "tweedie_fit: bad tol/max_iter");
-    DLSA_REQUIRE(tweedie_power_ok(power), "tweedie_fit: the variance power must lie strictly between 1 and 2");
-    DLSA_REQUIRE(!(dispersion_fixed > 0) || isfinite(dispersion_fixed), "tweedie_fit: a fixed dispersion must be finite");
-    int64_t max_rows = 0;
-    for (int k = 0; k < K; ++k) {
-        DLSA_REQUIRE(part_rows_host[k] >= 0 && part_first_host[k] >= 0, "tweedie_fit: negative partition shape (partition %d)", k);
-        max_rows = std::max(max_rows, part_rows_host[k]);
-    }
-    const TweedieLayout l = tweedie_layout(max_rows, p, row_step);
-    const size_t need = dlsa_tweedie_workspace_bytes(max_rows, p, intercept, row_step);
-    const int rcw = newton_check_ws("tweedie_fit", ws, ws_bytes, need);
-    if (rcw) return rcw;
-    hipStream_t s = (hipStream_t)stream;
-    char* wsc = (char*)ws;
-    TweedieFitBufs b{};
-    b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
-    b.dpart = (double*)(wsc + l.off_dpart); b.dst = (double*)(wsc + l.off_dst);
-    b.ybuf = (double*)(wsc + l.off_y); b.obuf = (double*)(wsc + l.off_o);
-    b.mu = (double*)(wsc + l.off_mu);
-    b.st = newton_state_at(wsc + align_up(l.total, 256), pe);
-    double* wv = (double*)(wsc + l.off_w);
-    const int64_t pitch = ldx * row_step;                     // rows first, first + step, ...: a strided view, no copy of X
-    const TweedieEval eval = [=](int k, const double* yk, const double* ok, int64_t nk, const double* beta, double* Hk, double* g,
-                                 double* ll, double* mu) {
-        return tweedie_pass_impl(power, X + part_first_host[k] * ldx, pitch, yk, ok, beta, nk, p, intercept, Hk, pe, g, ll, wv, mu, wsc, l, s);
-    };
-    return tweedie_fit_core("tweedie_fit", y, offset, part_first_host, part_rows_host, row_step, K, pe, intercept ? 0 : -1, power,
-                            dispersion_fixed, tol, max_iter, coef, Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host,
-                            dispersion_host, pearson_host, deviance_host, b, eval, s);
+    return dlsa::disp_fit_entry("tweedie_fit", dlsa::tweedie_family(power), dlsa::tweedie_rows(power), X, ldx, y, offset,
+                                part_first_host, part_rows_host, row_step, K, p, intercept, dispersion_fixed, tol, max_iter, coef,
+                                Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host, dispersion_host, pearson_host,
+                                deviance_host, ws, ws_bytes, stream);
 }
 
 }  // extern "C"
