@@ -1044,6 +1044,62 @@ def multinomial_fit_ex(X, y, part_first, part_rows, row_step=1, classes=None, fi
     return out.result(rc)
 
 
+def ordinal_classes(who, classes, p):
+    """The class count of an ordinal entry: an int in 2 .. 8 with (classes - 1) + p <= 2048 coefficients (ValueError otherwise)."""
+    if isinstance(classes, bool) or int(classes) != classes:
+        raise ValueError("%s: classes must be an integer, got %r" % (who, classes))
+    classes = int(classes)
+    if not 2 <= classes <= MULTINOMIAL_MAX_CLASSES:
+        raise ValueError("%s: classes must lie in 2 .. %d, got %d" % (who, MULTINOMIAL_MAX_CLASSES, classes))
+    if classes - 1 + p > 2048:
+        raise ValueError("%s: (classes - 1) + p = %d coefficients exceed the solver's 2048" % (who, classes - 1 + p))
+    return classes
+
+
+def ordinal_pass(X, y, theta, classes, want_H=True, want_w=False):
+    """One ordinal (proportional-odds) partition at a fixed theta (dlsa_ordinal_pass_f64, include/dlsa_hip_ordinal.h): y [n] holds
+    the class codes 0 .. classes - 1 as fp64, J = classes - 1, logit P(y <= j) = alpha_{j+1} - x'beta.  theta [J + p] = [alpha_1 ..
+    alpha_J | beta], cutpoints first; there is no intercept argument, the cutpoints are the intercepts.  Returns (H [d, d] the
+    observed information or None, g [d] the score, loglik [1] = sum log P(y_i) -- NaN when the cutpoints are not strictly increasing
+    or a response is no class code --, w [n] = -d2l/deta2 per row or None)."""
+    lib = _lib.load()
+    _require_gpu(X, y, theta)
+    _f64(X, "X"); _f64(y, "y"); _f64(theta, "theta")
+    n, p = X.shape
+    classes = ordinal_classes("ordinal_pass", classes, p)
+    d = classes - 1 + p
+    if n < 1 or y.numel() != n or theta.numel() != d:
+        raise ValueError("ordinal_pass: need n >= 1 rows, y with n = %d and theta with %d elements" % (n, d))
+    H, g, ll, w = _pass_out(d, n, X.device, want_H, want_w)
+    ws = _workspace(lib.dlsa_ordinal_workspace_bytes(n, p, classes, 1), X.device)
+    check(lib.dlsa_ordinal_pass_f64(_ptr(X), _rowmajor(X), _ptr(y), _ptr(theta), classes, n, p, _ptr(H), d, _ptr(g), _ptr(ll), _ptr(w),
+                                    _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, w
+
+
+def ordinal_fit_ex(X, y, part_first, part_rows, row_step=1, classes=None, tol=1e-13, max_iter=100):
+    """Per-partition ordinal (proportional-odds) fit (dlsa_ordinal_fit_f64): partitions as poisson_fit_ex, y and the layout
+    [alpha_1 .. alpha_J | beta] as ordinal_pass; `classes` (2 .. 8) is required -- a partition cannot discover the classes it lacks,
+    and one that lacks a class is refused with the partition and the class named, as is a response that is no class code.  Same result
+    dict as multinomial_fit_ex with J + p columns; `loglik` is the log-likelihood at coef.  classes = 2 is the logistic fit with
+    theta = [-intercept | beta]."""
+    lib = _lib.load()
+    _require_gpu(X, y)
+    _f64(X, "X"); _f64(y, "y")
+    n, p = X.shape
+    if y.numel() != n:
+        raise ValueError("ordinal_fit_ex: y must have n = %d elements" % n)
+    if classes is None:
+        raise ValueError("ordinal_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
+    classes = ordinal_classes("ordinal_fit_ex", classes, p)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("ordinal_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, classes - 1 + p, X.device)
+    ws = _workspace(lib.dlsa_ordinal_workspace_bytes(max_rows, p, classes, step), X.device)
+    rc = lib.dlsa_ordinal_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), c_first, c_rows, step, K, p, classes, tol, max_iter, *out.args,
+                                  _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
+
+
 def negbin_special(theta, y):
     """The dispersion kernel's special functions (dlsa_negbin_special_f64, a test entry): theta [m] > 0, y [m] >= 0 on the GPU;
     returns [m, 4] = psi(theta), psi'(theta), psi(y + theta) - psi(theta), lgamma(y + theta) - lgamma(theta) - y log(theta)."""

@@ -1264,3 +1264,83 @@ def multinomial_model_eval(sample_df, Y_name, par, classes, fit_intercept=False,
         def run(b):
             return engine.multinomial_pass(X, yd, b, C, fit_intercept=fit_intercept, want_H=False)
     return _loglik_frame(par, run)
+
+
+# ---------------------------------------------------------------------------------------------
+# Ordinal (proportional-odds) map step for a response with C ORDERED classes (delay bucket, credit grade, severity score):
+# logit P(y <= j) = alpha_{j+1} - x'beta.  A partition's block is [coef | Sig_inv coef | Sig_inv] over the J + p coefficients
+# ["intercept:1" .. "intercept:J"] + names, the J = C - 1 cutpoints first, so dlsa_mapred applies unchanged and
+# dlsa(..., unpenalized="intercepts") keeps the cutpoints out of the penalty (intercept_columns above).
+# ---------------------------------------------------------------------------------------------
+def ordinal_column_names(names, classes):
+    """The J + p column names of an ordinal block: the cutpoints "intercept:1" .. "intercept:J" (J = classes - 1), then `names`."""
+    return ["intercept:%d" % j for j in range(1, int(classes))] + list(names)
+
+
+def simulate_ordinal(sample_size, p, partition_num, classes, seed=20260101, coef_value=1.0):
+    """Seeded rows with an ordered class response: x as simulate_logistic's (U(-0.5, 0.5), the rows of engine.synth), beta* =
+    coef_value on the first int(0.4p) coefficients, the cutpoints alpha*_j = logit(j / classes) (equal class shares at eta = 0),
+    y = the number of cutpoints below eta + a logistic draw (numpy), class codes 0 .. classes - 1.  partition_id = i %
+    partition_num.  Returns the frame partition_id, y, x0 .. x{p-1}."""
+    n, p, C = int(sample_size), int(p), int(classes)
+    X, _ = engine.synth(seed, 0, n, p, labels=False)
+    X = X.cpu().numpy()
+    beta = np.zeros(p)
+    beta[:int(0.4 * p)] = float(coef_value)
+    share = np.arange(1, C) / C
+    alpha = np.log(share / (1.0 - share))
+    rng = np.random.default_rng(seed)
+    latent = X @ beta + rng.logistic(size=n)
+    y = (latent[:, None] > alpha[None, :]).sum(1).astype(np.float64)
+    pid = (np.arange(n) % int(partition_num)).astype(np.float64)
+    return pd.DataFrame(np.concatenate([pid[:, None], y[:, None], X], 1), columns=["partition_id", "y"] + ["x" + str(i) for i in range(p)])
+
+
+def fit_ordinal_partitions(X, y, classes, partition_num=None, part_offsets=None, names=None, tol=1e-13, max_iter=100):
+    """Ordinal (proportional-odds) map step for the partitions of one device-resident shard: X [n, p] fp64 row-major WITHOUT a
+    constant column (the cutpoints are the intercepts), y [n] class codes 0 .. classes - 1 on the GPU.  Partitions as
+    fit_poisson_partitions.  Every partition with rows must hold every class.  Returns MappedBlocks over the (classes - 1) + p
+    coefficients ordinal_column_names(names, classes), with `loglik` = the log-likelihood per partition."""
+    _require_dense_rows("fit_ordinal_partitions", X)
+    n, p = X.shape
+    y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
+    if y.numel() != n:
+        raise ValueError("fit_ordinal_partitions: y must have n = %d elements" % n)
+    classes = engine.ordinal_classes("fit_ordinal_partitions", classes, p)
+    names = ordinal_column_names(_column_names(names, p, False), classes)
+    first, rows, step = _partitions(n, partition_num, part_offsets)
+    r = engine.ordinal_fit_ex(engine.row_major(X), y, first, rows, row_step=step, classes=classes, tol=tol, max_iter=max_iter)
+    return _blocks(r, names, n)
+
+
+def _ordinal_frame(who, sample_df, Y_name, classes, dummy_info, dummy_factors_baseline, data_info, for_eval=False):
+    """(X device design without a ones column or None, its p names, the class codes on the device, C) of one chunk whose response
+    column holds the labels `classes`, lowest first."""
+    frame, C = _multinomial_codes_frame(who, sample_df, Y_name, classes)
+    Xd, names = _device_design(frame, Y_name, False, dummy_info, dummy_factors_baseline, data_info, for_eval=for_eval)
+    return Xd, list(names), _to_device(frame, Y_name), C
+
+
+def ordinal_model(sample_df, Y_name, classes, dummy_info=[], dummy_factors_baseline=[], data_info=[], tol=1e-13, max_iter=100):
+    """Frame-level sibling of multinomial_model for an ORDERED response: one partition (a pandas frame) whose column Y_name holds the
+    labels listed in `classes`, lowest first.  `classes` is required: a partition cannot discover the classes it lacks.  There is no
+    fit_intercept: the J cutpoints are the intercepts.  Returns the stacked (J + p) x (3 + J + p) frame `par_id, coef, Sig_invMcoef,
+    intercept:1 .. intercept:J, <name> ...`; a chunk that lacks an expected dummy level returns the all-zero block with a warning.
+    The dense path only (the design matrix is built by the design kernel)."""
+    Xd, names, yd, C = _ordinal_frame("ordinal_model", sample_df, Y_name, classes, dummy_info, dummy_factors_baseline, data_info)
+    if Xd is None:
+        return _zero_block(ordinal_column_names(names, C))
+    mb = fit_ordinal_partitions(Xd, yd, C, names=names, tol=tol, max_iter=max_iter)
+    return _first_block_frame(mb, "ordinal_model")
+
+
+def ordinal_model_eval(sample_df, Y_name, par, classes, dummy_info=[], dummy_factors_baseline=[], data_info=[]):
+    """Log-likelihood (sum log P(y)) of every estimator column of `par` (J + p rows, cutpoints first) on one partition, shaped like
+    logistic_model_eval's output: one row, a column per estimator (one pass without the information per column)."""
+    Xd, _, yd, C = _ordinal_frame("ordinal_model_eval", sample_df, Y_name, classes, dummy_info, dummy_factors_baseline, data_info,
+                                  for_eval=True)
+    X = engine.row_major(Xd)
+
+    def run(b):
+        return engine.ordinal_pass(X, yd, b, C, want_H=False)
+    return _loglik_frame(par, run)
