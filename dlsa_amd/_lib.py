@@ -209,6 +209,16 @@ ORDINAL_SIGNATURES = {
                                      ctypes.POINTER(c_dbl), c_vp, c_sz, c_vp]),
 }
 
+# name -> (restype, argtypes); every symbol the family extension header include/dlsa_hip_onehot_ordinal.h declares
+ONEHOT_ORDINAL_SIGNATURES = {
+    "dlsa_onehot_ordinal_workspace_bytes": (c_sz, [c_vp, c_i64, c_int, c_i64]),
+    "dlsa_onehot_ordinal_pass_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                             c_vp, c_sz, c_vp]),
+    "dlsa_onehot_ordinal_fit_f64": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_i64,
+                                            c_int, c_int, c_dbl, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                            ctypes.POINTER(c_dbl), c_vp, c_sz, c_vp]),
+}
+
 _lib = None
 
 
@@ -230,7 +240,7 @@ def load():
     # pointers and streams are shared (loading the system libamdhip64 first gives two runtimes).
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(ORDINAL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(ORDINAL_SIGNATURES.items()) + list(ONEHOT_ORDINAL_SIGNATURES.items()):
         fn = getattr(lib, name)       # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

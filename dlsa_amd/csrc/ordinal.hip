@@ -225,12 +225,14 @@ __global__ void ord_mask_kernel(const double* __restrict__ y, const double* __re
     if (i < n) v[i] = -((y[i] == (double)(j - 1) ? aa[i] : 0.0) + (y[i] == (double)j ? bb[i] : 0.0));
 }
 
-// g_alpha (nullable), and of H (nullable; d x d, pitch ldh) the J border rows and columns and the tridiagonal corner, both
-// triangles, from the finished sums: sc (layout of ordinal_internal.h) and the border vectors bd[j * ldbd + k] = (X'v_{j+1})_k.
+// g_alpha (nullable; with gbeta also g_beta, copied), and of H (nullable; d x d, pitch ldh) the J border rows and columns and the
+// tridiagonal corner, both triangles, from the finished sums: sc (layout of ordinal_internal.h) and the border vectors
+// bd[j * ldbd + k] = (X'v_{j+1})_k.
 __global__ void ord_assemble_kernel(const double* __restrict__ sc, const double* __restrict__ bd, int ldbd, int J, int p,
-                                    double* __restrict__ H, int64_t ldh, double* __restrict__ g) {
+                                    double* __restrict__ H, int64_t ldh, double* __restrict__ g, const double* __restrict__ gbeta) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (g && i < J) g[i] = sc[ORD_SC_GA + i];
+    if (g && gbeta && i < p) g[J + i] = gbeta[i];
     if (!H) return;
     if (i < J * p) {
         const int j = i / p, k = i - j * p;
@@ -252,6 +254,27 @@ __global__ void ord_start_kernel(double* __restrict__ theta, int J, int d, OrdSt
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
+// the launchers onehot_ordinal.hip shares (ordinal_internal.h)
+int ord_mask(const double* y, const double* aa, const double* bb, int j, int64_t n, double* v, hipStream_t s) {
+    hipLaunchKernelGGL(ord_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, aa, bb, j, n, v);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int ord_assemble(const double* sc, const double* bd, int ldbd, int J, int p, double* H, int64_t ldh, double* g, const double* gbeta,
+                 hipStream_t s) {
+    const int cells = std::max(J * p, J * J);
+    hipLaunchKernelGGL(ord_assemble_kernel, dim3((cells + 255) / 256), dim3(256), 0, s, sc, bd, ldbd, J, p, H, ldh, g, gbeta);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
+int ord_start(double* theta, int J, int d, const OrdStart& st, hipStream_t s) {
+    hipLaunchKernelGGL(ord_start_kernel, dim3((d + 255) / 256), dim3(256), 0, s, theta, J, d, st);
+    DLSA_HIP_CHECK(hipGetLastError());
+    return DLSA_OK;
+}
+
 template <int C, int NC, bool BORDER>
 static void ord_launch_v(const OrdArgs& a, bool vec, int blocks, hipStream_t s) {
     constexpr int RB = NC <= 2 ? 8 : NC == 4 ? 4 : NC == 8 ? 2 : 1;          // count_rb
@@ -353,10 +376,9 @@ static int ord_pass_impl(const double* X, int64_t ldx, const double* y, const do
     if (masked) {
         double* v = (double*)(ws + l.off_v);
         for (int j = 1; j <= J; ++j) {
-            hipLaunchKernelGGL(ord_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, (const double*)a.aa_out,
-                               (const double*)a.bb_out, j, n, v);
-            DLSA_HIP_CHECK(hipGetLastError());
-            const int rc = xtv_impl(X, ldx, v, n, p, bd + (size_t)(j - 1) * W, nullptr, nullptr, ws + l.off_gram, l.gram_bytes, s);
+            int rc = ord_mask(y, a.aa_out, a.bb_out, j, n, v, s);
+            if (rc) return rc;
+            rc = xtv_impl(X, ldx, v, n, p, bd + (size_t)(j - 1) * W, nullptr, nullptr, ws + l.off_gram, l.gram_bytes, s);
             if (rc) return rc;
         }
     }
@@ -364,11 +386,7 @@ static int ord_pass_impl(const double* X, int64_t ldx, const double* y, const do
         const int rc = gram_impl_f64(X, ldx, a.w_out, n, p, H + (size_t)J * ldh + J, ldh, 0, ws + l.off_gram, l.gram_bytes, s);
         if (rc) return rc;
     }
-    const int cells = std::max(J * p, J * J);
-    hipLaunchKernelGGL(ord_assemble_kernel, dim3((cells + 255) / 256), dim3(256), 0, s, (const double*)sc, (const double*)bd, W, J, p, H,
-                       ldh, g);
-    DLSA_HIP_CHECK(hipGetLastError());
-    return DLSA_OK;
+    return ord_assemble(sc, bd, W, J, p, H, ldh, g, nullptr, s);
 }
 
 static int ord_shape_ok(const char* who, int p, int classes) {
@@ -412,8 +430,9 @@ int dlsa_ordinal_pass_f64(const double* X, int64_t ldx, const double* y, const d
     return mn_ll_fix(loglik, (const double*)(wsc + l.off_cst), s);
 }
 
-// The shape of mn_fit_core (multinomial_internal.h): the data check of EVERY partition first, then per partition the null
-// model's start, newton_fit_loop with the policy NEWTON_POISSON on d coefficients and newton_fit_finish.
+// The per-partition driver is ord_fit_core (ordinal_internal.h, shared with the structured sibling): the data check of EVERY
+// partition first, then per partition the null model's start, newton_fit_loop with the policy NEWTON_POISSON on d coefficients and
+// newton_fit_finish.
 int dlsa_ordinal_fit_f64(const double* X, int64_t ldx, const double* y, const int64_t* part_first_host, const int64_t* part_rows_host,
                          int64_t row_step, int K, int p, int classes, double tol, int max_iter, double* coef, double* Sig_inv,
                          double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, void* ws, size_t ws_bytes,
@@ -437,72 +456,16 @@ int dlsa_ordinal_fit_f64(const double* X, int64_t ldx, const double* y, const in
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
-    double* cpart = (double*)(wsc + l.off_cpart);
-    double* cst_dev = (double*)(wsc + l.off_cst);
-    double* ybuf = (double*)(wsc + l.off_y);
-    const NewtonState st = newton_state_at(wsc + align_up(l.total, 256), d);
+    OrdFitBufs b{};
+    b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
+    b.ybuf = (double*)(wsc + l.off_y);
+    b.st = newton_state_at(wsc + align_up(l.total, 256), d);
     const int64_t pitch = ldx * row_step;                     // rows first, first + step, ...: a strided view, no copy of X
-
-    std::vector<double> counts((size_t)K * MN_NQ, 0.0);
-    const double* yk = nullptr;
-    const double* none = nullptr;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        if (nk <= 0) continue;
-        rc = pois_gather_rows(y, nullptr, part_first_host[k], row_step, nk, ybuf, nullptr, yk, none, s);
-        if (rc) return rc;
-        rc = mn_check(yk, nk, classes, cpart, cst_dev, s);
-        if (rc) return rc;
-        double* cst = counts.data() + (size_t)k * MN_NQ;
-        DLSA_HIP_CHECK(hipMemcpyAsync(cst, cst_dev, MN_NQ * sizeof(double), hipMemcpyDeviceToHost, s));
-        DLSA_HIP_CHECK(hipStreamSynchronize(s));
-        if (cst[MN_BAD] > 0.0) {
-            set_error("ordinal_fit: partition %d has %.0f rows whose response is not a class code 0 .. %d", k, cst[MN_BAD], classes - 1);
-            return DLSA_ERR_INVALID;
-        }
-        for (int c = 0; c < classes; ++c) {
-            if (!(cst[c] > 0.0)) {
-                set_error("ordinal_fit: partition %d has no row of class %d: its maximum-likelihood fit merges two cutpoints", k, c);
-                return DLSA_ERR_INVALID;
-            }
-        }
-    }
-    int overall = DLSA_OK;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        double* Hk = Sig_inv + (size_t)k * d * d;
-        double* ck = coef + (size_t)k * d;
-        double* sk = Sig_invMcoef + (size_t)k * d;
-        int st_k = DLSA_PART_EMPTY, iters = 0;
-        double ll = 0.0;
-        if (nk > 0) {
-            rc = pois_gather_rows(y, nullptr, part_first_host[k], row_step, nk, ybuf, nullptr, yk, none, s);
-            if (rc) return rc;
-            const double* cst = counts.data() + (size_t)k * MN_NQ;
-            OrdStart start{};
-            double cum = 0.0;
-            for (int j = 0; j < J; ++j) {
-                cum += cst[j];
-                start.a[j] = log(cum / ((double)nk - cum));           // the logit of the cumulative class share
-            }
-            hipLaunchKernelGGL(ord_start_kernel, dim3((d + 255) / 256), dim3(256), 0, s, st.beta, J, d, start);
-            DLSA_HIP_CHECK(hipGetLastError());
-            const NewtonDevice dev{st, Hk, d, s};
-            NewtonOutcome o;
-            const double* Xk = X + part_first_host[k] * ldx;
-            rc = newton_fit_loop(NEWTON_POISSON, tol, max_iter + 1,
-                                 [&](bool&) {
-                                     return ord_pass_impl(Xk, pitch, yk, st.beta, classes, nk, p, Hk, d, st.g, st.stats + 3, nullptr, wsc, l, s);
-                                 },
-                                 dev, newton_no_hook, o);
-            if (rc) return rc;
-            st_k = o.status; iters = o.n_iter; ll = o.ll;
-        }
-        const int rcf = newton_fit_finish(st_k, iters, ll, st.beta, d, Hk, ck, sk, k, n_iter_host, status_host, loglik_host, overall, s);
-        if (rcf) return rcf;
-    }
-    DLSA_HIP_CHECK(hipStreamSynchronize(s));
-    return overall;
+    auto eval = [=](int k, const double* yk, int64_t nk, const double* theta, double* Hk, double* g, double* ll) {
+        return ord_pass_impl(X + part_first_host[k] * ldx, pitch, yk, theta, classes, nk, p, Hk, d, g, ll, nullptr, wsc, l, s);
+    };
+    return ord_fit_core("ordinal_fit", y, part_first_host, part_rows_host, row_step, K, p, classes, tol, max_iter, coef, Sig_inv,
+                        Sig_invMcoef, n_iter_host, status_host, loglik_host, b, eval, s);
 }
 
 }  // extern "C"

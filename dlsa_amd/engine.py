@@ -1536,6 +1536,44 @@ def onehot_multinomial_fit_ex(plan, num, codes, y, part_first, part_rows, row_st
     return out.result(rc)
 
 
+def onehot_ordinal_pass(plan, num, codes, y, theta, classes, want_H=True, want_w=False):
+    """ordinal_pass on the raw representation of a one-hot design (dlsa_onehot_ordinal_pass_f64, include/dlsa_hip_onehot_ordinal.h):
+    rows as onehot_poisson_pass, y and `classes` as ordinal_pass.  The plan must have no constant column -- the cutpoints are the
+    intercepts.  theta [J + plan.p] = [alpha_1 .. alpha_J | beta], beta in the plan's column order.  Returns (H [d, d] or None, g [d],
+    loglik [1] -- NaN when the cutpoints are not strictly increasing or a response is no class code --, w [n] or None) of the matrix
+    dlsa_design_f64 would build -- which is never built."""
+    lib = _lib.load()
+    _require_gpu(theta)
+    _f64(theta, "theta")
+    n = _oh_poisson_rows(plan, num, codes, y, None, "onehot_ordinal_pass")
+    classes = ordinal_classes("onehot_ordinal_pass", classes, plan.p)
+    d = classes - 1 + plan.p
+    if n < 1 or theta.numel() != d:
+        raise ValueError("onehot_ordinal_pass: need n >= 1 rows and theta with %d elements" % d)
+    H, g, ll, w = _pass_out(d, n, y.device, want_H, want_w)
+    ws = _workspace(lib.dlsa_onehot_ordinal_workspace_bytes(plan._h, n, classes, 1), y.device)
+    check(lib.dlsa_onehot_ordinal_pass_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), _ptr(theta), classes, n, _ptr(H), d, _ptr(g),
+                                           _ptr(ll), _ptr(w), _ptr(ws), ws.numel(), _stream()))
+    return H, g, ll, w
+
+
+def onehot_ordinal_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1, classes=None, tol=1e-13, max_iter=100):
+    """ordinal_fit_ex on the raw representation of a one-hot design (dlsa_onehot_ordinal_fit_f64): partitions as
+    onehot_poisson_fit_ex, `classes` (2 .. 8, required) and the refusals as ordinal_fit_ex; a plan with a constant column is refused.
+    Same result dict as ordinal_fit_ex with J + plan.p columns, cutpoints first, then the plan's column order."""
+    lib = _lib.load()
+    n = _oh_poisson_rows(plan, num, codes, y, None, "onehot_ordinal_fit_ex")
+    if classes is None:
+        raise ValueError("onehot_ordinal_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
+    classes = ordinal_classes("onehot_ordinal_fit_ex", classes, plan.p)
+    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_ordinal_fit_ex", part_first, part_rows, row_step, n)
+    out = _FitOut(K, classes - 1 + plan.p, y.device)
+    ws = _workspace(lib.dlsa_onehot_ordinal_workspace_bytes(plan._h, max_rows, classes, step), y.device)
+    rc = lib.dlsa_onehot_ordinal_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), c_first, c_rows, step, K, classes, tol, max_iter,
+                                         *out.args, _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
+
+
 class RcclComm:
     """An RCCL communicator opened through the C ABI (dlsa_comm_unique_id / dlsa_comm_init_rank), for hosts that do not
     use torch.distributed: rank 0 creates `RcclComm.unique_id()`, ships the 128 bytes to the other ranks out of band, every

@@ -1313,6 +1313,24 @@ def fit_ordinal_partitions(X, y, classes, partition_num=None, part_offsets=None,
     return _blocks(r, names, n)
 
 
+def fit_ordinal_design(num, codes, y, spec, classes, partition_num=None, part_offsets=None, structured=True, tol=1e-13, max_iter=100):
+    """Ordinal (proportional-odds) map step for a design given by its RAW columns, the sibling of fit_multinomial_design: num [n, q]
+    fp64, codes [n, f] int32 level codes (DesignSpec.encode) and the class codes y [n] (0 .. classes - 1, lowest first), all on the
+    GPU.  The spec must have NO constant column (ValueError otherwise): the cutpoints are the intercepts.  With structured=True and a
+    qualifying design (spec.onehot_plan()) the fit runs on the raw representation -- the dense [n, p] matrix is never built;
+    otherwise the matrix is built once by the design kernel and the dense ordinal fit runs on it.  Partitions as
+    fit_poisson_partitions; every partition with rows must hold every class.  Same MappedBlocks either way over the (classes - 1) + p
+    coefficients ordinal_column_names(spec.names, classes)."""
+    _require_raw_rows("fit_ordinal_design", num, y)
+    if any(int(k) == 0 for k in spec.kind):
+        raise ValueError("fit_ordinal_design: the design has a constant column; the cutpoints are the intercepts of an ordinal "
+                         "model, so build the spec with fit_intercept=False")
+    y = y.to(torch.float64).contiguous()
+    classes = engine.ordinal_classes("fit_ordinal_design", classes, len(spec.names))
+    return _fit_design(engine.onehot_ordinal_fit_ex, engine.ordinal_fit_ex, num, codes, y, spec, partition_num, part_offsets,
+                       structured, names=ordinal_column_names(spec.names, classes), classes=classes, tol=tol, max_iter=max_iter)
+
+
 def _ordinal_frame(who, sample_df, Y_name, classes, dummy_info, dummy_factors_baseline, data_info, for_eval=False):
     """(X device design without a ones column or None, its p names, the class codes on the device, C) of one chunk whose response
     column holds the labels `classes`, lowest first."""
@@ -1321,12 +1339,26 @@ def _ordinal_frame(who, sample_df, Y_name, classes, dummy_info, dummy_factors_ba
     return Xd, list(names), _to_device(frame, Y_name), C
 
 
-def ordinal_model(sample_df, Y_name, classes, dummy_info=[], dummy_factors_baseline=[], data_info=[], tol=1e-13, max_iter=100):
+def ordinal_model(sample_df, Y_name, classes, dummy_info=[], dummy_factors_baseline=[], data_info=[], tol=1e-13, max_iter=100,
+                  structured=False):
     """Frame-level sibling of multinomial_model for an ORDERED response: one partition (a pandas frame) whose column Y_name holds the
     labels listed in `classes`, lowest first.  `classes` is required: a partition cannot discover the classes it lacks.  There is no
     fit_intercept: the J cutpoints are the intercepts.  Returns the stacked (J + p) x (3 + J + p) frame `par_id, coef, Sig_invMcoef,
     intercept:1 .. intercept:J, <name> ...`; a chunk that lacks an expected dummy level returns the all-zero block with a warning.
-    The dense path only (the design matrix is built by the design kernel)."""
+    structured=True with a dummy_info and a qualifying design fits on the raw numerics + level codes (fit_ordinal_design; the dense
+    one-hot matrix is never built, the missing-level check runs on the codes); the default is the dense path (the design matrix is
+    built by the design kernel)."""
+    if structured and len(dummy_info) > 0:
+        frame, C = _multinomial_codes_frame("ordinal_model", sample_df, Y_name, classes)
+        spec, plan, codes, unknown, yd, _, _ = _count_raw_frame(frame, Y_name, False, None, None, dummy_info, dummy_factors_baseline,
+                                                                data_info)
+        if plan is not None:
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                _warn_missing_levels(missing, len(sample_df), spec.names, False, skip=True)
+                return _zero_block(ordinal_column_names(spec.names, C))
+            mb = fit_ordinal_design(spec.numeric_to_device(frame), torch.from_numpy(codes).cuda(), yd, spec, C, tol=tol, max_iter=max_iter)
+            return _first_block_frame(mb, "ordinal_model")
     Xd, names, yd, C = _ordinal_frame("ordinal_model", sample_df, Y_name, classes, dummy_info, dummy_factors_baseline, data_info)
     if Xd is None:
         return _zero_block(ordinal_column_names(names, C))
@@ -1334,13 +1366,28 @@ def ordinal_model(sample_df, Y_name, classes, dummy_info=[], dummy_factors_basel
     return _first_block_frame(mb, "ordinal_model")
 
 
-def ordinal_model_eval(sample_df, Y_name, par, classes, dummy_info=[], dummy_factors_baseline=[], data_info=[]):
+def ordinal_model_eval(sample_df, Y_name, par, classes, dummy_info=[], dummy_factors_baseline=[], data_info=[], structured=False):
     """Log-likelihood (sum log P(y)) of every estimator column of `par` (J + p rows, cutpoints first) on one partition, shaped like
-    logistic_model_eval's output: one row, a column per estimator (one pass without the information per column)."""
-    Xd, _, yd, C = _ordinal_frame("ordinal_model_eval", sample_df, Y_name, classes, dummy_info, dummy_factors_baseline, data_info,
-                                  for_eval=True)
-    X = engine.row_major(Xd)
+    logistic_model_eval's output: one row, a column per estimator (one pass without the information per column).  structured=True
+    with a dummy_info and a qualifying design runs the passes on the raw numerics + level codes."""
+    run = None
+    if structured and len(dummy_info) > 0:
+        frame, C = _multinomial_codes_frame("ordinal_model_eval", sample_df, Y_name, classes)
+        spec, plan, codes, unknown, yd, _, _ = _count_raw_frame(frame, Y_name, False, None, None, dummy_info, dummy_factors_baseline,
+                                                                data_info)
+        if plan is not None:
+            missing = spec.missing_levels(codes)
+            if missing or unknown:
+                _warn_missing_levels(missing, len(sample_df), spec.names, False, skip=False)
+            num, cd = spec.numeric_to_device(frame), torch.from_numpy(codes).cuda()
 
-    def run(b):
-        return engine.ordinal_pass(X, yd, b, C, want_H=False)
+            def run(b):
+                return engine.onehot_ordinal_pass(plan, num, cd, yd, b, C, want_H=False)
+    if run is None:
+        Xd, _, yd, C = _ordinal_frame("ordinal_model_eval", sample_df, Y_name, classes, dummy_info, dummy_factors_baseline, data_info,
+                                      for_eval=True)
+        X = engine.row_major(Xd)
+
+        def run(b):
+            return engine.ordinal_pass(X, yd, b, C, want_H=False)
     return _loglik_frame(par, run)
