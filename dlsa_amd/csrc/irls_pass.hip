@@ -372,7 +372,8 @@ __global__ __launch_bounds__(256, (!HESS ? fp_logit_wgs(NT + (G > 0 ? 1 : 0)) : 
 
     LogitState<NTC> L;
     // The pieces below are the operations of logistic.h (exp_neg, logistic_terms) in the same order on the same values -- w and mu
-    // come out to the last bit as logit.hip's pass gives them -- written so that every step is ONE VALU instruction: next to fp64
+    // come out to the last bit as logit.hip's pass gives them (held to it for every variant over the whole range of eta, subnormal
+    // weights included: tests/test_gpu_logistic_terms.py) -- written so that every step is ONE VALU instruction: next to fp64
     // MFMAs each VALU instruction, a move included, costs ~4.7 cycles of the matrix pipe and each separate group of them ~11 more
     // (bench/ubench_gap.hip), so coefficients are scalar operands (fp_fma_sc), selects pick one dword, and the pieces form few groups.
     // piece 0: the row's columns and its label out of LDS (chunk `chunk` in stage `buf`)
