@@ -6,12 +6,7 @@
 // Included inside namespace dlsa after rowdot.h (merged_reduce, row_of_lane, rep_mask, rank1_update) and poisson_exp.h
 // (exp_full), with poisson_internal.h above it; the library is built without relocatable device code, so the kernel is
 // instantiated in the file that launches it.
-
-typedef double count_d2v __attribute__((ext_vector_type(2)));
-
-constexpr int COUNT_THREADS = 256;
-constexpr int COUNT_WAVES = COUNT_THREADS / 64;
-constexpr int COUNT_MAX_BLOCKS = 2048;
+#include "row_pass.h"     // the batch load, the batch loop, the block reduction, the shapes and the dispatcher
 
 template <class M>
 struct CountArgs {
@@ -33,62 +28,37 @@ struct CountArgs {
     M m;
 };
 
-static __device__ __forceinline__ double2 count_ld2(const double* ptr) {
-    const count_d2v t = __builtin_nontemporal_load(reinterpret_cast<const count_d2v*>(ptr));
-    double2 r; r.x = t.x; r.y = t.y; return r;
-}
+struct CountRowIn { double y, off; };      // the lane's own row's count and offset: they travel with the batch
 
-// The logit pass's skeleton (logit.hip logit_kernel) with the model's terms: branch-free clamped loads, the lane's own row's
-// count and offset travel with the batch, a second register set prefetches the next batch at NC = 1.
+// The skeleton of row_pass.h with the model's terms.  Accumulator sets: g, then (BORDER) h = X'w; scalars: ll, s0, then sw.
 template <class M, int NC, int RB, bool VEC, bool OFF, bool BORDER>
 __global__ __launch_bounds__(COUNT_THREADS) void count_pass_kernel(CountArgs<M> a) {
-    __shared__ double red[NC * 128 + 2];
-    __shared__ double redh[BORDER ? NC * 128 + 1 : 1];
+    constexpr int SETS = BORDER ? 2 : 1, W = NC * 128;
+    __shared__ double red[SETS * W + 2 + (BORDER ? 1 : 0)];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const double b0 = a.beta0 ? *a.beta0 : 0.0;
     const M m = a.m;
     double s0 = 0.0, sw = 0.0, ll = 0.0;
-    double2 b[NC], g[NC], h[BORDER ? NC : 1];
+    double2 b[NC], g[SETS][NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int col = c * 128 + 2 * lane;
         b[c].x = col < a.p ? a.beta[col] : 0.0;
         b[c].y = col + 1 < a.p ? a.beta[col + 1] : 0.0;
-        g[c].x = 0.0; g[c].y = 0.0;
-        if constexpr (BORDER) { h[c].x = 0.0; h[c].y = 0.0; }
+#pragma unroll
+        for (int k = 0; k < SETS; ++k) { g[k][c].x = 0.0; g[k][c].y = 0.0; }
     }
     const int myrow = row_of_lane<RB>(lane);
     const bool rep = (lane & rep_mask<RB>()) == 0;
-    const int64_t nbatch = (a.n + RB - 1) / RB;
-    const int64_t stride = (int64_t)gridDim.x * COUNT_WAVES;
 
-    auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], double& yv, double& ov) {
-        const int64_t row0 = bt * RB;
-        const int64_t ry = min(row0 + myrow, a.n - 1);
-        const double ytmp = a.y[ry];
-        const double otmp = OFF ? a.off[ry] : 0.0;
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            const int64_t r = min(row0 + i, a.n - 1);
-            const double* rowp = a.X + r * a.ldx;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int col = c * 128 + 2 * lane;
-                const int c0 = col < a.p ? col : 0;                   // clamped columns meet beta = 0
-                if (VEC) {                                            // VEC implies p even: a pair never straddles p
-                    x[i][c] = count_ld2(rowp + c0);
-                } else {
-                    x[i][c].x = __builtin_nontemporal_load(rowp + c0);
-                    x[i][c].y = __builtin_nontemporal_load(rowp + (col + 1 < a.p ? col + 1 : 0));
-                }
-            }
-        }
-        yv = ytmp;
-        ov = otmp;
+    auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], CountRowIn& in) {
+        const int64_t ry = row_pass_load<NC, RB, VEC>(a.X, a.ldx, a.n, a.p, bt, lane, myrow, x);
+        in.y = a.y[ry];
+        in.off = OFF ? a.off[ry] : 0.0;
     };
-    auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const double yraw, const double oraw) {
+    auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const CountRowIn& in) {
         const int64_t row0 = bt * RB;
         double dot[RB];
 #pragma unroll
@@ -100,8 +70,8 @@ __global__ __launch_bounds__(COUNT_THREADS) void count_pass_kernel(CountArgs<M> 
         }
         const int64_t r = row0 + myrow;
         const bool valid = r < a.n;
-        const double yv = valid ? yraw : 0.0;
-        const double eta = merged_reduce<RB>(dot, lane) + b0 + (OFF ? oraw : 0.0);
+        const double yv = valid ? in.y : 0.0;
+        const double eta = merged_reduce<RB>(dot, lane) + b0 + (OFF ? in.off : 0.0);
         const double mu = exp_full(eta);
         double wgt, rs, llt;
         m.terms(yv, eta, mu, wgt, rs, llt);
@@ -112,88 +82,57 @@ __global__ __launch_bounds__(COUNT_THREADS) void count_pass_kernel(CountArgs<M> 
             ll += llt;
             s0 += resid;
         }
-        rank1_update<RB, NC, 0>(resid, x, g);
+        rank1_update<RB, NC, 0>(resid, x, g[0]);
         if constexpr (BORDER) {                 // X'w and sum w of the same rows (a clamped row past n weighs nothing)
             const double wv = valid ? wgt : 0.0;
             if (rep) sw += wv;
-            rank1_update<RB, NC, 0>(wv, x, h);
+            rank1_update<RB, NC, 0>(wv, x, g[1]);
         }
     };
 
+    // The batch loop of row_pass_stream (row_pass.h), kept as this kernel's own text: on the shared template the NC = 1 instantiations
+    // without BORDER take 2 VGPRs more (one 64-bit value moves out of the SGPRs), and <TweedieRow, 1, 8, true, true, false>
+    // loses its fourth wave over them (130 VGPRs for 128).
+    const int64_t nbatch = (a.n + RB - 1) / RB;
+    const int64_t stride = (int64_t)gridDim.x * COUNT_WAVES;
     int64_t bt = (int64_t)blockIdx.x * COUNT_WAVES + wave;
     if constexpr (NC == 1) {
         double2 xa[RB][NC], xb[RB][NC];
-        double ya = 0.0, yb = 0.0, oa = 0.0, ob = 0.0;
+        CountRowIn ia{}, ib{};
         if (a.n > 0) {
-            load_batch(bt, xa, ya, oa);
+            load_batch(bt, xa, ia);
             for (; bt < nbatch; bt += 2 * stride) {
                 const int64_t b1 = bt + stride, b2 = bt + 2 * stride;
-                load_batch(b1, xb, yb, ob);
-                process(bt, xa, ya, oa);
-                load_batch(b2, xa, ya, oa);
-                if (b1 < nbatch) process(b1, xb, yb, ob);
+                load_batch(b1, xb, ib);
+                process(bt, xa, ia);
+                load_batch(b2, xa, ia);
+                if (b1 < nbatch) process(b1, xb, ib);
             }
         }
     } else {
         for (; bt < nbatch; bt += stride) {
             double2 x[RB][NC];
-            double yv, ov;
-            load_batch(bt, x, yv, ov);
-            process(bt, x, yv, ov);
+            CountRowIn in;
+            load_batch(bt, x, in);
+            process(bt, x, in);
         }
     }
 
-    // block reduction: waves add into LDS one after another (fixed order)
-    ll = wave_allreduce_sum(ll);
-    s0 = wave_allreduce_sum(s0);
-    if constexpr (BORDER) sw = wave_allreduce_sum(sw);
-    for (int wv = 0; wv < COUNT_WAVES; ++wv) {
-        if (wave == wv) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                double* dst = red + c * 128 + 2 * lane;
-                if (wv == 0) { dst[0] = g[c].x; dst[1] = g[c].y; }
-                else { dst[0] += g[c].x; dst[1] += g[c].y; }
-                if constexpr (BORDER) {
-                    double* dh = redh + c * 128 + 2 * lane;
-                    if (wv == 0) { dh[0] = h[c].x; dh[1] = h[c].y; }
-                    else { dh[0] += h[c].x; dh[1] += h[c].y; }
-                }
-            }
-            if (lane == 0) {
-                if (wv == 0) { red[NC * 128] = ll; red[NC * 128 + 1] = s0; }
-                else { red[NC * 128] += ll; red[NC * 128 + 1] += s0; }
-                if constexpr (BORDER) { if (wv == 0) redh[NC * 128] = sw; else redh[NC * 128] += sw; }
-            }
-        }
-        __syncthreads();
-    }
-    double* gp = a.gpart + (int64_t)blockIdx.x * (NC * 128);
-    for (int col = tid; col < NC * 128; col += COUNT_THREADS) gp[col] = red[col];
-    if (tid == 0) { a.llpart[blockIdx.x] = red[NC * 128]; a.s0part[blockIdx.x] = red[NC * 128 + 1]; }
+    double sc[2 + (BORDER ? 1 : 0)];
+    sc[0] = ll; sc[1] = s0;
+    if constexpr (BORDER) sc[2] = sw;
+    row_pass_reduce(g, sc, red, lane, wave);
+    double* gp = a.gpart + (int64_t)blockIdx.x * W;
+    for (int col = tid; col < W; col += COUNT_THREADS) gp[col] = red[col];
+    if (tid == 0) { a.llpart[blockIdx.x] = red[SETS * W]; a.s0part[blockIdx.x] = red[SETS * W + 1]; }
     if constexpr (BORDER) {
-        double* hp = a.hpart + (int64_t)blockIdx.x * (NC * 128);
-        for (int col = tid; col < NC * 128; col += COUNT_THREADS) hp[col] = redh[col];
-        if (tid == 0) a.swpart[blockIdx.x] = redh[NC * 128];
+        double* hp = a.hpart + (int64_t)blockIdx.x * W;
+        for (int col = tid; col < W; col += COUNT_THREADS) hp[col] = red[W + col];
+        if (tid == 0) a.swpart[blockIdx.x] = red[SETS * W + 2];
     }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static int count_nc(int p) {
-    const int chunks = (p + 127) / 128;
-    int nc = 1;
-    while (nc < chunks) nc *= 2;
-    return nc;
-}
-
-static int count_rb(int nc) { return nc <= 2 ? 8 : nc == 4 ? 4 : nc == 8 ? 2 : 1; }
-
-static int count_blocks(int64_t n, int rb) {
-    const int64_t nbatch = (n + rb - 1) / rb;
-    int64_t blocks = (nbatch + COUNT_WAVES * 4 - 1) / (COUNT_WAVES * 4);   // >= 4 batches per wave
-    return (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), COUNT_MAX_BLOCKS);
-}
-
 // The pass's scratch: the per-block partials and the Hessian's border.  A workspace layout takes the six through
 // count_scratch_take (one order, one alignment) and hands the pass the pointers of count_scratch_at.
 template <class T>
@@ -248,15 +187,9 @@ static int count_pass(const M& m, const double* X, int64_t ldx, const double* y,
     a.X = X; a.y = y; a.off = off; a.beta = intercept ? beta + 1 : beta; a.beta0 = intercept ? beta : nullptr;
     a.w_out = w; a.mu_out = mu; a.ldx = ldx; a.n = n; a.p = p; a.m = m;
     a.gpart = sc.gpart; a.llpart = sc.llpart; a.s0part = sc.s0part; a.hpart = sc.hpart; a.swpart = sc.swpart;
-    const bool vec = (ldx % 2 == 0) && (p % 2 == 0) && (((uintptr_t)X & 15) == 0);
+    const bool vec = row_pass_vec(X, ldx, p);
     const int blocks = count_blocks(n, rb);
-    switch (nc) {
-        case 1: count_launch<M, 1, 8>(a, vec, border, blocks, s); break;
-        case 2: count_launch<M, 2, 8>(a, vec, border, blocks, s); break;
-        case 4: count_launch<M, 4, 4>(a, vec, border, blocks, s); break;
-        case 8: count_launch<M, 8, 2>(a, vec, border, blocks, s); break;
-        default: count_launch<M, 16, 1>(a, vec, border, blocks, s); break;
-    }
+    row_pass_dispatch(nc, [&](auto sh) { count_launch<M, decltype(sh)::NC, decltype(sh)::RB>(a, vec, border, blocks, s); });
     DLSA_HIP_CHECK(hipGetLastError());
     if (g || loglik) {
         logit_finish_launch(a.gpart, a.llpart, blocks, nc * 128, p, (g && intercept) ? g + 1 : g, loglik, s,

@@ -15,7 +15,7 @@
 // keeps its relative accuracy when one class dominates.
 //
 // Launches per evaluation (every partial combines in a fixed order: no float atomics, no waits between workgroups):
-//   1 mn_pass_kernel        one read of the rows in the count pass's layout (count_pass.h, rowdot.h: lane l holds the columns
+//   1 mn_pass_kernel        one read of the rows on the dense row-pass skeleton (row_pass.h, rowdot.h: lane l holds the columns
 //                           128c + 2l + {0,1}, RB rows per wave and batch, branch-free clamped non-temporal loads): J dot products
 //                           per row (one merged butterfly each), the softmax on the lanes of the row, J residuals broadcast into J
 //                           accumulator sets; P (when wanted), per-block partials of g, of the J intercept entries and of loglik.
@@ -37,7 +37,7 @@
 namespace dlsa {
 
 #include "rowdot.h"       // merged_reduce, row_of_lane, rep_mask, rank1_update
-#include "count_pass.h"   // count_ld2, count_nc, count_rb, count_blocks, COUNT_*
+#include "row_pass.h"     // the batch load, loop and block reduction, count_nc, count_rb, count_blocks, COUNT_*, the dispatcher
 
 struct MnArgs {
     const double* X;
@@ -51,7 +51,7 @@ struct MnArgs {
     int p, icpt;
 };
 
-// The count pass's skeleton (count_pass.h count_pass_kernel) with J linear predictors per row.
+// The skeleton of row_pass.h with J linear predictors per row.
 template <int J, int NC, int RB, bool VEC>
 __global__ __launch_bounds__(COUNT_THREADS) void mn_pass_kernel(MnArgs a) {
     constexpr int W = NC * 128;                     // padded columns of one class block
@@ -66,6 +66,7 @@ __global__ __launch_bounds__(COUNT_THREADS) void mn_pass_kernel(MnArgs a) {
     }
     double b0[J], s0[J];
     double2 g[J][NC];
+    double ll = 0.0;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         b0[j] = a.icpt ? a.theta[j * pe] : 0.0;
@@ -73,34 +74,12 @@ __global__ __launch_bounds__(COUNT_THREADS) void mn_pass_kernel(MnArgs a) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) { g[j][c].x = 0.0; g[j][c].y = 0.0; }
     }
-    double ll = 0.0;
     __syncthreads();
     const int myrow = row_of_lane<RB>(lane);
     const bool rep = (lane & rep_mask<RB>()) == 0;
-    const int64_t nbatch = (a.n + RB - 1) / RB;
-    const int64_t stride = (int64_t)gridDim.x * COUNT_WAVES;
 
     auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], double& yv) {
-        const int64_t row0 = bt * RB;
-        const int64_t ry = min(row0 + myrow, a.n - 1);
-        const double ytmp = a.y[ry];
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            const int64_t r = min(row0 + i, a.n - 1);
-            const double* rowp = a.X + r * a.ldx;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int col = c * 128 + 2 * lane;
-                const int c0 = col < a.p ? col : 0;
-                if (VEC) {                                            // VEC implies p even: a pair never straddles p
-                    x[i][c] = count_ld2(rowp + c0);
-                } else {
-                    x[i][c].x = __builtin_nontemporal_load(rowp + c0);
-                    x[i][c].y = __builtin_nontemporal_load(rowp + (col + 1 < a.p ? col + 1 : 0));
-                }
-            }
-        }
-        yv = ytmp;
+        yv = a.y[row_pass_load<NC, RB, VEC>(a.X, a.ldx, a.n, a.p, bt, lane, myrow, x)];
     };
     auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const double yraw) {
         const int64_t r = bt * RB + myrow;
@@ -136,55 +115,14 @@ __global__ __launch_bounds__(COUNT_THREADS) void mn_pass_kernel(MnArgs a) {
         }
     };
 
-    int64_t bt = (int64_t)blockIdx.x * COUNT_WAVES + wave;
-    if constexpr (NC == 1) {
-        double2 xa[RB][NC], xb[RB][NC];
-        double ya = 0.0, yb = 0.0;
-        if (a.n > 0) {
-            load_batch(bt, xa, ya);
-            for (; bt < nbatch; bt += 2 * stride) {
-                const int64_t b1 = bt + stride, b2 = bt + 2 * stride;
-                load_batch(b1, xb, yb);
-                process(bt, xa, ya);
-                load_batch(b2, xa, ya);
-                if (b1 < nbatch) process(b1, xb, yb);
-            }
-        }
-    } else {
-        for (; bt < nbatch; bt += stride) {
-            double2 x[RB][NC];
-            double yv;
-            load_batch(bt, x, yv);
-            process(bt, x, yv);
-        }
-    }
+    row_pass_stream<NC, RB, double>(a.n, wave, load_batch, process);
 
-    // block reduction: waves add into LDS one after another (fixed order); the coefficients are no longer read
-    ll = wave_allreduce_sum(ll);
+    __syncthreads();                                // the coefficients are no longer read: their LDS takes the block reduction
+    double sc[1 + J];
+    sc[0] = ll;
 #pragma unroll
-    for (int j = 0; j < J; ++j) s0[j] = wave_allreduce_sum(s0[j]);
-    __syncthreads();
-    for (int wv = 0; wv < COUNT_WAVES; ++wv) {
-        if (wave == wv) {
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    double* dst = sh + j * W + c * 128 + 2 * lane;
-                    if (wv == 0) { dst[0] = g[j][c].x; dst[1] = g[j][c].y; }
-                    else { dst[0] += g[j][c].x; dst[1] += g[j][c].y; }
-                }
-            }
-            if (lane == 0) {
-                if (wv == 0) sh[J * W] = ll; else sh[J * W] += ll;
-#pragma unroll
-                for (int j = 0; j < J; ++j) {
-                    if (wv == 0) sh[J * W + 1 + j] = s0[j]; else sh[J * W + 1 + j] += s0[j];
-                }
-            }
-        }
-        __syncthreads();
-    }
+    for (int j = 0; j < J; ++j) sc[1 + j] = s0[j];
+    row_pass_reduce(g, sc, sh, lane, wave);
     double* gp = a.gpart + (int64_t)blockIdx.x * (J * W);
     for (int col = tid; col < J * W; col += COUNT_THREADS) gp[col] = sh[col];
     if (tid == 0) a.llpart[blockIdx.x] = sh[J * W];
@@ -253,24 +191,20 @@ __global__ void mn_mirror_kernel(double* __restrict__ H, int64_t ldh, int J, int
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-template <int J, int NC>
-static int mn_launch_nc(const MnArgs& a, bool vec, int blocks, hipStream_t s) {
-    constexpr int RB = NC <= 2 ? 8 : NC == 4 ? 4 : NC == 8 ? 2 : 1;          // count_rb
-    if (vec) hipLaunchKernelGGL((mn_pass_kernel<J, NC, RB, true>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((mn_pass_kernel<J, NC, RB, false>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
-    return DLSA_OK;
-}
-
 // J pe <= 2048 bounds the chunks of a class block: 16 at J = 1, 8 at J <= 3, 4 beyond.  A shape without a kernel is an error.
 template <int J>
 static int mn_launch(const MnArgs& a, int nc, bool vec, int blocks, hipStream_t s) {
-    if (nc == 1) return mn_launch_nc<J, 1>(a, vec, blocks, s);
-    if (nc == 2) return mn_launch_nc<J, 2>(a, vec, blocks, s);
-    if (nc == 4) return mn_launch_nc<J, 4>(a, vec, blocks, s);
-    if constexpr (J <= 3) { if (nc == 8) return mn_launch_nc<J, 8>(a, vec, blocks, s); }
-    if constexpr (J == 1) { if (nc == 16) return mn_launch_nc<J, 16>(a, vec, blocks, s); }
-    set_error("multinomial: no row kernel for %d classes and %d column chunks", J + 1, nc);
-    return DLSA_ERR_INVALID;
+    return row_pass_dispatch(nc, [&](auto sh) {
+        constexpr int NC = decltype(sh)::NC, RB = decltype(sh)::RB;
+        if constexpr (NC <= 4 || (NC == 8 && J <= 3) || (NC == 16 && J == 1)) {
+            if (vec) hipLaunchKernelGGL((mn_pass_kernel<J, NC, RB, true>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
+            else hipLaunchKernelGGL((mn_pass_kernel<J, NC, RB, false>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
+            return (int)DLSA_OK;
+        } else {
+            set_error("multinomial: no row kernel for %d classes and %d column chunks", J + 1, nc);
+            return (int)DLSA_ERR_INVALID;
+        }
+    });
 }
 
 struct MnLayout {
@@ -344,7 +278,7 @@ static int mn_pass_impl(const double* X, int64_t ldx, const double* y, const dou
     MnArgs a{};
     a.X = X; a.y = y; a.theta = theta; a.prob = prob; a.ldx = ldx; a.n = n; a.ldprob = ldprob; a.p = p; a.icpt = icpt;
     a.gpart = (double*)(ws + l.off_gpart); a.llpart = (double*)(ws + l.off_llpart); a.s0part = (double*)(ws + l.off_s0part);
-    const bool vec = (ldx % 2 == 0) && (p % 2 == 0) && (((uintptr_t)X & 15) == 0);
+    const bool vec = row_pass_vec(X, ldx, p);
     const int blocks = count_blocks(n, rb);
     int rc;
     switch (J) {
@@ -462,8 +396,8 @@ int dlsa_multinomial_fit_f64(const double* X, int64_t ldx, const double* y, cons
         return mn_pass_impl(X + part_first_host[k] * ldx, pitch, yk, theta, classes, nk, p, intercept, Hk, d, g, ll,
                             (double*)(wsc + l.off_prob), l.ldprob, wsc, l, s);
     };
-    return mn_fit_core("multinomial_fit", y, part_first_host, part_rows_host, row_step, K, pe, icpt ? 0 : -1, classes, tol, max_iter, coef, Sig_inv,
-                       Sig_invMcoef, n_iter_host, status_host, loglik_host, b, eval, s);
+    return mn_fit_core("multinomial_fit", MN_NO_CLASS, y, part_first_host, part_rows_host, row_step, K, d, classes, tol, max_iter, coef, Sig_inv,
+                       Sig_invMcoef, n_iter_host, status_host, loglik_host, b, mn_null_start(J, pe, icpt ? 0 : -1), eval, s);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // What is the multinomial family's among the things its two translation units (multinomial.hip: the dense rows,
 // onehot_multinomial.hip: the raw representation of a one-hot design) share: the limits, the softmax of one row, the host launchers
 // of the once-per-partition check and of the weight, mirror, start and log-likelihood-fix kernels, and the per-partition fit driver
-// that takes the evaluation as a callable.  The kernels are multinomial.hip's: the library is built without relocatable device code,
+// of every family whose response is a class code (the ordinal family's too), which takes the start and the evaluation as callables.  The kernels are multinomial.hip's: the library is built without relocatable device code,
 // so the other unit reaches them through these host functions.  The gather of a strided partition's responses is
 // poisson_internal.h's, the Newton state, loop and epilogue newton_fit.h's.
 #pragma once
@@ -76,17 +76,17 @@ struct MnFitBufs {
     NewtonState st;
 };
 
-// The per-partition driver of the multinomial fits, beside pois_fit_core: the data check of EVERY partition first (a partition
-// that lacks a class has no finite MLE, and the blocks of different partitions must mean the same parameter), then per partition
-// the start at theta = 0 with entry icpt_col (-1: none) of class block j at log(n_j / n_0), newton_fit_loop with the policy
-// NEWTON_POISSON on J pe coefficients and newton_fit_finish.  eval(k, yk, nk, theta, H, g, ll) is the only part that knows the
-// representation of the design.
-template <class Eval>
-static int mn_fit_core(const char* who, const double* y, const int64_t* part_first_host, const int64_t* part_rows_host, int64_t row_step,
-                       int K, int pe, int icpt_col, int classes, double tol, int max_iter, double* coef, double* Sig_inv,
-                       double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, const MnFitBufs& b, Eval&& eval,
-                       hipStream_t s) {
-    const int J = classes - 1, d = J * pe;
+// The per-partition fit driver of the families whose response is a class code (multinomial, ordinal; dense and structured), beside
+// pois_fit_core: the data check of EVERY partition first (a partition that lacks a class has no finite MLE -- `no_class` ends the
+// refusal in the family's words -- and the blocks of different partitions must mean the same parameter), then per partition the
+// family's start, newton_fit_loop with the policy NEWTON_POISSON on d coefficients and newton_fit_finish.
+//   start(cst, nk, theta, s)                   theta = the null model's MLE from the class counts cst[0 .. classes - 1] of the nk rows
+//   eval(k, yk, nk, theta, H, g, ll)           the only part that knows the representation of the design
+template <class Start, class Eval>
+static int mn_fit_core(const char* who, const char* no_class, const double* y, const int64_t* part_first_host, const int64_t* part_rows_host,
+                       int64_t row_step, int K, int d, int classes, double tol, int max_iter, double* coef, double* Sig_inv,
+                       double* Sig_invMcoef, int* n_iter_host, int* status_host, double* loglik_host, const MnFitBufs& b, Start&& start,
+                       Eval&& eval, hipStream_t s) {
     std::vector<double> counts((size_t)K * MN_NQ, 0.0);
     const double* yk = nullptr;
     const double* none = nullptr;
@@ -106,7 +106,7 @@ static int mn_fit_core(const char* who, const double* y, const int64_t* part_fir
         }
         for (int c = 0; c < classes; ++c) {
             if (!(cst[c] > 0.0)) {
-                set_error("%s: partition %d has no row of class %d: its maximum-likelihood fit runs off to eta = -inf", who, k, c);
+                set_error("%s: partition %d has no row of class %d: its maximum-likelihood fit %s", who, k, c, no_class);
                 return DLSA_ERR_INVALID;
             }
         }
@@ -122,10 +122,7 @@ static int mn_fit_core(const char* who, const double* y, const int64_t* part_fir
         if (nk > 0) {
             int rc = pois_gather_rows(y, nullptr, part_first_host[k], row_step, nk, b.ybuf, nullptr, yk, none, s);
             if (rc) return rc;
-            const double* cst = counts.data() + (size_t)k * MN_NQ;
-            MnStart start{};
-            for (int j = 0; j < J; ++j) start.b0[j] = log(cst[j + 1] / cst[0]);
-            rc = mn_start(b.st.beta, J, pe, icpt_col, start, s);
+            rc = start(counts.data() + (size_t)k * MN_NQ, nk, b.st.beta, s);
             if (rc) return rc;
             const NewtonDevice dev{b.st, Hk, d, s};
             NewtonOutcome o;
@@ -139,6 +136,18 @@ static int mn_fit_core(const char* who, const double* y, const int64_t* part_fir
     }
     DLSA_HIP_CHECK(hipStreamSynchronize(s));
     return overall;
+}
+
+constexpr char MN_NO_CLASS[] = "runs off to eta = -inf";       // what a partition without a row of some class does to the fit
+
+// the multinomial fits' start: theta = 0 with entry icpt_col (-1: none) of class block j (pe entries each) at log(n_j / n_0), the
+// exact MLE of the intercept-only model
+static inline auto mn_null_start(int J, int pe, int icpt_col) {
+    return [=](const double* cst, int64_t, double* theta, hipStream_t s) {
+        MnStart start{};
+        for (int j = 0; j < J; ++j) start.b0[j] = log(cst[j + 1] / cst[0]);
+        return mn_start(theta, J, pe, icpt_col, start, s);
+    };
 }
 
 }  // namespace dlsa

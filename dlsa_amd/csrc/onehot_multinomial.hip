@@ -321,8 +321,8 @@ int dlsa_onehot_multinomial_fit_f64(const dlsa_onehot_plan* plan, const double* 
         const int32_t* codesk = codes ? codes + part_first_host[k] * ldc : nullptr;
         return oh_mn_pass_impl(plan, numk, pn, codesk, pc, yk, theta, classes, nk, Hk, d, g, ll, prob, ldprob, wv, ws_oh, oh_bytes, s);
     };
-    return mn_fit_core("onehot_multinomial_fit", y, part_first_host, part_rows_host, row_step, K, p, oh_pois_icpt_col(plan), classes, tol,
-                       max_iter, coef, Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host, b, eval, s);
+    return mn_fit_core("onehot_multinomial_fit", MN_NO_CLASS, y, part_first_host, part_rows_host, row_step, K, d, classes, tol, max_iter, coef,
+                       Sig_inv, Sig_invMcoef, n_iter_host, status_host, loglik_host, b, mn_null_start(J, p, oh_pois_icpt_col(plan)), eval, s);
 }
 
 }  // extern "C"

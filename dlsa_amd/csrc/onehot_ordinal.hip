@@ -81,19 +81,8 @@ __global__ __launch_bounds__(OH_THREADS) void oh_ord_row_kernel(OhDesc ds, const
     double* sg_mine = sg + (threadIdx.x % nrep) * cells;
     for (int c = threadIdx.x; c < ds.nlev_total; c += blockDim.x) scol[c] = level_col[c];
     __syncthreads();
-    // the cutpoints and the class factors: functions of theta alone, once per launch
-    double al[J], E[C], logE[C];
-#pragma unroll
-    for (int j = 0; j < J; ++j) al[j] = sbeta[p + j];
-    bool ordered = true;
-    E[0] = 1.0; logE[0] = 0.0; E[J] = 1.0; logE[J] = 0.0;
-#pragma unroll
-    for (int c = 1; c < J; ++c) {
-        const double gap = al[c] - al[c - 1];
-        ordered = ordered && gap > 0.0;           // (a NaN cutpoint fails too)
-        E[c] = -expm1(-gap);
-        logE[c] = log(E[c]);
-    }
+    double al[J], E[C], logE[C];                  // once per launch
+    const bool ordered = ord_cutpoints<J>(sbeta + p, al, E, logE);
     double gd[SETS][OH_MAXD];                     // the dense columns of the g set and of the border sets
 #pragma unroll
     for (int k = 0; k < SETS; ++k) {
@@ -137,15 +126,11 @@ __global__ __launch_bounds__(OH_THREADS) void oh_ord_row_kernel(OhDesc ds, const
             ll += llt;
         }
         const double r = valid ? resid : 0.0;
-        // cutpoint j + 1 is the upper one of class j and the lower one of class j + 1: selects, no branch on y
         int cls = 0;                               // 0 .. J: bounded whatever y holds
         bool isclass = yv == 0.0;
 #pragma unroll
         for (int j = 0; j < J; ++j) {
-            const bool up = valid && yv == (double)j, lo = valid && yv == (double)(j + 1);
-            sc[j] += (up ? su : 0.0) - (lo ? sl : 0.0);
-            sc[J + j] += (up ? aa + q : 0.0) + (lo ? bb + q : 0.0);
-            if (j < J - 1) sc[2 * J + j] -= lo ? q : 0.0;
+            ord_cutpoint_sums<J>(j, yv, valid, su, sl, aa, bb, q, sc);
             cls += yv == (double)(j + 1) ? j + 1 : 0;
             isclass = isclass || yv == (double)(j + 1);
         }
@@ -198,14 +183,15 @@ __global__ __launch_bounds__(OH_THREADS) void oh_ord_row_kernel(OhDesc ds, const
     // the block's row of scalars in the layout of ordinal_internal.h: [g_alpha | diagonal | off-diagonal], 7 slots each
     double* scrow = a.scpart + (int64_t)blockIdx.x * ORD_SC;
     if (threadIdx.x < ORD_SC) {                     // the slots no sum goes to
-        const int grp = threadIdx.x / ORD_MAX_J, j = threadIdx.x - grp * ORD_MAX_J;
-        if (!(grp < 3 && j < (grp == 2 ? J - 1 : J))) scrow[threadIdx.x] = 0.0;
+        bool used = false;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) used = used || ord_sc_slot<J>(i) == (int)threadIdx.x;
+        if (!used) scrow[threadIdx.x] = 0.0;
     }
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
         const double s = oh_block_sum(sc[i], red);
-        const int slot = i < J ? ORD_SC_GA + i : i < 2 * J ? ORD_SC_DG + (i - J) : ORD_SC_OF + (i - 2 * J);
-        if (threadIdx.x == 0) scrow[slot] = s;
+        if (threadIdx.x == 0) scrow[ord_sc_slot<J>(i)] = s;
     }
     const double sll = oh_block_sum(ll, red);
     __syncthreads();
@@ -415,7 +401,7 @@ int dlsa_onehot_ordinal_fit_f64(const dlsa_onehot_plan* plan, const double* num,
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
-    OrdFitBufs b{};
+    MnFitBufs b{};
     b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
     b.ybuf = (double*)(wsc + l.off_y);
     b.st = newton_state_at(wsc + l.off_state, d);
@@ -425,8 +411,8 @@ int dlsa_onehot_ordinal_fit_f64(const dlsa_onehot_plan* plan, const double* num,
         const int32_t* codesk = codes ? codes + part_first_host[k] * ldc : nullptr;
         return oh_ord_pass_impl(plan, numk, pn, codesk, pc, yk, theta, classes, nk, Hk, d, g, ll, nullptr, wsc, l, s);
     };
-    return ord_fit_core("onehot_ordinal_fit", y, part_first_host, part_rows_host, row_step, K, p, classes, tol, max_iter, coef, Sig_inv,
-                        Sig_invMcoef, n_iter_host, status_host, loglik_host, b, eval, s);
+    return mn_fit_core("onehot_ordinal_fit", ORD_NO_CLASS, y, part_first_host, part_rows_host, row_step, K, d, classes, tol, max_iter, coef, Sig_inv,
+                       Sig_invMcoef, n_iter_host, status_host, loglik_host, b, ord_null_start(classes - 1, d), eval, s);
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 // Cutpoints that are not strictly increasing give loglik = NaN (the launch stays harmless: the terms are selects and arithmetic).
 //
 // Launches per evaluation (every partial combines in a fixed order: no float atomics):
-//   1 ord_pass_kernel       one read of the rows in the count pass's layout (count_pass.h, rowdot.h): one dot product per row, the
+//   1 ord_pass_kernel       one read of the rows on the dense row-pass skeleton (row_pass.h, rowdot.h): one dot product per row, the
 //                           terms above on the lanes of the row, the residual broadcast into the g set and -- BORDER, where the C
 //                           accumulator sets of NC double2 fit (C NC <= 16) -- the row's v entries into the J border sets; w (and,
 //                           without BORDER but with H, A Abar and B Bbar) per row; per-block partials of the sets, of the 3J - 1
@@ -40,7 +40,7 @@
 namespace dlsa {
 
 #include "rowdot.h"       // merged_reduce, row_of_lane, rep_mask, rank1_update
-#include "count_pass.h"   // count_ld2, count_nc, count_rb, count_blocks, COUNT_*
+#include "row_pass.h"     // the batch load, loop and block reduction, count_nc, count_rb, count_blocks, COUNT_*, the dispatcher
 
 struct OrdArgs {
     const double* X;
@@ -56,7 +56,7 @@ struct OrdArgs {
     int p;
 };
 
-// The count pass's skeleton (count_pass.h count_pass_kernel) with the ordinal terms and C accumulator sets.
+// The skeleton of row_pass.h with the ordinal terms and C accumulator sets.
 template <int C, int NC, int RB, bool VEC, bool BORDER>
 __global__ __launch_bounds__(COUNT_THREADS) void ord_pass_kernel(OrdArgs a) {
     constexpr int J = C - 1;
@@ -67,19 +67,8 @@ __global__ __launch_bounds__(COUNT_THREADS) void ord_pass_kernel(OrdArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    // the cutpoints and the class factors: functions of theta alone, the same in every lane
     double al[J], E[C], logE[C];
-#pragma unroll
-    for (int j = 0; j < J; ++j) al[j] = a.theta[j];
-    bool ordered = true;
-    E[0] = 1.0; logE[0] = 0.0; E[J] = 1.0; logE[J] = 0.0;
-#pragma unroll
-    for (int c = 1; c < J; ++c) {
-        const double gap = al[c] - al[c - 1];
-        ordered = ordered && gap > 0.0;             // (a NaN cutpoint fails too)
-        E[c] = -expm1(-gap);
-        logE[c] = log(E[c]);
-    }
+    const bool ordered = ord_cutpoints<J>(a.theta, al, E, logE);
     double sc[NS];
 #pragma unroll
     for (int i = 0; i < NS; ++i) sc[i] = 0.0;
@@ -95,30 +84,9 @@ __global__ __launch_bounds__(COUNT_THREADS) void ord_pass_kernel(OrdArgs a) {
     }
     const int myrow = row_of_lane<RB>(lane);
     const bool rep = (lane & rep_mask<RB>()) == 0;
-    const int64_t nbatch = (a.n + RB - 1) / RB;
-    const int64_t stride = (int64_t)gridDim.x * COUNT_WAVES;
 
     auto load_batch = [&](int64_t bt, double2 (&x)[RB][NC], double& yv) {
-        const int64_t row0 = bt * RB;
-        const int64_t ry = min(row0 + myrow, a.n - 1);
-        const double ytmp = a.y[ry];
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            const int64_t r = min(row0 + i, a.n - 1);
-            const double* rowp = a.X + r * a.ldx;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int col = c * 128 + 2 * lane;
-                const int c0 = col < a.p ? col : 0;
-                if (VEC) {                                            // VEC implies p even: a pair never straddles p
-                    x[i][c] = count_ld2(rowp + c0);
-                } else {
-                    x[i][c].x = __builtin_nontemporal_load(rowp + c0);
-                    x[i][c].y = __builtin_nontemporal_load(rowp + (col + 1 < a.p ? col + 1 : 0));
-                }
-            }
-        }
-        yv = ytmp;
+        yv = a.y[row_pass_load<NC, RB, VEC>(a.X, a.ldx, a.n, a.p, bt, lane, myrow, x)];
     };
     auto process = [&](int64_t bt, const double2 (&x)[RB][NC], const double yraw) {
         double dot[RB];
@@ -140,14 +108,8 @@ __global__ __launch_bounds__(COUNT_THREADS) void ord_pass_kernel(OrdArgs a) {
             if (a.aa_out) { a.aa_out[r] = aa; a.bb_out[r] = bb; }
             ll += llt;
         }
-        // cutpoint j + 1 is the upper one of class j and the lower one of class j + 1: selects, no branch on y
 #pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const bool up = mine && yraw == (double)j, lo = mine && yraw == (double)(j + 1);
-            sc[j] += (up ? su : 0.0) - (lo ? sl : 0.0);
-            sc[J + j] += (up ? aa + q : 0.0) + (lo ? bb + q : 0.0);
-            if (j < J - 1) sc[2 * J + j] -= lo ? q : 0.0;
-        }
+        for (int j = 0; j < J; ++j) ord_cutpoint_sums<J>(j, yraw, mine, su, sl, aa, bb, q, sc);
         rank1_update<RB, NC, 0>(valid ? resid : 0.0, x, g[0]);
         if constexpr (BORDER) {
 #pragma unroll
@@ -158,63 +120,21 @@ __global__ __launch_bounds__(COUNT_THREADS) void ord_pass_kernel(OrdArgs a) {
         }
     };
 
-    int64_t bt = (int64_t)blockIdx.x * COUNT_WAVES + wave;
-    if constexpr (NC == 1) {
-        double2 xa[RB][NC], xb[RB][NC];
-        double ya = 0.0, yb = 0.0;
-        if (a.n > 0) {
-            load_batch(bt, xa, ya);
-            for (; bt < nbatch; bt += 2 * stride) {
-                const int64_t b1 = bt + stride, b2 = bt + 2 * stride;
-                load_batch(b1, xb, yb);
-                process(bt, xa, ya);
-                load_batch(b2, xa, ya);
-                if (b1 < nbatch) process(b1, xb, yb);
-            }
-        }
-    } else {
-        for (; bt < nbatch; bt += stride) {
-            double2 x[RB][NC];
-            double yv;
-            load_batch(bt, x, yv);
-            process(bt, x, yv);
-        }
-    }
+    row_pass_stream<NC, RB, double>(a.n, wave, load_batch, process);
 
-    // block reduction: waves add into LDS one after another (fixed order)
-    ll = wave_allreduce_sum(ll);
+    double rs[1 + NS];                              // loglik, then the scalar sums
+    rs[0] = ll;
 #pragma unroll
-    for (int i = 0; i < NS; ++i) sc[i] = wave_allreduce_sum(sc[i]);
-    for (int wv = 0; wv < COUNT_WAVES; ++wv) {
-        if (wave == wv) {
-#pragma unroll
-            for (int k = 0; k < SETS; ++k) {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    double* dst = red + k * W + c * 128 + 2 * lane;
-                    if (wv == 0) { dst[0] = g[k][c].x; dst[1] = g[k][c].y; }
-                    else { dst[0] += g[k][c].x; dst[1] += g[k][c].y; }
-                }
-            }
-            if (lane == 0) {
-                double* ds = red + SETS * W;
-                if (wv == 0) ds[0] = ll; else ds[0] += ll;
-#pragma unroll
-                for (int i = 0; i < NS; ++i) {
-                    if (wv == 0) ds[1 + i] = sc[i]; else ds[1 + i] += sc[i];
-                }
-            }
-        }
-        __syncthreads();
-    }
+    for (int i = 0; i < NS; ++i) rs[1 + i] = sc[i];
+    row_pass_reduce(g, rs, red, lane, wave);
     double* gp = a.gpart + (int64_t)blockIdx.x * (SETS * W);
     for (int col = tid; col < SETS * W; col += COUNT_THREADS) gp[col] = red[col];
     if (tid == 0) a.llpart[blockIdx.x] = ordered ? red[SETS * W] : NAN;
-    if (tid < ORD_SC) {
-        // the block's row of scalars in the layout of ordinal_internal.h: [g_alpha | diagonal | off-diagonal], 7 slots each
-        const int grp = tid / ORD_MAX_J, j = tid - grp * ORD_MAX_J;
-        const bool has = grp < 3 && j < (grp == 2 ? J - 1 : J);
-        a.scpart[(int64_t)blockIdx.x * ORD_SC + tid] = has ? red[SETS * W + 1 + grp * J + j] : 0.0;
+    if (tid < ORD_SC) {                             // the block's row of scalars in the layout of ordinal_internal.h
+        double v = 0.0;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) v = ord_sc_slot<J>(i) == tid ? red[SETS * W + 1 + i] : v;
+        a.scpart[(int64_t)blockIdx.x * ORD_SC + tid] = v;
     }
 }
 
@@ -275,31 +195,21 @@ int ord_start(double* theta, int J, int d, const OrdStart& st, hipStream_t s) {
     return DLSA_OK;
 }
 
-template <int C, int NC, bool BORDER>
-static void ord_launch_v(const OrdArgs& a, bool vec, int blocks, hipStream_t s) {
-    constexpr int RB = NC <= 2 ? 8 : NC == 4 ? 4 : NC == 8 ? 2 : 1;          // count_rb
-    if (vec) hipLaunchKernelGGL((ord_pass_kernel<C, NC, RB, true, BORDER>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((ord_pass_kernel<C, NC, RB, false, BORDER>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
-}
-
 // BORDER is instantiated where C NC <= ORD_BORDER_SETS (ord_border_in_pass): the caller asks for it nowhere else
-template <int C, int NC>
-static void ord_launch_nc(const OrdArgs& a, bool vec, bool border, int blocks, hipStream_t s) {
-    if constexpr (C * NC <= ORD_BORDER_SETS) {
-        if (border) { ord_launch_v<C, NC, true>(a, vec, blocks, s); return; }
-    }
-    ord_launch_v<C, NC, false>(a, vec, blocks, s);
-}
-
 template <int C>
 static void ord_launch(const OrdArgs& a, int nc, bool vec, bool border, int blocks, hipStream_t s) {
-    switch (nc) {
-        case 1: ord_launch_nc<C, 1>(a, vec, border, blocks, s); break;
-        case 2: ord_launch_nc<C, 2>(a, vec, border, blocks, s); break;
-        case 4: ord_launch_nc<C, 4>(a, vec, border, blocks, s); break;
-        case 8: ord_launch_nc<C, 8>(a, vec, border, blocks, s); break;
-        default: ord_launch_nc<C, 16>(a, vec, border, blocks, s); break;
-    }
+    row_pass_dispatch(nc, [&](auto sh) {
+        constexpr int NC = decltype(sh)::NC, RB = decltype(sh)::RB;
+        if constexpr (C * NC <= ORD_BORDER_SETS) {
+            if (border) {
+                if (vec) hipLaunchKernelGGL((ord_pass_kernel<C, NC, RB, true, true>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
+                else hipLaunchKernelGGL((ord_pass_kernel<C, NC, RB, false, true>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
+                return;
+            }
+        }
+        if (vec) hipLaunchKernelGGL((ord_pass_kernel<C, NC, RB, true, false>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((ord_pass_kernel<C, NC, RB, false, false>), dim3(blocks), dim3(COUNT_THREADS), 0, s, a);
+    });
 }
 
 struct OrdLayout {
@@ -347,7 +257,7 @@ static int ord_pass_impl(const double* X, int64_t ldx, const double* y, const do
     a.aa_out = masked ? (double*)(ws + l.off_aa) : nullptr;
     a.bb_out = masked ? (double*)(ws + l.off_bb) : nullptr;
     a.gpart = (double*)(ws + l.off_gpart); a.llpart = (double*)(ws + l.off_llpart); a.scpart = (double*)(ws + l.off_scpart);
-    const bool vec = (ldx % 2 == 0) && (p % 2 == 0) && (((uintptr_t)X & 15) == 0);
+    const bool vec = row_pass_vec(X, ldx, p);
     const int blocks = count_blocks(n, rb);
     switch (classes) {
         case 2: ord_launch<2>(a, nc, vec, border, blocks, s); break;
@@ -430,7 +340,7 @@ int dlsa_ordinal_pass_f64(const double* X, int64_t ldx, const double* y, const d
     return mn_ll_fix(loglik, (const double*)(wsc + l.off_cst), s);
 }
 
-// The per-partition driver is ord_fit_core (ordinal_internal.h, shared with the structured sibling): the data check of EVERY
+// The per-partition driver is mn_fit_core (multinomial_internal.h, shared with the multinomial fits): the data check of EVERY
 // partition first, then per partition the null model's start, newton_fit_loop with the policy NEWTON_POISSON on d coefficients and
 // newton_fit_finish.
 int dlsa_ordinal_fit_f64(const double* X, int64_t ldx, const double* y, const int64_t* part_first_host, const int64_t* part_rows_host,
@@ -442,7 +352,7 @@ int dlsa_ordinal_fit_f64(const double* X, int64_t ldx, const double* y, const in
                  "ordinal_fit: null argument (X, y, the partitions, coef, Sig_inv and Sig_invMcoef are required)");
     int rc = ord_shape_ok("ordinal_fit", p, classes);
     if (rc) return rc;
-    const int J = classes - 1, d = J + p;
+    const int d = classes - 1 + p;
     DLSA_REQUIRE(K > 0 && ldx >= p && row_step >= 1, "ordinal_fit: bad shape K=%d p=%d ldx=%lld step=%lld", K, p, (long long)ldx,
                  (long long)row_step);
     DLSA_REQUIRE(max_iter > 0 && tol > 0, "ordinal_fit: bad tol/max_iter");
@@ -456,7 +366,7 @@ int dlsa_ordinal_fit_f64(const double* X, int64_t ldx, const double* y, const in
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* wsc = (char*)ws;
-    OrdFitBufs b{};
+    MnFitBufs b{};
     b.cpart = (double*)(wsc + l.off_cpart); b.cst = (double*)(wsc + l.off_cst);
     b.ybuf = (double*)(wsc + l.off_y);
     b.st = newton_state_at(wsc + align_up(l.total, 256), d);
@@ -464,8 +374,8 @@ int dlsa_ordinal_fit_f64(const double* X, int64_t ldx, const double* y, const in
     auto eval = [=](int k, const double* yk, int64_t nk, const double* theta, double* Hk, double* g, double* ll) {
         return ord_pass_impl(X + part_first_host[k] * ldx, pitch, yk, theta, classes, nk, p, Hk, d, g, ll, nullptr, wsc, l, s);
     };
-    return ord_fit_core("ordinal_fit", y, part_first_host, part_rows_host, row_step, K, p, classes, tol, max_iter, coef, Sig_inv,
-                        Sig_invMcoef, n_iter_host, status_host, loglik_host, b, eval, s);
+    return mn_fit_core("ordinal_fit", ORD_NO_CLASS, y, part_first_host, part_rows_host, row_step, K, d, classes, tol, max_iter, coef, Sig_inv,
+                       Sig_invMcoef, n_iter_host, status_host, loglik_host, b, ord_null_start(classes - 1, d), eval, s);
 }
 
 }  // extern "C"

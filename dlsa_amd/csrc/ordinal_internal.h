@@ -1,11 +1,11 @@
 // What the ordinal (proportional-odds) family's two translation units (ordinal.hip: the dense rows, onehot_ordinal.hip: the raw
 // representation of a one-hot design) share: the limits, the layout of the per-block scalar partials, the terms of one row, the
-// host launchers of the mask, assemble and start kernels (ordinal.hip's) and the per-partition fit driver that takes the
-// evaluation as a callable.  The class check, the gather of a strided partition's responses and the Newton state, loop and
-// epilogue are the multinomial family's, poisson_internal.h's and newton_fit.h's.
+// host launchers of the mask, assemble and start kernels (ordinal.hip's), the fits' start and, device side, the cutpoint preamble
+// and the scalar sums of both row kernels.  The class check and the fit driver (mn_fit_core) are multinomial_internal.h's, the
+// gather of a strided partition's responses poisson_internal.h's, the Newton state, loop and epilogue newton_fit.h's.
 #pragma once
 #include "common.h"
-#include "multinomial_internal.h"   // MN_MAX_CLASSES, mn_check, mn_ll_fix, exp_full (poisson_exp.h)
+#include "multinomial_internal.h"   // MN_MAX_CLASSES, mn_check, mn_ll_fix, mn_fit_core, MnFitBufs, exp_full (poisson_exp.h)
 
 namespace dlsa {
 
@@ -14,6 +14,9 @@ constexpr int ORD_MAX_J = ORD_MAX_CLASSES - 1;
 // the scalar sums of a pass, one row of ORD_SC doubles per block: g_alpha (J), the corner's diagonal (J), its off-diagonal (J - 1)
 constexpr int ORD_SC = 32;
 constexpr int ORD_SC_GA = 0, ORD_SC_DG = ORD_MAX_J, ORD_SC_OF = 2 * ORD_MAX_J;
+// the slot of the row that sum i of a kernel's 3J - 1 goes to; the slots no sum goes to hold 0
+template <int J>
+constexpr int ord_sc_slot(int i) { return i < J ? ORD_SC_GA + i : i < 2 * J ? ORD_SC_DG + (i - J) : ORD_SC_OF + (i - 2 * J); }
 // in-pass borders where the C accumulator sets of NC double2 fit the lane's registers
 constexpr int ORD_BORDER_SETS = 16;
 static inline bool ord_border_in_pass(int classes, int nc) { return classes * nc <= ORD_BORDER_SETS; }
@@ -32,80 +35,20 @@ int ord_assemble(const double* sc, const double* bd, int ldbd, int J, int p, dou
 // the Newton start: theta = [st.a | 0], d = J + p entries
 int ord_start(double* theta, int J, int d, const OrdStart& st, hipStream_t s);
 
-// device scratch of the fit loop
-struct OrdFitBufs {
-    double* cpart;     // MN_NQ * MN_CHECK_BLOCKS
-    double* cst;       // MN_NQ
-    double* ybuf;      // max_rows when row_step > 1: the gathered responses
-    NewtonState st;
-};
+constexpr char ORD_NO_CLASS[] = "merges two cutpoints";           // what a partition without a row of some class does to the fit
 
-// The per-partition driver of the ordinal fits, in the shape of mn_fit_core (multinomial_internal.h): the data check of EVERY
-// partition first (a partition that lacks a class merges two cutpoints, and the blocks of different partitions must mean the same
-// parameter), then per partition the null model's start (alpha_j = the logit of the cumulative class share, beta = 0),
-// newton_fit_loop with the policy NEWTON_POISSON on d = J + p coefficients and newton_fit_finish.  eval(k, yk, nk, theta, H, g, ll)
-// is the only part that knows the representation of the design; `who` prefixes messages.
-template <class Eval>
-static int ord_fit_core(const char* who, const double* y, const int64_t* part_first_host, const int64_t* part_rows_host, int64_t row_step,
-                        int K, int p, int classes, double tol, int max_iter, double* coef, double* Sig_inv, double* Sig_invMcoef,
-                        int* n_iter_host, int* status_host, double* loglik_host, const OrdFitBufs& b, Eval&& eval, hipStream_t s) {
-    const int J = classes - 1, d = J + p;
-    std::vector<double> counts((size_t)K * MN_NQ, 0.0);
-    const double* yk = nullptr;
-    const double* none = nullptr;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        if (nk <= 0) continue;
-        int rc = pois_gather_rows(y, nullptr, part_first_host[k], row_step, nk, b.ybuf, nullptr, yk, none, s);
-        if (rc) return rc;
-        rc = mn_check(yk, nk, classes, b.cpart, b.cst, s);
-        if (rc) return rc;
-        double* cst = counts.data() + (size_t)k * MN_NQ;
-        DLSA_HIP_CHECK(hipMemcpyAsync(cst, b.cst, MN_NQ * sizeof(double), hipMemcpyDeviceToHost, s));
-        DLSA_HIP_CHECK(hipStreamSynchronize(s));
-        if (cst[MN_BAD] > 0.0) {
-            set_error("%s: partition %d has %.0f rows whose response is not a class code 0 .. %d", who, k, cst[MN_BAD], classes - 1);
-            return DLSA_ERR_INVALID;
+// the ordinal fits' start for mn_fit_core (multinomial_internal.h): alpha_j = the logit of the cumulative class share, beta = 0,
+// the exact MLE of the null model on d = J + p coefficients
+static inline auto ord_null_start(int J, int d) {
+    return [=](const double* cst, int64_t nk, double* theta, hipStream_t s) {
+        OrdStart start{};
+        double cum = 0.0;
+        for (int j = 0; j < J; ++j) {
+            cum += cst[j];
+            start.a[j] = log(cum / ((double)nk - cum));
         }
-        for (int c = 0; c < classes; ++c) {
-            if (!(cst[c] > 0.0)) {
-                set_error("%s: partition %d has no row of class %d: its maximum-likelihood fit merges two cutpoints", who, k, c);
-                return DLSA_ERR_INVALID;
-            }
-        }
-    }
-    int overall = DLSA_OK;
-    for (int k = 0; k < K; ++k) {
-        const int64_t nk = part_rows_host[k];
-        double* Hk = Sig_inv + (size_t)k * d * d;
-        double* ck = coef + (size_t)k * d;
-        double* sk = Sig_invMcoef + (size_t)k * d;
-        int st_k = DLSA_PART_EMPTY, iters = 0;
-        double ll = 0.0;
-        if (nk > 0) {
-            int rc = pois_gather_rows(y, nullptr, part_first_host[k], row_step, nk, b.ybuf, nullptr, yk, none, s);
-            if (rc) return rc;
-            const double* cst = counts.data() + (size_t)k * MN_NQ;
-            OrdStart start{};
-            double cum = 0.0;
-            for (int j = 0; j < J; ++j) {
-                cum += cst[j];
-                start.a[j] = log(cum / ((double)nk - cum));           // the logit of the cumulative class share
-            }
-            rc = ord_start(b.st.beta, J, d, start, s);
-            if (rc) return rc;
-            const NewtonDevice dev{b.st, Hk, d, s};
-            NewtonOutcome o;
-            rc = newton_fit_loop(NEWTON_POISSON, tol, max_iter + 1, [&](bool&) { return eval(k, yk, nk, b.st.beta, Hk, b.st.g, b.st.stats + 3); },
-                                 dev, newton_no_hook, o);
-            if (rc) return rc;
-            st_k = o.status; iters = o.n_iter; ll = o.ll;
-        }
-        const int rcf = newton_fit_finish(st_k, iters, ll, b.st.beta, d, Hk, ck, sk, k, n_iter_host, status_host, loglik_host, overall, s);
-        if (rcf) return rcf;
-    }
-    DLSA_HIP_CHECK(hipStreamSynchronize(s));
-    return overall;
+        return ord_start(theta, J, d, start, s);
+    };
 }
 
 #if defined(__HIPCC__)
@@ -149,6 +92,38 @@ static __device__ __forceinline__ void ord_row_terms(double yraw, double eta, co
     su = Ab / (Bb * Ec);
     sl = B / (A * Ec);
     q = su * sl;
+}
+
+// The cutpoints al[j] = alpha[j] = alpha_{j+1} and the class factors E_c = -expm1(-(alpha_{c+1} - alpha_c)) of the interior classes
+// (1 for the two end classes) with their logarithms: functions of theta alone, the same in every lane.  Returns whether the
+// cutpoints increase strictly (a NaN cutpoint fails too).
+template <int J>
+static __device__ __forceinline__ bool ord_cutpoints(const double* alpha, double (&al)[J], double (&E)[J + 1], double (&logE)[J + 1]) {
+#pragma unroll
+    for (int j = 0; j < J; ++j) al[j] = alpha[j];
+    bool ordered = true;
+    E[0] = 1.0; logE[0] = 0.0; E[J] = 1.0; logE[J] = 0.0;
+#pragma unroll
+    for (int c = 1; c < J; ++c) {
+        const double gap = al[c] - al[c - 1];
+        ordered = ordered && gap > 0.0;
+        E[c] = -expm1(-gap);
+        logE[c] = log(E[c]);
+    }
+    return ordered;
+}
+
+// One row's share of the scalar sums sc = [g_alpha (J) | the corner's diagonal (J) | its off-diagonal (J - 1)] that belong to
+// cutpoint j + 1, the upper one of class j and the lower one of class j + 1; a kernel calls it for j = 0 .. J - 1.  Selects, no
+// branch on y; a row that is not `valid` adds 0.  (Per cutpoint, the loop in the kernel: with the loop in here
+// oh_ord_row_kernel<2, true> takes 169 VGPRs for 167 and loses a wave.)
+template <int J>
+static __device__ __forceinline__ void ord_cutpoint_sums(int j, double y, bool valid, double su, double sl, double aa, double bb, double q,
+                                                         double (&sc)[3 * J - 1]) {
+    const bool up = valid && y == (double)j, lo = valid && y == (double)(j + 1);
+    sc[j] += (up ? su : 0.0) - (lo ? sl : 0.0);
+    sc[J + j] += (up ? aa + q : 0.0) + (lo ? bb + q : 0.0);
+    if (j < J - 1) sc[2 * J + j] -= lo ? q : 0.0;
 }
 #endif
 

@@ -985,16 +985,71 @@ def tweedie_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_int
 MULTINOMIAL_MAX_CLASSES = 8
 
 
-def multinomial_classes(who, classes, pe):
-    """The class count of a multinomial entry: an int in 2 .. 8 with (classes - 1) * pe <= 2048 coefficients (ValueError otherwise)."""
+def _class_count(who, classes, coefficients, formula):
+    """The body of multinomial_classes / ordinal_classes: `classes` as an int in 2 .. 8 whose coefficients(classes), named `formula`
+    in the refusal, do not exceed the solver's 2048 (ValueError otherwise)."""
     if isinstance(classes, bool) or int(classes) != classes:
         raise ValueError("%s: classes must be an integer, got %r" % (who, classes))
     classes = int(classes)
     if not 2 <= classes <= MULTINOMIAL_MAX_CLASSES:
         raise ValueError("%s: classes must lie in 2 .. %d, got %d" % (who, MULTINOMIAL_MAX_CLASSES, classes))
-    if (classes - 1) * pe > 2048:
-        raise ValueError("%s: (classes - 1) * (p + intercept) = %d coefficients exceed the solver's 2048" % (who, (classes - 1) * pe))
+    if coefficients(classes) > 2048:
+        raise ValueError("%s: %s = %d coefficients exceed the solver's 2048" % (who, formula, coefficients(classes)))
     return classes
+
+
+def multinomial_classes(who, classes, pe):
+    """The class count of a multinomial entry: an int in 2 .. 8 with (classes - 1) * pe <= 2048 coefficients (ValueError otherwise)."""
+    return _class_count(who, classes, lambda c: (c - 1) * pe, "(classes - 1) * (p + intercept)")
+
+
+def ordinal_classes(who, classes, p):
+    """The class count of an ordinal entry: an int in 2 .. 8 with (classes - 1) + p <= 2048 coefficients (ValueError otherwise)."""
+    return _class_count(who, classes, lambda c: c - 1 + p, "(classes - 1) + p")
+
+
+class _ClassFamily(NamedTuple):
+    """What varies between the families whose response is a class code behind the {,onehot_}<name>_fit_ex wrappers.  The C entries
+    are dlsa_[onehot_]<name>_{workspace_bytes,fit_f64}."""
+    name: str
+    classes: Callable           # (who, classes, pe) -> the checked class count
+    d: Callable                 # (classes, pe) -> the coefficients of a partition's block
+    intercept: bool             # the dense entries take an intercept argument after p
+
+
+CLASS_FAMILIES = {f.name: f for f in (
+    _ClassFamily("multinomial", multinomial_classes, lambda c, pe: (c - 1) * pe, True),
+    _ClassFamily("ordinal", ordinal_classes, lambda c, pe: c - 1 + pe, False),
+)}
+
+
+def _class_fit(fam, rows, y, part_first, part_rows, row_step, classes, fit_intercept, tol, max_iter):
+    """The body of <name>_fit_ex (rows: the dense X) and onehot_<name>_fit_ex (rows: (plan, num, codes)): dlsa_[onehot_]<name>_fit_f64
+    on strided partitions of the rows."""
+    onehot = isinstance(rows, tuple)
+    entry = ("onehot_" if onehot else "") + fam.name
+    who = entry + "_fit_ex"
+    lib = _lib.load()
+    if onehot:
+        n = _oh_poisson_rows(*rows, y, None, who)
+        pe, device, rows_at, plan_at, shape = rows[0].p, y.device, (rows[0]._h, *_oh_args(*rows)), (rows[0]._h,), ()
+    else:
+        _require_gpu(rows, y)
+        _f64(rows, "X"); _f64(y, "y")
+        n, p = rows.shape
+        if y.numel() != n:
+            raise ValueError("%s: y must have n = %d elements" % (who, n))
+        shape = (p, 1 if fit_intercept else 0) if fam.intercept else (p,)
+        pe, device, rows_at, plan_at = sum(shape), rows.device, (_ptr(rows), _rowmajor(rows)), ()
+    if classes is None:
+        raise ValueError("%s: classes (the number of classes, 2 .. %d) is required" % (who, MULTINOMIAL_MAX_CLASSES))
+    classes = fam.classes(who, classes, pe)
+    K, step, max_rows, c_first, c_rows = _strided_partitions(who, part_first, part_rows, row_step, n)
+    out = _FitOut(K, fam.d(classes, pe), device)
+    ws = _workspace(getattr(lib, "dlsa_%s_workspace_bytes" % entry)(*plan_at, max_rows, *shape, classes, step), device)
+    rc = getattr(lib, "dlsa_%s_fit_f64" % entry)(*rows_at, _ptr(y), c_first, c_rows, step, K, *shape, classes, tol, max_iter, *out.args,
+                                                 _ptr(ws), ws.numel(), _stream())
+    return out.result(rc)
 
 
 def multinomial_pass(X, y, theta, classes, fit_intercept=False, want_H=True, want_prob=False):
@@ -1026,34 +1081,7 @@ def multinomial_fit_ex(X, y, part_first, part_rows, row_step=1, classes=None, fi
     class-major layout as multinomial_pass; `classes` (2 .. 8) is required -- a partition cannot discover the classes it lacks, and one
     that lacks a class is refused with the partition and the class named, as is a response that is no class code.  Same result dict
     as irls_fit_ex with J * pe columns; `loglik` is the log-likelihood at coef.  classes = 2 is the logistic fit."""
-    lib = _lib.load()
-    _require_gpu(X, y)
-    _f64(X, "X"); _f64(y, "y")
-    n, p = X.shape
-    if y.numel() != n:
-        raise ValueError("multinomial_fit_ex: y must have n = %d elements" % n)
-    if classes is None:
-        raise ValueError("multinomial_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
-    icpt = 1 if fit_intercept else 0
-    classes = multinomial_classes("multinomial_fit_ex", classes, p + icpt)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("multinomial_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, (classes - 1) * (p + icpt), X.device)
-    ws = _workspace(lib.dlsa_multinomial_workspace_bytes(max_rows, p, icpt, classes, step), X.device)
-    rc = lib.dlsa_multinomial_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), c_first, c_rows, step, K, p, icpt, classes, tol, max_iter, *out.args,
-                                      _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
-
-
-def ordinal_classes(who, classes, p):
-    """The class count of an ordinal entry: an int in 2 .. 8 with (classes - 1) + p <= 2048 coefficients (ValueError otherwise)."""
-    if isinstance(classes, bool) or int(classes) != classes:
-        raise ValueError("%s: classes must be an integer, got %r" % (who, classes))
-    classes = int(classes)
-    if not 2 <= classes <= MULTINOMIAL_MAX_CLASSES:
-        raise ValueError("%s: classes must lie in 2 .. %d, got %d" % (who, MULTINOMIAL_MAX_CLASSES, classes))
-    if classes - 1 + p > 2048:
-        raise ValueError("%s: (classes - 1) + p = %d coefficients exceed the solver's 2048" % (who, classes - 1 + p))
-    return classes
+    return _class_fit(CLASS_FAMILIES["multinomial"], X, y, part_first, part_rows, row_step, classes, fit_intercept, tol, max_iter)
 
 
 def ordinal_pass(X, y, theta, classes, want_H=True, want_w=False):
@@ -1083,21 +1111,7 @@ def ordinal_fit_ex(X, y, part_first, part_rows, row_step=1, classes=None, tol=1e
     and one that lacks a class is refused with the partition and the class named, as is a response that is no class code.  Same result
     dict as multinomial_fit_ex with J + p columns; `loglik` is the log-likelihood at coef.  classes = 2 is the logistic fit with
     theta = [-intercept | beta]."""
-    lib = _lib.load()
-    _require_gpu(X, y)
-    _f64(X, "X"); _f64(y, "y")
-    n, p = X.shape
-    if y.numel() != n:
-        raise ValueError("ordinal_fit_ex: y must have n = %d elements" % n)
-    if classes is None:
-        raise ValueError("ordinal_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
-    classes = ordinal_classes("ordinal_fit_ex", classes, p)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("ordinal_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, classes - 1 + p, X.device)
-    ws = _workspace(lib.dlsa_ordinal_workspace_bytes(max_rows, p, classes, step), X.device)
-    rc = lib.dlsa_ordinal_fit_f64(_ptr(X), _rowmajor(X), _ptr(y), c_first, c_rows, step, K, p, classes, tol, max_iter, *out.args,
-                                  _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
+    return _class_fit(CLASS_FAMILIES["ordinal"], X, y, part_first, part_rows, row_step, classes, False, tol, max_iter)
 
 
 def negbin_special(theta, y):
@@ -1523,17 +1537,7 @@ def onehot_multinomial_fit_ex(plan, num, codes, y, part_first, part_rows, row_st
     """multinomial_fit_ex on the raw representation of a one-hot design (dlsa_onehot_multinomial_fit_f64): partitions as
     onehot_poisson_fit_ex, `classes` (2 .. 8, required) and the refusals as multinomial_fit_ex.  Same result dict as
     multinomial_fit_ex with J * plan.p columns, class-major in the plan's column order."""
-    lib = _lib.load()
-    n = _oh_poisson_rows(plan, num, codes, y, None, "onehot_multinomial_fit_ex")
-    if classes is None:
-        raise ValueError("onehot_multinomial_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
-    classes = multinomial_classes("onehot_multinomial_fit_ex", classes, plan.p)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_multinomial_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, (classes - 1) * plan.p, y.device)
-    ws = _workspace(lib.dlsa_onehot_multinomial_workspace_bytes(plan._h, max_rows, classes, step), y.device)
-    rc = lib.dlsa_onehot_multinomial_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), c_first, c_rows, step, K, classes, tol, max_iter,
-                                             *out.args, _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
+    return _class_fit(CLASS_FAMILIES["multinomial"], (plan, num, codes), y, part_first, part_rows, row_step, classes, False, tol, max_iter)
 
 
 def onehot_ordinal_pass(plan, num, codes, y, theta, classes, want_H=True, want_w=False):
@@ -1561,17 +1565,7 @@ def onehot_ordinal_fit_ex(plan, num, codes, y, part_first, part_rows, row_step=1
     """ordinal_fit_ex on the raw representation of a one-hot design (dlsa_onehot_ordinal_fit_f64): partitions as
     onehot_poisson_fit_ex, `classes` (2 .. 8, required) and the refusals as ordinal_fit_ex; a plan with a constant column is refused.
     Same result dict as ordinal_fit_ex with J + plan.p columns, cutpoints first, then the plan's column order."""
-    lib = _lib.load()
-    n = _oh_poisson_rows(plan, num, codes, y, None, "onehot_ordinal_fit_ex")
-    if classes is None:
-        raise ValueError("onehot_ordinal_fit_ex: classes (the number of classes, 2 .. %d) is required" % MULTINOMIAL_MAX_CLASSES)
-    classes = ordinal_classes("onehot_ordinal_fit_ex", classes, plan.p)
-    K, step, max_rows, c_first, c_rows = _strided_partitions("onehot_ordinal_fit_ex", part_first, part_rows, row_step, n)
-    out = _FitOut(K, classes - 1 + plan.p, y.device)
-    ws = _workspace(lib.dlsa_onehot_ordinal_workspace_bytes(plan._h, max_rows, classes, step), y.device)
-    rc = lib.dlsa_onehot_ordinal_fit_f64(plan._h, *_oh_args(plan, num, codes), _ptr(y), c_first, c_rows, step, K, classes, tol, max_iter,
-                                         *out.args, _ptr(ws), ws.numel(), _stream())
-    return out.result(rc)
+    return _class_fit(CLASS_FAMILIES["ordinal"], (plan, num, codes), y, part_first, part_rows, row_step, classes, False, tol, max_iter)
 
 
 class RcclComm:

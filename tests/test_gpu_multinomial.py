@@ -76,6 +76,21 @@ def test_pass_short_and_wide_shapes(eng, n, p, C, intercept):
     _check_pass(eng, X, y, mr.away_from_optimum((C - 1) * (p + intercept)), C, intercept)
 
 
+# Edge shapes of the shared row-pass skeleton (csrc/row_pass.h) that neither list above reaches: n = 7 is one batch of 8 with one
+# clamped row; n = 1003 at p = 3 is several batches per wave on the NC = 1 two-set loop with a last prefetched batch past the end;
+# n = 300 001 at p = 3 meets the cap on the block count (37 501 batches of 8 ask for 2344 blocks of 16); p = 2 is the 16-byte loads at
+# the smallest width; p = 513 at C = 4 is NC = 8 (two rows per batch) with the most classes that have it, p = 1025 at C = 2 is NC = 16
+# on the scalar loads.
+SKELETON_EDGES = [(7, 3, 3), (7, 130, 4), (1003, 3, 3), (300001, 3, 3), (67, 2, 5), (67, 513, 4), (67, 1025, 2)]
+
+
+@pytest.mark.parametrize("n,p,C", SKELETON_EDGES)
+@pytest.mark.parametrize("intercept", [False, True])
+def test_pass_edge_shapes_of_the_row_pass_skeleton(eng, n, p, C, intercept):
+    X, y = mr.data(700 + p + n % 1000, n, p, C, intercept)
+    _check_pass(eng, X, y, mr.away_from_optimum((C - 1) * (p + intercept)), C, intercept)
+
+
 def test_pass_with_an_absent_class_is_legal(eng):
     X, y = mr.data(31, 200, 7, 4, True)
     y[y == 2] = 0.0

@@ -78,6 +78,21 @@ def test_pass_fewer_rows_than_one_batch(eng, p, C):
     _check_pass(eng, X, y, theta, C, orf.terms(X, y, theta, C), what="short pass")
 
 
+# Edge shapes of the shared row-pass skeleton (csrc/row_pass.h) that no list above reaches: n = 1, 7 and 9 are a batch of 8 that is
+# all clamp but one row, one with a single clamped row, and a second batch with one row; n = 1003 at p = 3 is several batches per
+# wave on the NC = 1 two-set loop with a last prefetched batch past the end, and a pair that straddles p; n = 300 001 at p = 3 meets
+# the cap on the block count (37 501 batches of 8 ask for 2344 blocks of 16); p = 1025 is NC = 16 on the scalar loads; (257, 8) is
+# the masked route at the most classes (C NC = 32 > 16) beside the in-pass borders of the others.
+SKELETON_EDGES = [(1, 5, 3), (7, 5, 3), (9, 5, 3), (9, 130, 8), (1003, 3, 4), (300001, 3, 3), (67, 1025, 2), (1003, 257, 8)]
+
+
+@pytest.mark.parametrize("n,p,C", SKELETON_EDGES)
+def test_pass_edge_shapes_of_the_row_pass_skeleton(eng, n, p, C):
+    X, y = orf.data(700 + p + n % 1000, n, p, C)
+    theta = orf.away_from_optimum(p, C)
+    _check_pass(eng, X, y, theta, C, orf.terms(X, y, theta, C), what="edge pass")
+
+
 @pytest.mark.parametrize("p,C,pad", [(5, 3, 3), (130, 8, 2), (257, 5, 3)])
 def test_pass_on_a_padded_pitch(eng, p, C, pad):
     """columns 1 .. p of a buffer with p + pad columns, passed as a view: an odd pitch, or an even one with the base 8 bytes off a

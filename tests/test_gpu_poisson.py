@@ -80,6 +80,20 @@ def test_pass_short_and_wide_shapes(eng, n, p, intercept, offset):
     _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), intercept)
 
 
+# Edge shapes of the shared row-pass skeleton (csrc/row_pass.h) that neither list above reaches: n = 1003 at p = 3 is several batches
+# per wave on the NC = 1 two-set loop with a last prefetched batch past the end, and a pair that straddles p; n = 300 001 at p = 3
+# meets the cap on the block count (37 501 batches of 8 ask for 2344 blocks of 16); 129, 257 and 513 are the scalar loads at
+# NC = 2, 4 and 8 with one column in the last chunk.
+SKELETON_EDGES = [(1003, 3), (300001, 3), (67, 129), (67, 257), (67, 513)]
+
+
+@pytest.mark.parametrize("n,p", SKELETON_EDGES)
+@pytest.mark.parametrize("intercept,offset", [(False, False), (True, True)])
+def test_pass_edge_shapes_of_the_row_pass_skeleton(eng, n, p, intercept, offset):
+    X, y, o = _data(700 + p + n % 1000, n, p, intercept, offset)
+    _check_pass(eng, X, y, o, _away_from_optimum(p + intercept), intercept)
+
+
 @pytest.mark.parametrize("p", [8, 130, 1030])
 @pytest.mark.parametrize("pad", [3, 2])
 @pytest.mark.parametrize("intercept,offset", [(False, False), (True, True)])
