@@ -13,7 +13,8 @@ from .models import (MappedBlocks, cox_model, fit_cox_partitions, fit_linear_chu
                      combine_gamma_dispersion, fit_gamma_design, fit_gamma_partitions, gamma_model, gamma_model_eval, simulate_gamma,
                      combine_tweedie_dispersion, fit_tweedie_design, fit_tweedie_partitions, simulate_tweedie, tweedie_model, tweedie_model_eval,
                      fit_multinomial_design, fit_multinomial_partitions, intercept_columns, multinomial_column_names, multinomial_model, multinomial_model_eval, simulate_multinomial,
-                     fit_ordinal_design, fit_ordinal_partitions, ordinal_column_names, ordinal_model, ordinal_model_eval, simulate_ordinal)
+                     fit_ordinal_design, fit_ordinal_partitions, ordinal_column_names, ordinal_model, ordinal_model_eval, simulate_ordinal,
+                     cloglog_model, cloglog_model_eval, fit_cloglog_partitions, fit_probit_partitions, probit_model, probit_model_eval, simulate_binary)
 from .design import DesignSpec, design_matrix                                                    # noqa: E402,F401
 from .dlsa import dlsa, dlsa_fit, dlsa_mapred, dlsa_mapreduce                                   # noqa: E402,F401
 from .lsa import lars_lsa                                                                        # noqa: E402,F401

@@ -219,6 +219,11 @@ ONEHOT_ORDINAL_SIGNATURES = {
                                             ctypes.POINTER(c_dbl), c_vp, c_sz, c_vp]),
 }
 
+# name -> (restype, argtypes); every symbol the family extension header include/dlsa_hip_binary.h declares: the probit and the cloglog
+# entries take, argument for argument, what the three Poisson entries take
+BINARY_SIGNATURES = {"dlsa_%s_%s" % (link, entry): SIGNATURES["dlsa_poisson_" + entry]
+                     for link in ("probit", "cloglog") for entry in ("workspace_bytes", "pass_f64", "fit_f64")}
+
 _lib = None
 
 
@@ -240,7 +245,8 @@ def load():
     # pointers and streams are shared (loading the system libamdhip64 first gives two runtimes).
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(ORDINAL_SIGNATURES.items()) + list(ONEHOT_ORDINAL_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(ORDINAL_SIGNATURES.items()) + list(ONEHOT_ORDINAL_SIGNATURES.items())
+                              + list(BINARY_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -753,6 +753,9 @@ GLM_FAMILIES = {f.name: f for f in (
             ("alpha", "alpha_info", "pearson"), other="poisson"),
     _Family("gamma", (_DISPERSION,), ((2, "want_stats"),), GAMMA_LISTS, df=True),
     _Family("tweedie", (_Scalar("power", tweedie_power, tweedie_power), _DISPERSION), ((2, "want_stats"),), GAMMA_LISTS, df=True),
+    # the two binary links beside the logit (include/dlsa_hip_binary.h): dense entries only so far
+    _Family("probit"),
+    _Family("cloglog"),
 )}
 
 
@@ -980,6 +983,32 @@ def tweedie_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_int
     estimated): partitions, offset and intercept as poisson_fit_ex, dispersion as gamma_fit_ex.  The result dict of gamma_fit_ex
     (`dispersion`, `pearson`, `deviance`, `df`); `loglik` is the quasi-log-likelihood at (coef, the dispersion used)."""
     return _glm_fit(GLM_FAMILIES["tweedie"], X, y, part_first, part_rows, row_step, offset, fit_intercept, (power, dispersion), tol, max_iter)
+
+
+def probit_pass(X, y, beta, offset=None, fit_intercept=False, want_H=True, want_w=False):
+    """One probit partition at a fixed beta (dlsa_probit_pass_f64, include/dlsa_hip_binary.h): y [n] holds 0.0 / 1.0, P(y = 1) =
+    Phi(eta), eta = [1 | X] beta + offset.  Arguments as poisson_pass.  Returns (H [pe,pe] = the OBSERVED information [1 | X]' diag(w)
+    [1 | X] or None, g [pe], loglik [1] = sum log Phi((2y - 1) eta) -- NaN when a response is not 0 or 1 --, w [n] or None)."""
+    return _glm_pass(GLM_FAMILIES["probit"], X, y, beta, (), offset, fit_intercept, want_H, want_w)
+
+
+def probit_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, tol=1e-13, max_iter=100):
+    """Per-partition probit fit (dlsa_probit_fit_f64): partitions, offset and intercept as poisson_fit_ex, y in {0, 1}.  The result dict
+    of poisson_fit_ex; Sig_inv is the observed information at coef.  A partition with an intercept and a single response value is
+    EMPTY with the all-zero block."""
+    return _glm_fit(GLM_FAMILIES["probit"], X, y, part_first, part_rows, row_step, offset, fit_intercept, (), tol, max_iter)
+
+
+def cloglog_pass(X, y, beta, offset=None, fit_intercept=False, want_H=True, want_w=False):
+    """One complementary log-log partition at a fixed beta (dlsa_cloglog_pass_f64, include/dlsa_hip_binary.h): y [n] holds 0.0 / 1.0,
+    P(y = 1) = 1 - exp(-e^eta), eta = [1 | X] beta + offset (offset = log interval length or exposure, as in poisson_pass).  Arguments and
+    results as probit_pass; on rows with y = 0 it is poisson_pass bit for bit."""
+    return _glm_pass(GLM_FAMILIES["cloglog"], X, y, beta, (), offset, fit_intercept, want_H, want_w)
+
+
+def cloglog_fit_ex(X, y, part_first, part_rows, row_step=1, offset=None, fit_intercept=False, tol=1e-13, max_iter=100):
+    """Per-partition complementary log-log fit (dlsa_cloglog_fit_f64): as probit_fit_ex."""
+    return _glm_fit(GLM_FAMILIES["cloglog"], X, y, part_first, part_rows, row_step, offset, fit_intercept, (), tol, max_iter)
 
 
 MULTINOMIAL_MAX_CLASSES = 8

@@ -701,8 +701,13 @@ def _tweedie_response(y):
     return None
 
 
+def _binary_response(y):
+    return None if bool(((y == 0) | (y == 1)).all()) else "the response must be 0 or 1"                                 # (NaN fails both)
+
+
 # What a log-link family refuses in its response: y -> the message, or None for a response it takes.
-_RESPONSE_REFUSED = {"poisson": _count_response, "negbin": _count_response, "gamma": _positive_response, "tweedie": _tweedie_response}
+_RESPONSE_REFUSED = {"poisson": _count_response, "negbin": _count_response, "gamma": _positive_response, "tweedie": _tweedie_response,
+                     "probit": _binary_response, "cloglog": _binary_response}
 
 
 def _alpha_not_zero(who, alpha, other):
@@ -880,6 +885,76 @@ def poisson_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=
     logistic_model_eval's output: one row, a column per estimator.  structured=True with a dummy_info and a qualifying design
     evaluates on the raw numerics + level codes (one structured pass per estimator column); the default is the dense path."""
     return _count_model_eval("poisson", par, structured, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                             dummy_factors_baseline, data_info)
+
+
+# ---------------------------------------------------------------------------------------------
+# Probit and complementary log-log map steps for a 0/1 response, the two binary links beside the logit: P(y = 1) = Phi(eta) and
+# P(y = 1) = 1 - exp(-e^eta) with eta = [1 | x]' beta + o.  The block is coef = the partition's MLE, Sig_inv = the OBSERVED information
+# there (not the Fisher information R's glm weights by; the two agree in expectation), Sig_invMcoef = Sig_inv coef, so dlsa_mapred /
+# dlsa / lars_lsa apply unchanged.  Offsets and exposure as in the Poisson step: under the cloglog link offset = log(exposure) is the
+# model of "any event within the exposure", the grouped-time twin of the Cox step.  Dense rows only so far.
+# ---------------------------------------------------------------------------------------------
+BINARY_LINKS = ("probit", "cloglog")
+
+
+def simulate_binary(sample_size, p, partition_num, link, seed=20260101, intercept=-0.5, coef_value=0.5, exposure=False):
+    """Seeded 0/1 rows under `link` ("probit" or "cloglog"): x and beta* as simulate_poisson's, eta = intercept + log(exposure) + x beta*,
+    y ~ Bernoulli(Phi(eta)) respectively Bernoulli(1 - exp(-e^eta)) drawn with numpy; exposure (with exposure=True) ~ U(0.5, 2), else 1.
+    partition_id = i % partition_num.  Returns the frame partition_id, y, [exposure,] x0 .. x{p-1}."""
+    if link not in BINARY_LINKS:
+        raise ValueError("simulate_binary: link must be one of %s, got %r" % (", ".join(BINARY_LINKS), link))
+
+    def draw(rng, mu):
+        eta = np.log(mu)
+        prob = -np.expm1(-mu) if link == "cloglog" else torch.special.ndtr(torch.from_numpy(eta)).numpy()
+        return (rng.uniform(size=len(mu)) < prob).astype(np.float64)
+    return _simulate_glm(sample_size, p, partition_num, seed, np.exp(float(intercept)), coef_value, exposure, draw)
+
+
+def fit_probit_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, names=None,
+                          tol=1e-13, max_iter=100):
+    """Probit map step for the partitions of one device-resident shard; arguments as fit_poisson_partitions, y in {0, 1} (anything else
+    is refused).  A partition with an intercept and a single response value returns the all-zero block (status EMPTY).  Returns
+    MappedBlocks with `loglik` = the log-likelihood per partition."""
+    return _fit_glm_partitions("probit", X, y, partition_num, part_offsets, fit_intercept, offset, exposure, names, tol, max_iter)
+
+
+def fit_cloglog_partitions(X, y, partition_num=None, part_offsets=None, fit_intercept=False, offset=None, exposure=None, names=None,
+                           tol=1e-13, max_iter=100):
+    """Complementary log-log map step for the partitions of one device-resident shard; arguments and results as fit_probit_partitions.
+    `exposure` [n] (interval length, effort) is turned into offset = log(exposure)."""
+    return _fit_glm_partitions("cloglog", X, y, partition_num, part_offsets, fit_intercept, offset, exposure, names, tol, max_iter)
+
+
+def probit_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                 dummy_factors_baseline=[], data_info=[]):
+    """Frame-level sibling of poisson_model for a 0/1 response under the probit link: one partition (a pandas frame) with the response
+    column Y_name and optionally an offset or an exposure column.  Returns the p x (3+p) frame `par_id, coef, Sig_invMcoef, [intercept,]
+    <features>`; a chunk that lacks an expected dummy level returns the all-zero block with a warning."""
+    return _count_model("probit", False, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                        dummy_factors_baseline, data_info)[0]
+
+
+def probit_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                      dummy_factors_baseline=[], data_info=[]):
+    """Probit log-likelihood of every estimator column of `par` on one partition, shaped like poisson_model_eval's output: one row, a
+    column per estimator (one pass without the information per column)."""
+    return _count_model_eval("probit", par, False, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                             dummy_factors_baseline, data_info)
+
+
+def cloglog_model(sample_df, Y_name, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                  dummy_factors_baseline=[], data_info=[]):
+    """probit_model under the complementary log-log link; exposure_name names the column of interval lengths or efforts."""
+    return _count_model("cloglog", False, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
+                        dummy_factors_baseline, data_info)[0]
+
+
+def cloglog_model_eval(sample_df, Y_name, par, fit_intercept=False, offset_name=None, exposure_name=None, dummy_info=[],
+                       dummy_factors_baseline=[], data_info=[]):
+    """probit_model_eval under the complementary log-log link."""
+    return _count_model_eval("cloglog", par, False, sample_df, Y_name, fit_intercept, offset_name, exposure_name, dummy_info,
                              dummy_factors_baseline, data_info)
 
 
